@@ -22,10 +22,17 @@ Other workloads (never the headline): `--config stress` = the bf16 core at one r
 10 000 concepts x 12 x 768 neurons) with a `gemm_stress` object (image-embedding x text-embedding GEMM: TFLOP/s and
 fraction of the 2.5 PFLOP/s bf16 MFMA peak); `--config core` = the fp32 core alone on random activations (dev / PMC runs).
 
-The JSON line carries `roofline` for the dominant kernel of the dissection core (K4, HBM roofline),
-`roofline_encoder` for the hand-written encoder kernel with the most GPU time (K9 attention, fp32 MFMA), both timed live
-with HIP events on the launch stream inside the timed region, `library_gemm_share` (hipBLASLt time / step) and
-`cpu_baseline` (rank 0, N=1 only): the like-for-like CPU rate of the same job on this box's host cores.
+A plain headline run does only what its headline figure needs: set-up, warm-up, the timed steps, the --dump-outputs files and
+the JSON line.  With --full the line also carries `stage_ms` / `core_ms`, `roofline` for the dominant kernel of the dissection
+core (K4, HBM roofline), `roofline_core`, `roofline_encoder` for the hand-written encoder kernel with the most GPU
+time (K9 attention, fp32 MFMA), all timed live with HIP events on the launch stream inside the timed region,
+`library_gemm_share` (hipBLASLt time / step), `gemm` (K1 alone), `gemm_stress` and `cpu_baseline` (rank 0, N=1 only): the
+like-for-like CPU rate of the same job on the host's cores.
+
+--dump-outputs DIR writes what the timed path handed its caller in the last step as DIR/<name>.npy (see dump_outputs); the
+inputs (model weights, probe images, activations) come from fixed seeds, so two builds can be compared output for output.
+Each run picks the encoder's hipBLASLt algorithms by timing (libmcd_blaslt.so), so two runs of the same build agree to the
+rounding of those GEMMs, not bit for bit: a few per cent of the `sim` entries differ, and near-tied concepts may swap ranks.
 """
 import argparse
 import json
@@ -95,7 +102,16 @@ def parse():
     ap.add_argument("--tune", action="store_true", help="let TunableOp tune unseen GEMM shapes")
     ap.add_argument("--stress-images", type=int, default=25000, help="--config stress: images of one rank's share")
     ap.add_argument("--stress-concepts", type=int, default=10000)
+    ap.add_argument("--full", action="store_true",
+                    help="the headline run also records HIP events around the stages and kernels of the timed steps and reports "
+                         "what they give (stage_ms, roofline, roofline_core, roofline_encoder, library_gemm_share), and after the "
+                         "timed steps measures K1 alone (gemm), the stress GEMM (gemm_stress) and the CPU baseline (cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
     if a.core_only:
         a.config = "core"
     a.preset = None
@@ -392,8 +408,18 @@ def run_headline(args):
 
     work = tempfile.mkdtemp(prefix="mcd_bench_")
     timer = StageTimer()
-    pipeline.STAGE_MARK = timer.mark
+    if args.full:
+        pipeline.STAGE_MARK = timer.mark
     step_no = [0]
+    last = {}
+    if args.dump_outputs:
+        # keep the scoring result of each step (the pipeline.DissectResult the driver writes its CSV from) for dump_outputs
+        describe = describe_broad_neurons.describe_layers
+
+        def keep_result(*a, **kw):
+            last["res"] = describe(*a, **kw)
+            return last["res"]
+        describe_broad_neurons.describe_layers = keep_result
 
     def one_step():
         i = step_no[0]
@@ -407,9 +433,11 @@ def run_headline(args):
     barrier = make_barrier(world)
     for _ in range(args.warmup):
         one_step()
-    data_utils.ATTENTION_EVENTS = attn_events = []   # K9 launches of the timed steps (every 8th is bracketed)
-    core.LINEAR_EVENTS = lin_events = []             # every hipBLASLt call of the timed steps
-    timer.on = True
+    attn_events = lin_events = None
+    if args.full:
+        data_utils.ATTENTION_EVENTS = attn_events = []   # K9 launches of the timed steps (every 8th is bracketed)
+        core.LINEAR_EVENTS = lin_events = []             # every hipBLASLt call of the timed steps
+        timer.on = True
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -419,9 +447,9 @@ def run_headline(args):
     timer.on = False
     data_utils.ATTENTION_EVENTS = None
     core.LINEAR_EVENTS = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last["res"], args.dump_outputs)
 
-    stage_ms = timer.stage_ms()
-    core_ms = sum(stage_ms.values())
     value = N_total * args.steps / elapsed
     mode = "strong: ONE probe set of %d images sharded over %d rank(s)" % (N_total, world) if strong else \
         "weak: %d images per GPU" % args.images
@@ -452,10 +480,14 @@ def run_headline(args):
                    "encoder_gemm": ("fp32 hipBLASLt; the ViT blocks' four GEMMs and the patch embedding with rank 0's best-of-32 pick "
                                     "per shape, broadcast to every rank (libmcd_blaslt.so); other nn.Linear calls: "
                                     + ("library defaults" if args.no_tunableop else "TunableOp picks (tunableop_gfx950.csv)"))},
-        "core_ms": round(core_ms, 4), "core_images_per_s": round(N_total / (core_ms / 1000.0), 1) if core_ms > 0 else None,
-        "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
     }
-    if rank == 0:
+    if args.full:
+        stage_ms = timer.stage_ms()
+        core_ms = sum(stage_ms.values())
+        out.update({"core_ms": round(core_ms, 4),
+                    "core_images_per_s": round(N_total / (core_ms / 1000.0), 1) if core_ms > 0 else None,
+                    "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()}})
+    if rank == 0 and args.full:
         k4_note = ("VALU-bound: U*K*C = %.3g correctly rounded logs per launch; the peak is the VALU issue rate over the floor of %.1f "
                    "lane-instructions per log (floor_breakdown); with conflict-free table lookups the kernel is 1.7 %% faster "
                    "(profiles/r03_k4_lds_ablation.txt); HBM traffic = algorithmic bytes"
@@ -520,11 +552,35 @@ def run_headline(args):
                 out["gemm_stress"] = {"error": str(e)}
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, out_dir, work, clip_model, images, words, widths, N_l)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     pipeline.STAGE_MARK = None
     shutil.rmtree(work, ignore_errors=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_SIM_BYTES = 60 << 20     # the similarity matrix's share of --dump-outputs' 64 MB (the other arrays: 25 values per neuron, 1.5 MB
+                              # at 9 216 neurons)
+
+
+def dump_outputs(res, path):
+    """--dump-outputs: the last timed step's pipeline.DissectResult -- what the driver writes its CSV from -- as <path>/<name>.npy:
+    `similarity` and `concept_ids` ([U, 10]: the CSV's similarity and description columns), `image_ids` ([U, 5]: its images
+    column) and `sim` ([U, C]: the soft-WPMI matrix they are selected from).  Ids are stored as float64 (exact).  A `sim` larger
+    than DUMP_SIM_BYTES is written as a fixed, seeded sample of its rows, whose indices go to `sim_rows`."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"similarity": res.vals.float(), "concept_ids": res.ids.double(), "image_ids": res.top_ids.double()}
+    sim = res.sim.float()
+    rows = max(1, DUMP_SIM_BYTES // (4 * max(1, sim.shape[1])))
+    if sim.shape[0] > rows:
+        pick = torch.randperm(sim.shape[0], generator=torch.Generator().manual_seed(0))[:rows].sort().values
+        arrays["sim_rows"] = pick.double()
+        sim = sim[pick.to(sim.device)]
+    arrays["sim"] = sim
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy())
 
 
 def k1_kernel_ms(core, dev, N, C, D=512, reps=20):
@@ -731,6 +787,8 @@ def run_core(args):
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0, world, dev, backend)
     assert bool(torch.isfinite(res.sim).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res, args.dump_outputs)
     stage_ms = timer.stage_ms()
     core_ms = sum(stage_ms.values())
     out = {

@@ -1,6 +1,6 @@
 """What one wrapper call costs the HOST (us per call, GPU-box Python): the pieces -- device context, current stream, allocation, event record --
 and whole core.* calls on kernels too short to hide them.  The scoring pass of one run is ~14 such calls: 0.73 ms of wall time for 0.5 ms of kernels
-(bench.py `core_ms` against the kernel trace), most of the difference in front of K1, where the stream starts dry."""
+(`bench.py --full`'s `core_ms` against the kernel trace), most of the difference in front of K1, where the stream starts dry."""
 import time, torch, ctypes, sys, os
 sys.path.insert(0, os.getcwd())
 import mammo_clip_dissect_amd

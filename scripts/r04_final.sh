@@ -21,10 +21,10 @@ if [ "$1" != quick ]; then
 fi
 rm -f $O/r04_parity_stats.txt
 MCD_STATS_FILE=$PWD/$O/r04_parity_stats.txt timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/r04_gputests.log 2>&1; echo "tests rc=$?"; tail -2 $O/r04_gputests.log
-python bench.py > $O/r04_bench.json 2> $O/r04_bench.err; echo "bench rc=$?"
+python bench.py --full > $O/r04_bench.json 2> $O/r04_bench.err; echo "bench rc=$?"
 python bench.py --config stress --steps 5 > $O/r04_stress_bench.json 2> $O/r04_stress.err; echo "stress rc=$?"
 rm -rf $O/kt_head $O/kt_stress
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_head -- python3 bench.py --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_head -- python3 bench.py --full --no-cpu-baseline > /dev/null 2>&1
 cp $(ls $O/kt_head/*/*kernel_stats.csv | head -1) $O/r04_bench_kernel_stats.csv
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_stress -- python3 bench.py --config stress --steps 5 > /dev/null 2>&1
 cp $(ls $O/kt_stress/*/*kernel_stats.csv | head -1) $O/r04_stress_kernel_stats.csv

@@ -21,11 +21,11 @@ if [ "$1" != quick ]; then
 fi
 rm -f $O/r05_parity_stats.txt
 MCD_STATS_FILE=$PWD/$O/r05_parity_stats.txt timeout -k 10 1100 python -m pytest tests -m gpu -x -q > $O/r05_gputests.log 2>&1; echo "tests rc=$?"; tail -2 $O/r05_gputests.log
-python bench.py > $O/r05_bench.json 2> $O/r05_bench.err; echo "bench rc=$?"
+python bench.py --full > $O/r05_bench.json 2> $O/r05_bench.err; echo "bench rc=$?"
 python bench.py --config stress --steps 5 > $O/r05_stress_bench.json 2> $O/r05_stress.err; echo "stress rc=$?"
-python bench.py --config cfg2 --no-cpu-baseline > $O/r05_bench_cfg2.json 2> $O/r05_cfg2.err; echo "cfg2 rc=$?"
+python bench.py --config cfg2 --full --no-cpu-baseline > $O/r05_bench_cfg2.json 2> $O/r05_cfg2.err; echo "cfg2 rc=$?"
 rm -rf $O/kt_head $O/kt_stress
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_head -- python3 bench.py --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_head -- python3 bench.py --full --no-cpu-baseline > /dev/null 2>&1
 cp $(ls $O/kt_head/*/*kernel_stats.csv | head -1) $O/r05_bench_kernel_stats.csv
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_stress -- python3 bench.py --config stress --steps 5 > /dev/null 2>&1
 cp $(ls $O/kt_stress/*/*kernel_stats.csv | head -1) $O/r05_stress_kernel_stats.csv

@@ -293,13 +293,13 @@ def test_bench_stress_line_carries_its_evidence(dev):
 
 
 def test_bench_headline_line_carries_the_stress_gemm_and_true_kernel_figures(dev):
-    """The driver-run headline line (a reduced probe set here) carries north_star's GEMM figure measured in the same run
+    """The driver-run headline line with --full (a reduced probe set here) carries north_star's GEMM figure measured in the same run
     (`gemm_stress`: the whole call and the kernel alone, at the full 25 000 x 10 000 x 512), `gemm` timed around the K1 kernel
     itself (not the host-gapped stage), and a K4 roofline whose `frac` is against the paper floor of instructions per log."""
     import json
     import subprocess
     import sys
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--images", "600", "--batch", "300",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "1", "--images", "600", "--batch", "300",
            "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, MCD_BENCH_NO_LAUNCH="1"))
     assert r.returncode == 0, r.stderr[-2000:]
@@ -325,3 +325,34 @@ def test_bench_headline_line_carries_the_stress_gemm_and_true_kernel_figures(dev
     roof = d["roofline"]
     assert roof["bound"] == "valu" and roof["valu_instr_per_log_floor"] == 7.5 and 0.0 < roof["frac"] < 1.0
     assert "valu_instr_per_log" not in roof                    # PMC-derived figures only at the shape they were counted on
+
+
+def test_bench_plain_headline_line_and_dumped_outputs(dev, tmp_path):
+    """A plain headline run (no --full) times exactly --steps steps and prints ONE line with the headline figure and none of --full's
+    measurements; --dump-outputs writes what its last timed step computed: the CSV's similarity / description / images columns
+    and the soft-WPMI matrix they are selected from."""
+    import json
+    import subprocess
+    import sys
+    out = str(tmp_path / "out")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "0", "--images", "600", "--batch", "300",
+           "--dump-outputs", out]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, MCD_BENCH_NO_LAUNCH="1"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["unit"] == "images/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 600 / (d["ms_per_step"] / 1000.0)) / d["value"] < 1e-3
+    moved = {"core_ms", "stage_ms", "roofline", "roofline_core", "roofline_encoder", "library_gemm_share", "gemm", "gemm_stress",
+             "cpu_baseline"}
+    assert not moved & set(d), moved & set(d)
+    a = {f[:-4]: np.load(os.path.join(out, f)) for f in os.listdir(out)}
+    assert set(a) == {"similarity", "concept_ids", "image_ids", "sim"}
+    U, C = 12 * 768, 763
+    assert a["sim"].shape == (U, C) and a["sim"].dtype == np.float32 and np.isfinite(a["sim"]).all()
+    assert a["similarity"].shape == (U, 10) and a["similarity"].dtype == np.float32
+    assert a["concept_ids"].shape == (U, 10) and a["image_ids"].shape == (U, 5) and a["image_ids"].dtype == np.float64
+    assert np.array_equal(np.take_along_axis(a["sim"], a["concept_ids"].astype(np.int64), axis=1), a["similarity"])
+    assert (np.diff(a["similarity"], axis=1) <= 0).all() and np.allclose(a["similarity"][:, 0], a["sim"].max(axis=1))
+    assert ((a["image_ids"] >= 0) & (a["image_ids"] < 600)).all()

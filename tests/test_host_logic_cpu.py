@@ -469,3 +469,34 @@ def test_bench_cfg2_preset_pairs_the_one_gpu_and_the_eight_gpu_job(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py"])
     a = bench.parse()
     assert a.preset is None and a.global_images is None and not a.align_shards     # the headline default is untouched
+
+
+def test_bench_dump_outputs_writes_the_result_within_its_budget(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last step's DissectResult as float32 / float64 .npy files, at most 64 MB in all -- the
+    whole similarity matrix at configs[1]'s shape, a fixed, seeded sample of its rows (indices in sim_rows) at the stress shape."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    from mammo_clip_dissect_amd.pipeline import DissectResult
+    U = 12 * 768
+    for C, sampled in ((763, False), (10000, True)):
+        sim = torch.randn(U, C, generator=torch.Generator().manual_seed(C))
+        vals, ids = sim.topk(10, dim=1)
+        top_ids = torch.randint(0, 10000, (U, 5), dtype=torch.int32, generator=torch.Generator().manual_seed(1))
+        res = DissectResult(["l%d" % i for i in range(12)], [768] * 12, sim, vals, ids.int(), top_ids, torch.zeros(U, 5), 10000)
+        got = []
+        for run in range(2):
+            d = str(tmp_path / ("c%d_%d" % (C, run)))
+            bench.dump_outputs(res, d)
+            files = sorted(os.listdir(d))
+            assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64 << 20
+            got.append({f[:-4]: np.load(os.path.join(d, f)) for f in files})
+        a = got[0]
+        assert set(a) == {"similarity", "concept_ids", "image_ids", "sim"} | ({"sim_rows"} if sampled else set())
+        assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+        assert np.array_equal(a["similarity"], vals.numpy()) and np.array_equal(a["concept_ids"], ids.numpy())
+        assert np.array_equal(a["image_ids"], top_ids.numpy())
+        rows = a["sim_rows"].astype(np.int64) if sampled else np.arange(U)
+        assert (len(rows) < U) == sampled and np.array_equal(a["sim"], sim.numpy()[rows])
+        assert all(np.array_equal(a[k], got[1][k]) for k in a)          # the same sample every time
