@@ -77,6 +77,24 @@ int mcd_center_cube_normalize_rows(const float* x, int64_t ldx, int64_t rows, in
                                    float* y, int64_t ldy, mcd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * K1a / K7 on rows that arrive in pieces: the rank-major message of an all-gather of neuron-major activation shards.
+ *      src holds G blocks, block g at src + g*ld_block; row u of block g at + u*ld_src, its first counts[g] floats valid.
+ *      The LOGICAL row u of length n = sum(counts) is the concatenation of its G pieces in block order.  For the rows
+ *      row0 <= u < row1 the prepared logical row is written densely to dst + (u - row0)*ldd:
+ *        mode 0: y = x / ||x||_2                                    bit-equal to mcd_normalize_rows on the logical row
+ *        mode 1: d = x - mean(x); c = d^3; y = c / max(||c||, min_norm)   bit-equal to mcd_center_cube_normalize_rows
+ *      (the same partition of logical indices over lanes, the same reduction trees, the same final division, for any
+ *      G and counts, empty pieces included).  Every element is read and written without an intermediate copy.
+ *      counts is a HOST array of G values (1 <= G <= 64); G = 1 with src = a neuron-major matrix is the plain
+ *      row preparation.  dst must not overlap src.
+ * replaces  the column normalisation of cos_similarity / cos_similarity_cubed   concept_vit/similarity.py:15-22, :40-41
+ *           on activations sharded over the images (pipeline.Dissector.finish with more than one rank)
+ * ------------------------------------------------------------------------------------------- */
+int mcd_prepare_rows_gathered(const float* src, int64_t ld_src, int64_t ld_block, int G, const int64_t* counts,
+                              int64_t n, int64_t row0, int64_t row1, int mode, float min_norm, float* dst, int64_t ldd,
+                              mcd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K1   P[n,c] = sum_k I[n,k] * T[c,k]      (I: [N,D] ld ldi, T: [C,D] ld ldt, P: [N,C] ld ldp)
  * replaces  clip_feats = image_features @ text_features.T                 concept_vit/utils.py:594
  *           (og_utils.py:501, CLIP_og_utils.py:160)

@@ -17,6 +17,8 @@ SIGNATURES = {
     "mcd_abi_version": (_int, []),
     "mcd_normalize_rows": (_int, [_p, _i64, _i64, _i64, _p, _i64, _p]),
     "mcd_center_cube_normalize_rows": (_int, [_p, _i64, _i64, _i64, _f, _p, _i64, _p]),
+    "mcd_prepare_rows_gathered": (_int, [_p, _i64, _i64, _int, ctypes.POINTER(_i64), _i64, _i64, _i64, _int, _f, _p, _i64,
+                                         _p]),
     "mcd_embed_gemm_workspace": (_sz, [_i64, _i64, _i64, _int]),
     "mcd_embed_gemm": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _int, _p, _i64, _p, _sz, _p]),
     "mcd_embed_gemm_exp_workspace": (_sz, [_i64, _i64, _i64]),
@@ -41,6 +43,7 @@ SIGNATURES = {
 }
 
 MCD_E_RANGE = -2
+MCD_E_UNSUPPORTED = -5
 
 _lib = None
 

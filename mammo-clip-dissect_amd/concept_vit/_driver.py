@@ -5,10 +5,15 @@ Two routes to the same CSV:
   * fused (the fast path): when save_activations has just run the extraction, its result is still resident in HBM
     (utils.Extraction) and every layer is scored in ONE pass -- P and S once (the reference recomputes them per layer,
     utils.py:570-594), one launch per kernel over all layers (pipeline.Dissector.finish) -- and the CSV is written by
-    pipeline.write_descriptions_csv.  Taken for soft_wpmi / wpmi.
+    pipeline.write_descriptions_csv.  Taken for soft_wpmi / wpmi, and for rank_reorder / cos_similarity /
+    cos_similarity_cubed in the og and clip drivers -- the broad driver passes top_k to the similarity function
+    (reference utils.py:602), which these three do not accept: TypeError there, as in the reference, so broad keeps the
+    per-layer route for them.
   * per layer (the reference's loop, line for line): when the activation cache already existed (nothing was
-    extracted), or for the other similarity functions: get_similarity_from_activations per layer from the cache files,
-    the `outputs` dict, DataFrame.to_csv.  The torch.max / torch.topk calls are the K6 / K3 HIP kernels.
+    extracted), for broad with the three functions above, or with MCD_DRIVER_PER_LAYER=1: get_similarity_from_activations
+    per layer from the cache files, the `outputs` dict, DataFrame.to_csv.  The torch.max / torch.topk calls are the K6 /
+    K3 HIP kernels.  The cache files are a single-process feature (utils.extract_and_save): a multi-rank run takes the
+    fused route.
 Both routes give the same bytes (tests/test_gpu_pipeline.py: test_fused_driver_equals_cache_driver)."""
 import datetime
 import json
@@ -41,7 +46,9 @@ def describe_layers(args, utils_mod, names_for, variant, pass_top_k, pass_d_prob
     """variant 'clip': top-1 description (describe_clip_neurons.py:64); 'og': top-10 (describe_og_neurons.py:99).
     live: the utils.Extraction save_activations returned (None: score from the cache files).
     Returns a pipeline.DissectResult (fused route) or a pandas DataFrame (per-layer route)."""
-    if live is not None and args.similarity_fn in ("soft_wpmi", "wpmi") and live.target_layers == list(args.target_layers) \
+    from ..pipeline import ROW_FNS
+    fused_fn = args.similarity_fn in ("soft_wpmi", "wpmi") or (args.similarity_fn in ROW_FNS and not pass_top_k)
+    if live is not None and fused_fn and live.target_layers == list(args.target_layers) \
             and os.environ.get("MCD_DRIVER_PER_LAYER", "0") != "1":
         # reference: utils.py:602 passes top_k (describe_broad_neurons.py:94-96); og_utils.py:508 / CLIP_og_utils.py:165
         # do not, so the similarity function's own default applies (100 / 28)

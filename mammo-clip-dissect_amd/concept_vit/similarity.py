@@ -14,6 +14,9 @@ Differences, all deliberate:
     (similarity.py:119).  The mirror draws the same permutations in the same order (5 per neuron, neuron by
     neuron) from the same generator, so under torch.manual_seed(s) both produce the same scores; only the
     permutation indices are made on the host, all arithmetic is in K8.
+
+pipeline.Dissector.finish computes all five functions for every layer at once, on one rank or image-sharded over
+several, with the same bits as these per-layer calls (the drivers' fused route).
 """
 import torch
 

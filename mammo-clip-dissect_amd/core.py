@@ -118,6 +118,41 @@ def center_cube_normalize_rows(x, min_norm=1e-3, out=None):
     return out
 
 
+PREP_MODES = {"normalize": 0, "center_cube": 1}
+
+
+@_on_device
+def prepare_rows_gathered(src, counts, rows, mode, min_norm=1e-3, out=None):
+    """normalize_rows (mode "normalize") or center_cube_normalize_rows (mode "center_cube") of logical rows that arrive in
+    pieces.  src: [G, R, ld] (the rank-major message of an all-gather: block g = rank g's [R, ld] rows, their first
+    counts[g] columns valid) or a 2-D [R, >= counts[0]] matrix for G = 1.  rows = (row0, row1).  Logical row u is the
+    concatenation of src[g, u, :counts[g]] over g; returns the prepared rows row0..row1-1 as [row1 - row0, sum(counts)],
+    bit-equal to the one-piece kernels on the concatenated rows."""
+    _need_gpu(src)
+    if src.dtype != torch.float32 or src.dim() not in (2, 3) or (src.shape[-1] > 1 and src.stride(-1) != 1):
+        raise TypeError("src must be a float32 [R, ld] or [G, R, ld] tensor with unit inner stride")
+    if src.dim() == 2:
+        src = src.unsqueeze(0)
+    G, R, _ = src.shape
+    counts = [int(c) for c in counts]
+    if len(counts) != G or any(c < 0 or c > src.shape[2] for c in counts):
+        raise ValueError("counts %s do not fit %d blocks of %d columns" % (counts, G, src.shape[2]))
+    row0, row1 = int(rows[0]), int(rows[1])
+    if not 0 <= row0 <= row1 <= R:
+        raise ValueError("rows [%d, %d) outside the %d rows of src" % (row0, row1, R))
+    n = sum(counts)
+    ld_src = src.stride(1) if R > 1 else src.shape[2]
+    ld_block = src.stride(0) if G > 1 else R * ld_src
+    if out is None:
+        out = torch.empty((row1 - row0, n), dtype=torch.float32, device=src.device)
+    out = _f32_out(out, "out")
+    arr = (ctypes.c_int64 * G)(*counts)
+    L = _lib.load()
+    check(L.mcd_prepare_rows_gathered(src.data_ptr(), ld_src, ld_block, G, arr, n, row0, row1, PREP_MODES[mode],
+                                      float(min_norm), out.data_ptr(), _ld(out), _stream()))
+    return out
+
+
 @_on_device
 def embed_gemm(I, T, mode="f32", out=None, use_workspace=True):
     """P = I @ T.T for I [N,D], T [C,D] (utils.py:594).  mode: "f32" (the parity mode: exact fp32 fma chains

@@ -1,6 +1,7 @@
 // k_rows.hip -- row-wise kernels over the embedding / similarity matrices (HBM-bound).
 //   K1a mcd_normalize_rows   concept_vit/utils.py:577-578   (bit-exact restatement of ATen's CPU norm + division)
 //   K2  mcd_row_softmax      concept_vit/similarity.py:54   (bit-exact restatement of ATen's CPU kernel)
+//   K7  mcd_center_cube_normalize_rows, and K1a / K7 on all-gathered row pieces (mcd_prepare_rows_gathered)
 // Rows live in registers between the passes; reductions are lane shuffles (no LDS).
 #include "mcd_common.h"
 #include <stdlib.h>
@@ -284,6 +285,102 @@ __global__ __launch_bounds__(256) void center_cube_normalize_kernel(const float*
     }
 }
 
+// ---- K1a / K7 on gathered rows: mcd_prepare_rows_gathered ----------------------------------------------
+// A logical row is the concatenation of G pieces (one per rank of an all-gather).  Both kernels keep the lane partition of
+// LOGICAL indices of the kernel they restate and walk the pieces in order, so every lane meets its indices in the same
+// order: piece g covers logical [off[g], off[g+1]) at xr + g*ld_block, and the lane that owns indices k = lane (mod S)
+// starts in it at off[g] + ((lane - off[g]) mod S).
+constexpr int GATHER_MAX_G = 64;
+struct GatherPieces {
+    int64_t off[GATHER_MAX_G + 1];   // off[0] = 0, off[G] = n
+};
+
+// K1a's order (the streaming form: rows of thousands of images): 8 lanes per row, lane j owns the chain over k = j (mod 8)
+// below full = n - n % 8, the tail one element at a time (product + add up to unfused_end, fused after), true division.
+__global__ __launch_bounds__(64) void prepare_rows_norm_kernel(const float* src, int64_t ld_src, int64_t ld_block, int G,
+                                                                GatherPieces pc, int64_t row0, int64_t rows, float* y,
+                                                                int64_t ldy) {
+    const int j = threadIdx.x & 7;
+    int64_t row = (int64_t)blockIdx.x * NORM_ROWS_PER_BLOCK + (threadIdx.x >> 3);
+    const bool live = row < rows;
+    if (!live) row = rows - 1;  // keep the shuffles below convergent
+    const float* xr = src + (row0 + row) * ld_src;
+    const int64_t d = pc.off[G];
+    const int64_t full = d - d % 8;
+    float acc = 0.f;
+    for (int g = 0; g < G; ++g) {
+        const int64_t a = pc.off[g], b = pc.off[g + 1] < full ? pc.off[g + 1] : full;
+        const float* xs = xr + g * ld_block - a;   // xs[k] = logical element k of this piece
+#pragma unroll 8
+        for (int64_t k = a + ((j - a) & 7); k < b; k += 8) {
+            const float t = xs[k];
+            acc = __builtin_fmaf(t, t, acc);
+        }
+    }
+    float ss = __shfl(acc, 0, 8);
+#pragma unroll
+    for (int l = 1; l < 8; ++l) ss = ss + __shfl(acc, l, 8);
+    const int64_t unfused_end = full + (d - full) / 4 * 4;
+    for (int g = 0; g < G; ++g) {
+        const int64_t a = pc.off[g], b = pc.off[g + 1];
+        const float* xs = xr + g * ld_block - a;
+        for (int64_t k = a > full ? a : full; k < b; ++k) {
+            const float t = xs[k];
+            if (k < unfused_end) {
+                const float sq = t * t;
+                ss = ss + sq;
+            } else {
+                ss = __builtin_fmaf(t, t, ss);
+            }
+        }
+    }
+    const float nrm = sqrtf(ss);
+    if (!live) return;
+    float* yr = y + row * ldy;
+    for (int g = 0; g < G; ++g) {
+        const int64_t a = pc.off[g], b = pc.off[g + 1];
+        const float* xs = xr + g * ld_block - a;
+        for (int64_t k = a + ((j - a) & 7); k < b; k += 8) yr[k] = xs[k] / nrm;
+    }
+}
+
+// K7's order: one 256-thread workgroup per row, thread t owns k = t (mod 256) in each of the three passes, block256_sum().
+__global__ __launch_bounds__(256) void prepare_rows_ccn_kernel(const float* src, int64_t ld_src, int64_t ld_block, int G,
+                                                                GatherPieces pc, int64_t row0, float min_norm, float* y,
+                                                                int64_t ldy) {
+    __shared__ float s_red[4];
+    const int t = threadIdx.x;
+    const float* xr = src + (row0 + (int64_t)blockIdx.x) * ld_src;
+    float* yr = y + (int64_t)blockIdx.x * ldy;
+    const int64_t n = pc.off[G];
+    float s = 0.f;
+    for (int g = 0; g < G; ++g) {
+        const int64_t a = pc.off[g], b = pc.off[g + 1];
+        const float* xs = xr + g * ld_block - a;
+        for (int64_t k = a + ((t - a) & 255); k < b; k += 256) s += xs[k];
+    }
+    const float mean = block256_sum(s, s_red) / (float)n;
+    float ss = 0.f;
+    for (int g = 0; g < G; ++g) {
+        const int64_t a = pc.off[g], b = pc.off[g + 1];
+        const float* xs = xr + g * ld_block - a;
+        for (int64_t k = a + ((t - a) & 255); k < b; k += 256) {
+            const float d = xs[k] - mean;
+            const float c = (d * d) * d;
+            ss += c * c;
+        }
+    }
+    const float nrm = fmaxf(sqrtf(block256_sum(ss, s_red)), min_norm);
+    for (int g = 0; g < G; ++g) {
+        const int64_t a = pc.off[g], b = pc.off[g + 1];
+        const float* xs = xr + g * ld_block - a;
+        for (int64_t k = a + ((t - a) & 255); k < b; k += 256) {
+            const float d = xs[k] - mean;
+            yr[k] = ((d * d) * d) / nrm;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int mcd_normalize_rows(const float* x, int64_t ldx, int64_t n, int64_t d, float* y, int64_t ldy,
@@ -337,5 +434,45 @@ extern "C" int mcd_center_cube_normalize_rows(const float* x, int64_t ldx, int64
     hipLaunchKernelGGL(center_cube_normalize_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, x, ldx, n,
                        min_norm, y, ldy);
     MCD_LAUNCH_CHECK("center_cube_normalize_kernel");
+    return MCD_OK;
+}
+
+extern "C" int mcd_prepare_rows_gathered(const float* src, int64_t ld_src, int64_t ld_block, int G, const int64_t* counts,
+                                         int64_t n, int64_t row0, int64_t row1, int mode, float min_norm, float* dst,
+                                         int64_t ldd, mcd_stream_t stream) {
+    MCD_REQUIRE(src && dst && counts, MCD_E_ARG, "mcd_prepare_rows_gathered: NULL pointer");
+    MCD_REQUIRE(G >= 1, MCD_E_ARG, "mcd_prepare_rows_gathered: G=%d", G);
+    MCD_REQUIRE(G <= GATHER_MAX_G, MCD_E_UNSUPPORTED, "mcd_prepare_rows_gathered: G=%d > %d pieces not supported", G,
+                GATHER_MAX_G);
+    MCD_REQUIRE(mode == 0 || mode == 1, MCD_E_ARG, "mcd_prepare_rows_gathered: mode=%d", mode);
+    MCD_REQUIRE(n > 0 && ld_src > 0 && ldd >= n && row0 >= 0 && row1 >= row0, MCD_E_ARG,
+                "mcd_prepare_rows_gathered: bad shape n=%lld ld_src=%lld ldd=%lld rows [%lld, %lld)", (long long)n,
+                (long long)ld_src, (long long)ldd, (long long)row0, (long long)row1);
+    // the blocks must not overlap: every row of the range fits in one block
+    MCD_REQUIRE(G == 1 || ld_block >= row1 * ld_src, MCD_E_ARG, "mcd_prepare_rows_gathered: ld_block=%lld < rows*ld_src",
+                (long long)ld_block);
+    GatherPieces pc;
+    pc.off[0] = 0;
+    for (int g = 0; g < G; ++g) {
+        MCD_REQUIRE(counts[g] >= 0 && counts[g] <= ld_src, MCD_E_ARG,
+                    "mcd_prepare_rows_gathered: counts[%d]=%lld outside [0, ld_src=%lld]", g, (long long)counts[g],
+                    (long long)ld_src);
+        pc.off[g + 1] = pc.off[g] + counts[g];
+    }
+    MCD_REQUIRE(pc.off[G] == n, MCD_E_ARG, "mcd_prepare_rows_gathered: counts add up to %lld, not n=%lld",
+                (long long)pc.off[G], (long long)n);
+    const int64_t rows = row1 - row0;
+    if (rows == 0) return MCD_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == 0) {
+        hipLaunchKernelGGL(prepare_rows_norm_kernel, dim3((unsigned)mcd_cdiv(rows, NORM_ROWS_PER_BLOCK)), dim3(64), 0, st, src,
+                           ld_src, ld_block, G, pc, row0, rows, dst, ldd);
+        MCD_LAUNCH_CHECK("prepare_rows_norm_kernel");
+    } else {
+        MCD_REQUIRE(rows <= 0x7fffffffLL, MCD_E_UNSUPPORTED, "mcd_prepare_rows_gathered: too many rows");
+        hipLaunchKernelGGL(prepare_rows_ccn_kernel, dim3((unsigned)rows), dim3(256), 0, st, src, ld_src, ld_block, G, pc, row0,
+                           min_norm, dst, ldd);
+        MCD_LAUNCH_CHECK("prepare_rows_ccn_kernel");
+    }
     return MCD_OK;
 }

@@ -15,7 +15,14 @@ number of ranks):
   1. S shard [N/G, C]                          -> all-gather -> S [N, C] on every rank
   2. local top-K (value, global image index)   -> all-gather -> merged to the global top-K per neuron
   3. neurons are split over the ranks for K4   -> all-gather of prob_d_given_e [sum U / G, C]
-K5/K6 are replicated.  Shards may be UNEVEN (the reference walks any N, utils.py:174-181): every rank tells the
+K5/K6 are replicated.
+rank_reorder, cos_similarity and cos_similarity_cubed (Dissector._finish_rows) score P and the activation rows themselves:
+  1. P shard [N/G, C] (no softmax)            -> all-gather -> P [N, C] on every rank
+  2. cos_*: activation shard [sum U, N/G]     -> all-gather -> this rank's neuron slice prepared (K1a / K7) straight out
+     of the rank-major message (mcd_prepare_rows_gathered), K1 over the images with the prepared P^T;
+     rank_reorder: the local top-n merged as for top-K, the baseline permutations drawn on the host by every rank, K8
+  3. the slices' [sum U / G, C] scores        -> all-gather; K6 replicated
+Shards may be UNEVEN (the reference walks any N, utils.py:174-181): every rank tells the
 others how many images it holds, shorter shards are padded for the fixed-size all-gather and the padding is dropped
 on arrival, so a probe set of any size can be split over any number of ranks (shard_bounds()).
 The compute backend (`ops`) and the row all-gather (`gather`) are injectable so the host logic above can be exercised
@@ -27,12 +34,17 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import _lib
 from . import core as _hip_ops
 
 
 # Optional callable(name) invoked between the stages of every Dissector.finish ("start", "gemm", "softmax", ...): bench.py
 # records HIP events there when the dissection runs inside the drop-in driver, which has no argument for it.
 STAGE_MARK = None
+
+# the similarity functions scored from P and the activation ROWS themselves (no softmax, no WPMI sums): finish() takes
+# _finish_rows() for them
+ROW_FNS = ("rank_reorder", "cos_similarity", "cos_similarity_cubed")
 
 
 def _round_up(x, m):
@@ -147,19 +159,33 @@ class Dissector:
         self.C, self.D = int(n_concepts), int(embed_dim)
         self.pool_mode = pool_mode
         self.gemm_mode = gemm_mode
-        self.set_scoring(similarity_fn, top_k, a=a, lam=lam, min_prob=min_prob, p_start=p_start, p_end=p_end)
+        self.set_scoring(similarity_fn, None if similarity_fn in ROW_FNS else top_k, a=a, lam=lam, min_prob=min_prob,
+                         p_start=p_start, p_end=p_end)
         self.ldA = _round_up(max(self.n_local, 1), 64)
         self.At = torch.zeros((self.U, self.ldA), dtype=torch.float32, device=self.device)  # neuron-major
         self.E_img = torch.zeros((self.n_local, self.D), dtype=torch.float32, device=self.device)
         self.cursor = 0
 
     def set_scoring(self, similarity_fn="soft_wpmi", top_k=None, a=None, lam=None, min_prob=1e-7, p_start=0.998,
-                    p_end=0.97):
+                    p_end=0.97, p=3, top_fraction=0.05, scale_p=0.5, min_norm=1e-3):
         """Which similarity function finish() computes and with what parameters (defaults: the reference's,
-        similarity.py:49 / :75).  Only the scoring side depends on it, so the drivers can extract first and choose
-        afterwards."""
+        similarity.py:49 / :75 / :99 / :7).  Only the scoring side depends on it, so the drivers can extract first and choose
+        afterwards.  soft_wpmi / wpmi use top_k, a, lam, min_prob, p_start, p_end; rank_reorder uses p, top_fraction,
+        scale_p; cos_similarity_cubed uses min_norm; cos_similarity none."""
+        if similarity_fn in ROW_FNS:
+            if top_k is not None:     # the reference's functions take no top_k (utils.py:602 passes one: TypeError there too)
+                raise TypeError("%s() got an unexpected keyword argument 'top_k'" % similarity_fn)
+            if self.gemm_mode == "bf16":
+                raise NotImplementedError("gemm_mode='bf16' never materialises fp32 P, which %s scores: use 'f32', "
+                                          "'bf16x3' or 'bf16_p'" % similarity_fn)
+            self.similarity_fn = similarity_fn
+            self.top_k = 0
+            self.rr_p, self.top_fraction, self.scale_p = float(p), float(top_fraction), float(scale_p)
+            self.min_norm = float(min_norm)
+            return
         if similarity_fn not in ("soft_wpmi", "wpmi"):
-            raise NotImplementedError("fused pipeline supports soft_wpmi and wpmi (got %r)" % (similarity_fn,))
+            raise NotImplementedError("fused pipeline supports soft_wpmi, wpmi, %s (got %r)" % (", ".join(ROW_FNS),
+                                                                                             similarity_fn))
         self.similarity_fn = similarity_fn
         soft = similarity_fn == "soft_wpmi"
         self.top_k = int(top_k if top_k is not None else (100 if soft else 28))
@@ -226,6 +252,36 @@ class Dissector:
             return full
         return torch.cat([full[r * m:r * m + lens[r]] for r in range(self.world)], dim=0)
 
+    def _col_topk_global(self, K, mark):
+        """Per neuron of every layer, the K most activating images of the WHOLE probe set, sorted descending, with global
+        image indices (torch.topk(target_feats, K, dim=0) per layer): K3 on this rank's shard, then -- with more than one
+        rank -- the (value, global index) candidates of every rank all-gathered and merged by a second K3.  Ties go to the
+        lower image index at any rank count, so the result is the one-rank result.  Returns (vals, idx) [U, K]."""
+        ops, G, N_l = self.ops, self.world, self.n_local
+        Kl = min(K, N_l)
+        if Kl > 0:
+            mark("topk:begin")        # K3 alone (the local selection; the cross-shard merge below is a second, small launch)
+            vals, idx = ops.col_topk(self.At[:, :N_l], Kl, neuron_major=True)
+            mark("topk:end")
+        else:
+            vals = torch.zeros((self.U, 0), dtype=torch.float32, device=self.device)
+            idx = torch.zeros((self.U, 0), dtype=torch.int32, device=self.device)
+        if G > 1:
+            # one message per rank: [U, 2*Km] = (values | global indices), the ranks' first min(K, n_r) columns valid
+            kls = [min(K, n) for n in self.counts]
+            Km = max(kls)
+            packed = torch.zeros((self.U, 2 * Km), dtype=torch.float32, device=self.device)
+            packed[:, :Kl] = vals
+            # (int32 indices carried as float32 BITS: only ever copied -- an all-gather moves bytes.  A reducing collective
+            # (all-reduce, reduce-scatter) would do arithmetic on these bit patterns and destroy them: never swap one in.)
+            packed[:, Km:Km + Kl] = (idx + self.row0).view(torch.float32)
+            allp = self._all_gather_rows(packed).view(G, self.U, 2 * Km)
+            cand_v = torch.cat([allp[r, :, :kls[r]] for r in range(G)], dim=1).contiguous()
+            cand_i = torch.cat([allp[r, :, Km:Km + kls[r]] for r in range(G)], dim=1).contiguous().view(torch.int32)
+            vals, pos = ops.col_topk(cand_v, K, neuron_major=True)  # ties -> lower position = lower image index
+            idx = torch.gather(cand_i, 1, pos.long())
+        return vals, idx
+
     # ---- scoring side ----------------------------------------------------------------------------
     def finish(self, E_txt, k_desc=10, k_img=5, marks=None):
         """Score every neuron of every layer.  E_txt: [C, D] text embeddings (replicated on every rank).
@@ -234,6 +290,8 @@ class Dissector:
         mark = marks if marks is not None else (STAGE_MARK if STAGE_MARK is not None else (lambda name: None))
         if self.cursor != self.n_local:
             raise RuntimeError("dissector holds %d of %d images" % (self.cursor, self.n_local))
+        if self.similarity_fn in ROW_FNS:
+            return self._finish_rows(E_txt, k_desc, k_img, mark)
         G, N_l, K = self.world, self.n_local, self.top_k
         if K > self.n_total or k_img > self.n_total:
             raise RuntimeError("selected index k out of range")
@@ -282,28 +340,7 @@ class Dissector:
                     rinv = self._all_gather_ragged(rinv.view(-1, 1), self.counts).view(-1)
                 mark("gather_S")
             # similarity.py:55 for all layers at once (local shard), then the cross-shard merge
-            Kl = min(K, N_l)
-            if Kl > 0:
-                mark("topk:begin")        # K3 alone (the local selection; the cross-shard merge below is a second, small launch)
-                vals, idx = ops.col_topk(self.At[:, :N_l], Kl, neuron_major=True)
-                mark("topk:end")
-            else:
-                vals = torch.zeros((self.U, 0), dtype=torch.float32, device=self.device)
-                idx = torch.zeros((self.U, 0), dtype=torch.int32, device=self.device)
-            if G > 1:
-                # one message per rank: [U, 2*Km] = (values | global indices), the ranks' first min(K, n_r) columns valid
-                kls = [min(K, n) for n in self.counts]
-                Km = max(kls)
-                packed = torch.zeros((self.U, 2 * Km), dtype=torch.float32, device=self.device)
-                packed[:, :Kl] = vals
-                # (int32 indices carried as float32 BITS: only ever copied -- an all-gather moves bytes.  A reducing collective
-                # (all-reduce, reduce-scatter) would do arithmetic on these bit patterns and destroy them: never swap one in.)
-                packed[:, Km:Km + Kl] = (idx + self.row0).view(torch.float32)
-                allp = self._all_gather_rows(packed).view(G, self.U, 2 * Km)
-                cand_v = torch.cat([allp[r, :, :kls[r]] for r in range(G)], dim=1).contiguous()
-                cand_i = torch.cat([allp[r, :, Km:Km + kls[r]] for r in range(G)], dim=1).contiguous().view(torch.int32)
-                vals, pos = ops.col_topk(cand_v, K, neuron_major=True)  # ties -> lower position = lower image index
-                idx = torch.gather(cand_i, 1, pos.long())
+            vals, idx = self._col_topk_global(K, mark)
             mark("topk")
             # similarity.py:59-65: neurons split over the ranks
             per = (self.U + G - 1) // G
@@ -336,13 +373,122 @@ class Dissector:
                              vals[:, :k_img].contiguous(), self.n_total)
 
 
+    def _finish_rows(self, E_txt, k_desc, k_img, mark):
+        """finish() for rank_reorder, cos_similarity and cos_similarity_cubed (similarity.py:99-132, :33-47, :7-31), all
+        layers at once:
+          P        K1a / K1 on this rank's images, then all-gathered to [N, C] on every rank (no softmax)
+          cos_*    Pt = K1a / K7 over transpose(P) [C, N] (replicated, small); this rank's slice of neurons prepared by
+                   mcd_prepare_rows_gathered straight out of the all-gathered activation shards (G = 1: out of At, which
+                   stays untouched -- the cache writer reads it afterwards); K1 A_prep @ Pt^T gives the slice's [u, C]
+          rank_reorder  the global top-n images per neuron (K3 + the cross-shard merge), the reference's permutations
+                   drawn on the host by every rank, K8 on the slice
+        then the slices are all-gathered and K6 picks the top concepts, as for soft_wpmi.  The per-neuron arithmetic is
+        the per-layer drop-in's (similarity.py mirror), so the result is bit-identical to it at any rank count."""
+        ops = self.ops
+        G, N_l, N = self.world, self.n_local, self.n_total
+        fn = self.similarity_fn
+        if k_img > N:
+            raise RuntimeError("selected index k out of range")
+        top_n = 0
+        if fn == "rank_reorder":
+            top_n = int(N * self.top_fraction)                                  # similarity.py:106
+            if top_n < 1:
+                raise RuntimeError("rank_reorder: top_fraction*N = %d images (the reference divides by zero here)" % top_n)
+            if top_n > 4096:      # K3 and K8 stop there; raised before any collective, on every rank alike
+                raise _hip_ops.McdError(_lib.MCD_E_UNSUPPORTED, "mcd_col_topk: K=%d > 4096 not supported" % top_n)
+            if top_n > N:
+                raise RuntimeError("selected index k out of range")
+        per = (self.U + G - 1) // G                        # neurons split over the ranks, as for K4
+        u0, u1 = min(self.rank * per, self.U), min((self.rank + 1) * per, self.U)
+        with torch.no_grad():
+            mark("start")
+            T = ops.normalize_rows(E_txt.to(self.device, torch.float32))
+            if N_l > 0:
+                I = ops.normalize_rows(self.E_img)
+                mode = {"bf16_p": "bf16"}.get(self.gemm_mode, self.gemm_mode)
+                mark("gemm:begin")
+                P = ops.embed_gemm(I, T, mode=mode) if mode != "f32" else ops.embed_gemm(I, T)
+                mark("gemm:end")
+            else:                                                # a rank without images only takes part
+                P = torch.zeros((0, self.C), dtype=torch.float32, device=self.device)
+            mark("gemm")
+            if G > 1:
+                P = self._all_gather_ragged(P, self.counts)     # [N, C], the global image order
+                mark("gather_P")
+            sim_l = torch.empty((per, self.C), dtype=torch.float32, device=self.device)
+            if u1 - u0 < per:
+                sim_l[u1 - u0:].zero_()          # rows of the all-gather message that no neuron of this rank fills
+            if fn == "rank_reorder":
+                vals, idx = self._col_topk_global(top_n, mark)                  # similarity.py:107
+                mark("topk")
+                if P.stride(0) % 4 != 0:       # K8's 16-byte gathers want whole quads per row: pad P once, not per call
+                    Pp = torch.zeros((P.shape[0], _round_up(self.C, 4)), dtype=torch.float32, device=self.device)
+                    Pp[:, :self.C] = P
+                    P = Pp[:, :self.C]
+                # similarity.py:119 layer by layer; K8 on a layer's part of the slice is queued as soon as its permutations
+                # are drawn, so the GPU scores one layer while the host draws the next
+                for a, b, perms in self._rank_reorder_perms(top_n, u0, u1):
+                    ops.rank_reorder(P, vals[a:b], idx[a:b], perms.to(self.device, non_blocking=True), p=self.rr_p,
+                                     scale_p=self.scale_p, out=sim_l[a - u0:b - u0])
+                mark("rank_reorder")
+            else:
+                prep = "normalize" if fn == "cos_similarity" else "center_cube"
+                mark("prep:begin")             # transpose + K1a / K7 of P, the gather of the activations, their preparation
+                Pt = ops.transpose(P)                                           # [C, N]
+                if prep == "normalize":
+                    Pt = ops.normalize_rows(Pt, out=Pt)
+                else:
+                    Pt = ops.center_cube_normalize_rows(Pt, min_norm=self.min_norm, out=Pt)
+                if G > 1:
+                    # rank r's message: its [U, n_max] shard, the first counts[r] columns valid -> [G, U, n_max] rank-major
+                    msg = torch.zeros((self.U, self.n_max), dtype=torch.float32, device=self.device)
+                    msg[:, :N_l] = self.At[:, :N_l]
+                    src = self._all_gather_rows(msg).view(G, self.U, self.n_max)
+                    mark("gather_A")
+                else:
+                    src = self.At
+                A_prep = torch.empty((u1 - u0, N), dtype=torch.float32, device=self.device)
+                if u1 > u0:
+                    ops.prepare_rows_gathered(src, self.counts, (u0, u1), prep, min_norm=self.min_norm, out=A_prep)
+                mark("prep:end")
+                mark("prep")
+                mark("cos_gemm:begin")         # K1 over the images: [u1 - u0, N] x [C, N]^T
+                if u1 > u0:
+                    ops.embed_gemm(A_prep, Pt, out=sim_l[:u1 - u0])
+                mark("cos_gemm:end")
+                mark("cos_gemm")
+            sim = self._all_gather_rows(sim_l)[:self.U] if G > 1 else sim_l
+            mark("row_topk:begin")     # K6 alone
+            v, ids = ops.row_topk(sim, min(k_desc, self.C))
+            mark("row_topk:end")
+            mark("row_topk")
+            # the images column: torch.topk(target_feats, k=5, dim=0) per layer (describe_og_neurons.py:100)
+            if fn == "rank_reorder" and top_n >= k_img:
+                tv, ti = vals[:, :k_img], idx[:, :k_img]     # a prefix of the sorted top-n (same tie rule)
+            else:
+                tv, ti = self._col_topk_global(k_img, lambda name: None)
+        return DissectResult(self.layer_names, self.layer_widths, sim, v, ids, ti.contiguous(), tv.contiguous(), N)
+
+    def _rank_reorder_perms(self, top_n, u0, u1):
+        """similarity.py:119 for every layer: five torch.randperm(top_n) per neuron on torch's global CPU generator, layer by
+        layer and neuron by neuron -- the order of the per-layer loop.  Every rank draws the whole stream, so every rank's
+        generator ends where a one-rank run's does.  Yields (a, b, perms) per layer for this rank's neurons a..b of it
+        (u0 <= a < b <= u1): int32 [b - a, 5, top_n], pinned host memory when a GPU is present."""
+        pin = self.device.type == "cuda"
+        for o0, o1 in zip(self.offsets[:-1], self.offsets[1:]):
+            draws = [torch.randperm(top_n) for _ in range(5 * (o1 - o0))]
+            a, b = max(u0, o0), min(u1, o1)
+            if a < b:
+                perms = torch.stack(draws[5 * (a - o0):5 * (b - o0)]).view(b - a, 5, top_n).to(torch.int32)
+                yield a, b, (perms.pin_memory() if pin else perms)
+
     def finish_graphed(self, E_txt, k_desc=10, k_img=5):
         """finish() as ONE hipGraph launch (single rank): the ~12 kernels of the scoring side are captured once --
         nothing inside the C ABI allocates or synchronises, and torch's allocations during capture come from the
         graph's private pool -- and replayed on later calls with the new text embeddings copied into the captured
         input.  Same bits as finish().  The returned tensors are the graph's output buffers: they are overwritten by
         the next replay."""
-        if self.world > 1:
+        if self.world > 1 or self.similarity_fn in ROW_FNS:   # (rank_reorder draws on the host generator: nothing to capture)
             return self.finish(E_txt, k_desc=k_desc, k_img=k_img)
         key = (int(k_desc), int(k_img))
         if getattr(self, "_graph_key", None) != key:
