@@ -256,6 +256,18 @@ int mcd_rank_reorder(const float* P, int64_t ldP, int64_t N, int64_t C, const fl
 int mcd_vit_attention(const float* qkv, int64_t B, int64_t T, int64_t H, float* out, mcd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * K9L  the same attention for long sequences: 1 <= T <= 32 768 tokens (2048 x 2048 at patch 16 is 16 385), the same
+ *      layout, arithmetic and alignment as K9, and one image's qkv block (T * 3 * H * 64 floats) under 2^31 bytes
+ *      (MCD_E_UNSUPPORTED past either limit; the whole batch may be larger).  One workgroup per (image, head, block of
+ *      256 queries) streams all of that head's 32-key tiles through K9's LDS ring; a query's arithmetic is K9's, in
+ *      the same order, so for T <= 256 the result is K9's, bit for bit, and it does not depend on the query block or
+ *      the batch.  No T x T buffer.  The query blocks of one (image, head) are placed on one XCD (speed only).
+ * replaces  the attention inside ViTModel(...) at high resolution          model/modules/image_encoder.py:37
+ *           nn.MultiheadAttention(x, x, x, need_weights=False)            concept_vit/clip/model.py:171-183
+ * ------------------------------------------------------------------------------------------- */
+int mcd_vit_attention_long(const float* qkv, int64_t B, int64_t T, int64_t H, float* out, mcd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K10  fp32 LayerNorm over the last dimension (biased variance, like torch): rows x D contiguous, D a multiple of 4
  *      up to 2048, pointers 16-byte aligned.  One wave per row, the row register-resident, two-pass statistics.
  *      Encoder-side op, fp32-accurate (<= 1e-6 relative from torch's), no bit-exactness claim.

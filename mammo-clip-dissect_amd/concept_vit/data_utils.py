@@ -24,9 +24,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 PROJ_DIM = 512
-# The image tower's mask-free fp32 attention runs on the HIP kernel K9; MCD_NO_HIP_ATTENTION=1 (or setting this to
-# False) keeps PyTorch's SDPA, e.g. to time one against the other.  Masked (text tower), autograd or non-fp32 calls
-# always take SDPA.
+# The image tower's mask-free fp32 attention runs on the HIP kernels K9 (T <= 256) and K9L (longer sequences, the
+# high-resolution towers); MCD_NO_HIP_ATTENTION=1 (or setting this to False) keeps PyTorch's SDPA, e.g. to time one
+# against the other.  Masked (text tower), autograd or non-fp32 calls always take SDPA (attention_route).
 HIP_ATTENTION = os.environ.get("MCD_NO_HIP_ATTENTION", "0") != "1"
 # bench.py sets this to a list to time K9 inside the forwards: every 8th call appends (start, end, B, T, heads) with
 # two HIP events recorded on the launch stream around the kernel.
@@ -74,6 +74,20 @@ def _fused_residual_ok(x):
 # ------------------------------------------------------------------------------------------------------
 # ViT-B/16 tower (module names follow HF ViTModel: embeddings / encoder.layer[i] / layernorm)
 # ------------------------------------------------------------------------------------------------------
+def attention_route(T, D, heads, masked, on_gpu, dtype, needs_grad):
+    """Which attention _Attention.heads_out takes for T tokens of width D = 64 * heads: 'k9' (T <= 256), 'long' (K9L,
+    up to core.VIT_ATTENTION_LONG_MAX_T tokens and one image's qkv under 2^31 bytes) or 'sdpa' (masked, autograd,
+    non-fp32 or off-GPU calls, HIP_ATTENTION off, other head widths, and anything past K9L's limits)."""
+    from .. import core
+    if not (HIP_ATTENTION and not masked and on_gpu and dtype == torch.float32 and D == 64 * heads and not needs_grad):
+        return "sdpa"
+    if T <= core.VIT_ATTENTION_MAX_T:
+        return "k9"
+    if T <= core.VIT_ATTENTION_LONG_MAX_T and T * 3 * D * 4 < 2 ** 31:
+        return "long"
+    return "sdpa"
+
+
 class _Attention(nn.Module):
     def __init__(self, dim, heads):
         super().__init__()
@@ -88,8 +102,9 @@ class _Attention(nn.Module):
         """The concatenated head outputs [B, T, D], i.e. attention before the output projection."""
         B, T, D = x.shape
         qkv = _linear(self.qkv, x)
-        if (HIP_ATTENTION and mask is None and qkv.is_cuda and qkv.dtype == torch.float32 and D == 64 * self.heads
-                and T <= 256 and not (torch.is_grad_enabled() and qkv.requires_grad)):
+        route = attention_route(T, D, self.heads, mask is not None, qkv.is_cuda, qkv.dtype,
+                                torch.is_grad_enabled() and qkv.requires_grad)
+        if route == "k9":
             # K9 (csrc/k_attn.hip): one launch, reads the fused projection's layout, writes the proj input's
             from .. import core
             global _attention_calls
@@ -102,6 +117,10 @@ class _Attention(nn.Module):
                 ATTENTION_EVENTS.append((e0, e1, B, T, self.heads))
                 return o
             return core.vit_attention(qkv, self.heads)
+        if route == "long":
+            # K9L (csrc/k_attn.hip): the same layouts, one workgroup per 256 queries of a head, no T x T buffer
+            from .. import core
+            return core.vit_attention_long(qkv, self.heads)
         q, k, v = qkv.view(B, T, 3, self.heads, D // self.heads).permute(2, 0, 3, 1, 4)
         o = F.scaled_dot_product_attention(q, k, v, attn_mask=mask)
         return o.transpose(1, 2).reshape(B, T, D)
@@ -141,14 +160,34 @@ class _Encoder(nn.Module):
         return x
 
 
+def image_hw(image_size):
+    """(H, W) of an image_size that is an int (square) or an (H, W) pair."""
+    if isinstance(image_size, (tuple, list)):
+        h, w = image_size
+        return int(h), int(w)
+    return int(image_size), int(image_size)
+
+
+def _parse_hw(text):
+    """'<S>' -> S (square, as before), '<H>x<W>' -> (H, W); None if `text` is neither."""
+    if text.isdigit():
+        return int(text)
+    h, sep, w = text.partition("x")
+    if sep and h.isdigit() and w.isdigit():
+        return int(h), int(w)
+    return None
+
+
 class ViTTower(nn.Module):
-    """[B,3,H,W] -> token sequence [B, 1+(H/16)*(W/16), 768]; hook points encoder.<list_name>[i]."""
+    """[B,3,H,W] -> token sequence [B, 1+(H/16)*(W/16), 768]; hook points encoder.<list_name>[i].  image_size is an int
+    (square) or (H, W): (H/16)*(W/16) + 1 position embeddings, e.g. 5 416 for Mammo-CLIP's 1520 x 912."""
 
     def __init__(self, image_size=224, patch=16, dim=768, depth=12, heads=12, mlp=3072, list_name="layer"):
         super().__init__()
         self.out_dim = dim
         self.patch_embed = nn.Conv2d(3, dim, patch, patch)
-        n = (image_size // patch) ** 2
+        h, w = image_hw(image_size)
+        n = (h // patch) * (w // patch)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, n + 1, dim))
         self.encoder = _Encoder(depth, dim, heads, mlp, list_name)
@@ -460,12 +499,15 @@ def _load_local(model, ckpt):
 def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, finetuned_ckpt=None, seed=0, image_size=224):
     """Returns (target model in eval mode, preprocess) -- reference data_utils.py:38-93.  Weights are
     random-init under `seed` unless a local checkpoint is given; nothing is downloaded.
-    image_size: input resolution of the ViT towers (position embeddings are sized for it; the reference's HF ViT is
-    built for its checkpoint's resolution the same way); also accepted as a suffix, 'breastclip_vit_1024'.  Beyond
-    256 tokens the attention takes PyTorch's SDPA (K9 covers T <= 256)."""
-    if target_name.startswith("breastclip_vit_") and target_name[len("breastclip_vit_"):].isdigit():
-        image_size = int(target_name[len("breastclip_vit_"):])
-        target_name = "breastclip_vit"
+    image_size: input resolution of the ViT towers, an int (square) or (H, W) (position embeddings are sized for it;
+    the reference's HF ViT is built for its checkpoint's resolution the same way); also accepted as a suffix,
+    'breastclip_vit_1024' or 'breastclip_vit_1520x912' (H x W, Mammo-CLIP's own input).  The attention is HIP at
+    every resolution: K9 up to 256 tokens, K9L beyond (attention_route)."""
+    if target_name.startswith("breastclip_vit_"):
+        hw = _parse_hw(target_name[len("breastclip_vit_"):])
+        if hw is not None:
+            image_size = hw
+            target_name = "breastclip_vit"
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
         if target_name == "breastclip":
@@ -493,14 +535,14 @@ class SyntheticImages(torch.utils.data.Dataset):
     Items follow the reference datasets: ((image, label)) tuples (reference data_utils.py:102-311)."""
 
     def __init__(self, n, size=224, seed=1234):
-        self.n, self.size, self.seed = n, size, seed
+        self.n, self.size, self.seed = n, size, seed   # size: an int (square) or (H, W)
 
     def __len__(self):
         return self.n
 
     def __getitem__(self, i):
         g = torch.Generator().manual_seed(self.seed * 1000003 + i)
-        return torch.randn(3, self.size, self.size, generator=g), 0
+        return torch.randn(3, *image_hw(self.size), generator=g), 0
 
     def on_device(self, device, lo=0, hi=None):
         """The same kind of probe set generated ON the device and kept resident in HBM (images lo..hi-1)."""
@@ -515,7 +557,8 @@ class DeviceSyntheticImages(torch.utils.data.Dataset):
     the 288 GB of an MI355X.  Holds images lo..hi-1 of the n (this rank's shard)."""
 
     def __init__(self, n, size, seed, device, lo=0, hi=None):
-        self.n_total, self.size, self.seed = int(n), int(size), int(seed)
+        self.n_total, self.seed = int(n), int(seed)
+        self.size = image_hw(size) if isinstance(size, (tuple, list)) else int(size)   # an int (square) or (H, W)
         self.lo, self.hi = int(lo), int(self.n_total if hi is None else hi)
         self.device = torch.device(device)
         self._images = None
@@ -526,7 +569,7 @@ class DeviceSyntheticImages(torch.utils.data.Dataset):
     def images(self):
         if self._images is None:
             g = torch.Generator(device=self.device)
-            x = torch.empty((len(self), 3, self.size, self.size), dtype=torch.float32, device=self.device)
+            x = torch.empty((len(self), 3) + image_hw(self.size), dtype=torch.float32, device=self.device)
             for j in range(len(self)):
                 g.manual_seed(self.seed * 1000003 + self.lo + j)
                 x[j].normal_(generator=g)
@@ -543,18 +586,21 @@ class DeviceSyntheticImages(torch.utils.data.Dataset):
 
 
 def get_data(dataset_name, preprocess=None, device=None, lo=0, hi=None):
-    """'synthetic_<N>' or 'synthetic_<N>_<size>' (e.g. synthetic_10000_224).  Real datasets are not in the
+    """'synthetic_<N>', 'synthetic_<N>_<size>' (e.g. synthetic_10000_224) or 'synthetic_<N>_<H>x<W>' (H rows, W columns,
+    e.g. synthetic_64_1520x912).  Real datasets are not in the
     container (reference data_utils.py:102-311 reads VinDr/CSAW/EMBED/ImageNet paths).  With a CUDA `device` the
     probe set is generated on the device and stays resident there (DeviceSyntheticImages); lo/hi select a rank's
     shard of it."""
     if dataset_name.startswith("synthetic"):
         parts = dataset_name.split("_")
         n = int(parts[1]) if len(parts) > 1 else 256
-        size = int(parts[2]) if len(parts) > 2 else 224
+        size = _parse_hw(parts[2]) if len(parts) > 2 else 224
+        if size is None:
+            raise ValueError("dataset %r: the size is <S> or <H>x<W>" % (dataset_name,))
         ds = SyntheticImages(n, size)
         if device is not None and torch.device(device).type == "cuda":
             return ds.on_device(device, lo, hi)
         if lo != 0 or (hi is not None and hi != n):
             return torch.utils.data.Subset(ds, range(lo, n if hi is None else hi))
         return ds
-    raise ValueError("dataset %r is not available offline; use synthetic_<N>[_<size>]" % (dataset_name,))
+    raise ValueError("dataset %r is not available offline; use synthetic_<N>[_<size> | _<H>x<W>]" % (dataset_name,))

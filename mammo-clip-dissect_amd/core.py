@@ -408,6 +408,29 @@ def vit_attention(qkv, heads, out=None):
     return out
 
 
+VIT_ATTENTION_LONG_MAX_T = 32768
+
+
+@_on_device
+def vit_attention_long(qkv, heads, out=None):
+    """vit_attention for any T from 1 to VIT_ATTENTION_LONG_MAX_T (K9L): the same layout and arithmetic, one workgroup
+    per 256 queries of a head; for T <= 256 the same bits as vit_attention.  Allocates only the [B, T, heads*64] output
+    (no T x T scores)."""
+    _need_gpu(qkv)
+    if qkv.dtype != torch.float32 or qkv.dim() != 3 or not qkv.is_contiguous():
+        raise TypeError("qkv must be a contiguous float32 [B, T, 3*heads*64] tensor")
+    B, T, W = qkv.shape
+    if W != 3 * heads * 64:
+        raise ValueError("qkv last dimension %d is not 3 * %d heads * 64" % (W, heads))
+    if out is None:
+        out = torch.empty((B, T, heads * 64), dtype=torch.float32, device=qkv.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, T, heads * 64) or not out.is_contiguous():
+        raise TypeError("out must be a contiguous float32 [B, T, heads*64] tensor")
+    L = _lib.load()
+    check(L.mcd_vit_attention_long(qkv.data_ptr(), B, T, heads, out.data_ptr(), _stream()))
+    return out
+
+
 # ---- K10 -----------------------------------------------------------------------------------------
 @_on_device
 def layer_norm(x, weight, bias, eps):

@@ -28,6 +28,11 @@
 // addresses) against 4096 MFMA cycles.
 // qkv is the [B, T, 3, H, 64] output of the fused qkv projection, out is [B, T, H*64] (what the output projection
 // reads): no permute / contiguous copies around the call.
+//
+// K9L (mcd_vit_attention_long): the same workgroup body (attn_block) for the high-resolution towers, T up to 32 768
+// (1024 x 1024 at patch 16 is 4 097 tokens, Mammo-CLIP's 1520 x 912 is 5 416): one workgroup per block of 256 queries
+// of a head, each streaming all of the head's key tiles.  At T = 4 097 attention is half of the tower's flops; PyTorch's
+// fp32 SDPA (its memory-efficient kernel) ran the same shapes at 0.56-0.60 of the fp32 MFMA peak, K9L at 0.68-0.71.
 #include "mcd_common.h"
 
 namespace {
@@ -36,28 +41,31 @@ using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int AT_D = 64;           // head dimension
 constexpr int AT_MAX_T = 256;      // 8 compute waves + the loader
+constexpr int AT_LONG_MAX_T = 32768;   // the long form (2048 x 2048 at patch 16 is 16 385 tokens)
 constexpr int AT_HALF = 32 * 256;  // bytes of a K (or V) tile
 constexpr int AT_STAGE = 2 * AT_HALF;
 constexpr int AT_NSTAGE = 4;       // ring of tiles: two pairs
 
-__global__ __launch_bounds__(576, 4) void vit_attention_kernel(const float* __restrict__ qkv, int T, int H,
-                                                                float* __restrict__ out) {
+// The workgroup body of both forms: queries q0 .. q0 + 32 * ncw - 1 of head h of image b, one compute wave per 32 of
+// them (waves 0 .. ncw-1), wave ncw the loader; all ntile key tiles of (b, h) go through the LDS ring.  Which block a
+// query sits in does not enter its arithmetic: the long form gives K9's bits wherever both run.
+__device__ __forceinline__ void attn_block(const float* __restrict__ qkv, int T, int H, int64_t b, int h, int q0, int ncw,
+                                           float* __restrict__ out) {
     __shared__ __attribute__((aligned(1024))) char at_lds[AT_NSTAGE * AT_STAGE];   // [stage][K | V][32 rows x 256 B]
     const int ntile = (T + 31) >> 5;
-    const int h = blockIdx.x;
-    const int64_t b = blockIdx.y;
     const int64_t row_stride = (int64_t)3 * H * AT_D;                 // floats between two tokens of qkv
     const float* base = qkv + b * T * row_stride + (int64_t)h * AT_D;  // q of token 0; k at +H*64, v at +2*H*64
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int ql = lane & 31, half = lane >> 5;
-    const int q = wave * 32 + ql;
+    const int q = q0 + wave * 32 + ql;
 
-    if (wave == ntile) {
+    if (wave == ncw) {
         // ---- loader wave: DMA of tile kt into its ring slot; piece p (0..7) = tile rows 4p..4p+3 of K and of V ----
         // BUFFER-load DMA (SGPR descriptor of this image's qkv block + one 32-bit VGPR offset per lane): beside waves that
         // keep the matrix pipe busy, global_load_lds with a 64-bit address pair per lane issues 3-4x slower
-        // (scripts/micro/ldsdma_rate.hip).  One image's block is T * 3 * H * 64 floats (1.8 MB at ViT-B/16): 32-bit offsets.
+        // (scripts/micro/ldsdma_rate.hip).  One image's block is T * 3 * H * 64 floats (1.8 MB at ViT-B/16, 151 MB at
+        // T = 16 385): 32-bit offsets; the image's base address is formed in 64 bits.
         auto stage = [&](int kt) {
             __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(qkv + b * T * row_stride), 0,
                                                                             (int)(T * row_stride * 4), 0x00020000);
@@ -201,6 +209,33 @@ __global__ __launch_bounds__(576, 4) void vit_attention_kernel(const float* __re
     }
 }
 
+// K9: one workgroup per (image, head), one compute wave per 32 queries (T <= 256) + the loader.
+__global__ __launch_bounds__(576, 4) void vit_attention_kernel(const float* __restrict__ qkv, int T, int H,
+                                                                float* __restrict__ out) {
+    const int ntile = (T + 31) >> 5;
+    const int h = blockIdx.x;
+    const int64_t b = blockIdx.y;
+    attn_block(qkv, T, H, b, h, 0, ntile, out);
+}
+
+// K9L, the long form: one workgroup per (image, head, block of 32 * ncw queries), ncw = min(8, ceil(T / 32)).  Every
+// workgroup streams all of its (image, head)'s key tiles, so the nqb query blocks of one (image, head) read the same
+// K / V (2.1 MB at T = 4 097).  Placement, for speed only: workgroups are dealt round-robin over the 8 XCDs, so
+// workgroup w runs on XCD slot w % 8.  The npairs = B * H * nqb (group, query block) pairs, group-major, are cut into
+// 8 runs of per_xcd consecutive pairs, and slot x takes run x in order: the blocks of a group share one XCD's L2 (a
+// group at a run's edge spans two), the load is even to one block, and at any moment each XCD works on one or two
+// groups.  The <= 7 workgroups past npairs return at once, before any barrier.  A last block that reaches past T
+// computes its surplus waves on clamped query rows (as K9's last wave does) and stores nothing for them: every wave
+// meets the loader at every barrier.
+__global__ __launch_bounds__(576, 4) void vit_attention_long_kernel(const float* __restrict__ qkv, int T, int H, int nqb,
+                                                                     int npairs, int per_xcd, float* __restrict__ out) {
+    const int pair = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
+    if (pair >= npairs) return;
+    const int grp = pair / nqb;                    // b * H + h
+    const int ncw = min(8, (T + 31) >> 5);
+    attn_block(qkv, T, H, grp / H, grp % H, (pair - grp * nqb) * 32 * ncw, ncw, out);
+}
+
 }  // namespace
 
 extern "C" int mcd_vit_attention(const float* qkv, int64_t B, int64_t T, int64_t H, float* out, mcd_stream_t stream) {
@@ -217,5 +252,31 @@ extern "C" int mcd_vit_attention(const float* qkv, int64_t B, int64_t T, int64_t
     hipLaunchKernelGGL(vit_attention_kernel, dim3((unsigned)H, (unsigned)B), dim3(64 * nwaves), 0, (hipStream_t)stream, qkv,
                        (int)T, (int)H, out);
     MCD_LAUNCH_CHECK("vit_attention_kernel");
+    return MCD_OK;
+}
+
+extern "C" int mcd_vit_attention_long(const float* qkv, int64_t B, int64_t T, int64_t H, float* out, mcd_stream_t stream) {
+    MCD_REQUIRE(qkv && out, MCD_E_ARG, "mcd_vit_attention_long: NULL pointer");
+    MCD_REQUIRE(B >= 0 && T >= 1 && H >= 1, MCD_E_ARG, "mcd_vit_attention_long: bad shape B=%lld T=%lld H=%lld",
+                (long long)B, (long long)T, (long long)H);
+    MCD_REQUIRE(T <= AT_LONG_MAX_T, MCD_E_UNSUPPORTED, "mcd_vit_attention_long: T=%lld tokens, at most %d", (long long)T,
+                AT_LONG_MAX_T);
+    MCD_REQUIRE(B <= INT32_MAX && H <= 65535, MCD_E_UNSUPPORTED, "mcd_vit_attention_long: B must be < 2^31, H <= 65535");
+    MCD_REQUIRE(T * 3 * H * AT_D * 4 <= INT32_MAX, MCD_E_UNSUPPORTED,
+                "mcd_vit_attention_long: one image's qkv block (T=%lld x H=%lld heads) must stay under 2^31 bytes",
+                (long long)T, (long long)H);
+    MCD_REQUIRE(((uintptr_t)qkv) % 16 == 0 && ((uintptr_t)out) % 16 == 0, MCD_E_ARG,
+                "mcd_vit_attention_long: qkv and out must be 16-byte aligned");
+    if (B == 0) return MCD_OK;
+    const int64_t ncw = std::min<int64_t>(8, (T + 31) / 32);   // compute waves per workgroup
+    const int64_t nqb = mcd_cdiv((T + 31) / 32, ncw);            // query blocks per (image, head)
+    const int64_t npairs = B * H * nqb;
+    MCD_REQUIRE(npairs <= INT32_MAX / 576 - 8, MCD_E_UNSUPPORTED,
+                "mcd_vit_attention_long: B=%lld x H=%lld x %lld query blocks is too large a grid", (long long)B,
+                (long long)H, (long long)nqb);
+    const int64_t per_xcd = mcd_cdiv(npairs, 8);
+    hipLaunchKernelGGL(vit_attention_long_kernel, dim3((unsigned)(8 * per_xcd)), dim3(64 * (unsigned)(ncw + 1)), 0,
+                       (hipStream_t)stream, qkv, (int)T, (int)H, (int)nqb, (int)npairs, (int)per_xcd, out);
+    MCD_LAUNCH_CHECK("vit_attention_long_kernel");
     return MCD_OK;
 }
