@@ -52,7 +52,8 @@ enum {
 enum { MCD_WPMI_SOFT = 1, MCD_WPMI_FAST_LOG = 2, MCD_WPMI_S_IS_PROB = 4 };
 
 /* hook pooling modes for mcd_hook_pool */
-enum { MCD_POOL_AVG = 0, MCD_POOL_MAX = 1, MCD_POOL_CLS = 2, MCD_POOL_NONE = 3 };
+enum { MCD_POOL_AVG = 0, MCD_POOL_MAX = 1, MCD_POOL_CLS = 2, MCD_POOL_NONE = 3,
+       MCD_POOL_SILU_AVG = 4 /* mcd_hook_pool_nhwc only: mean over HW of SiLU(x) */ };
 
 const char* mcd_last_error(void);
 int mcd_abi_version(void);
@@ -286,6 +287,66 @@ int mcd_layer_norm(const float* x, int64_t rows, int64_t D, const float* gamma, 
  *           (ViTPatchEmbeddings.projection), conv1                          concept_vit/clip/model.py:206-223
  * ------------------------------------------------------------------------------------------- */
 int mcd_patchify(const float* x, int64_t B, int64_t Cin, int64_t H, int64_t W, int64_t P, float* out, mcd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * EfficientNet-B5 image tower, inference route (K12-K15, K0n): channels-last (NHWC) activations, batch norm (eval,
+ * running statistics) folded into the weights as W' = W * g / sqrt(var + eps) per output channel and
+ * b' = beta - mean * g / sqrt(var + eps); the 1x1 convolutions are GEMMs on libmcd_blaslt.so.  fp32, SiLU and sigmoid
+ * with the accurate exp.  Every kernel addresses one image from a 64-bit base with 32-bit offsets inside it: a tensor
+ * of one image of 2^31 bytes or more, or B > 65535, is MCD_E_UNSUPPORTED (the caller takes the ATen route).  No
+ * atomics: an image's bits do not depend on the batch it is in.  Encoder-side ops, fp32-accurate, no bit-exactness
+ * claim against the reference's backend (K0n excepted: bit-equal to K0, below).  TF-SAME padding throughout: for n
+ * input rows, kernel k and stride s the output has ceil(n/s) rows and the pad max((ceil(n/s)-1)*s + k - n, 0) is split
+ * with its smaller half on top (left).  Float pointers 16-byte aligned.
+ *
+ * K12  stem: x NCHW [B, Cin, H, W] (Cin <= 4) -> y NHWC [B, ceil(H/2), ceil(W/2), Cout] = SiLU(conv3x3/2(x, W') + b'),
+ *      w tap-major [Cin, 3, 3, Cout], Cout % 4 == 0.
+ * replaces  _conv_stem + _bn0 + swish                          model/modules/efficientnet_custom.py:241, :273
+ * ------------------------------------------------------------------------------------------- */
+int mcd_conv_stem_nhwc(const float* x, int64_t B, int64_t Cin, int64_t H, int64_t W, const float* w, const float* bias,
+                       int64_t Cout, float* y, mcd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * K13  depthwise k x k (k in {3, 5}), stride 1 or 2, on NHWC x [B, H, W, C] (C % 4 == 0):
+ *        y[b, oy, ox, c] = SiLU( sum_taps w[dy*k + dx, c] * a(x[b, iy, ix, c]) + bias[c] ),  y [B, ceil(H/s), ceil(W/s), C]
+ *      a = SiLU when silu_in != 0 (x is the raw expand-GEMM output; the zero padding commutes: SiLU(0) = 0), the
+ *      identity otherwise.  w is tap-major [k*k, C].  Also writes the squeeze-excite partial sums
+ *      psum[b, t, c] = sum of y[b, ., ., c] over output tile t, for the T = ceil(Ho/8) * ceil(Wo/8) tiles of 8 x 8
+ *      output pixels (row-major; the tiling depends on (Ho, Wo) only).  One workgroup per (tile, channel slice, image)
+ *      stages the tile's input window in LDS once.
+ * replaces  _depthwise_conv + _bn1 + swish + adaptive_avg_pool2d  model/modules/efficientnet_custom.py:109-115
+ * ------------------------------------------------------------------------------------------- */
+int mcd_dwconv_bn_silu(const float* x, int64_t B, int64_t H, int64_t W, int64_t C, const float* w, const float* bias,
+                       int k, int stride, int silu_in, float* y, float* psum, int64_t T, mcd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * K14  squeeze-excite gate, one workgroup per image:  mean[c] = (sum_t psum[b, t, c], in t order) / HW,
+ *        s[b, c] = sigmoid( b_e[c] + sum_j w_et[j, c] * SiLU( b_r[j] + sum_c' w_r[j, c'] * mean[c'] ) )
+ *      w_r [sq, C] (_se_reduce's weight), w_et [sq, C] (_se_expand's weight TRANSPOSED), any SE width sq >= 1,
+ *      C + sq <= 16384.
+ * replaces  _se_reduce, swish, _se_expand, sigmoid             model/modules/efficientnet_custom.py:116-119
+ * ------------------------------------------------------------------------------------------- */
+int mcd_se_gate(const float* psum, int64_t B, int64_t T, int64_t C, int64_t HW, const float* w_r, const float* b_r,
+                int64_t sq, const float* w_et, const float* b_e, float* s, mcd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * K15  y[b, p, c] *= s[b, c] in place on NHWC y [B, HW, C] (C % 4 == 0), 16-byte accesses: the same bits as
+ *      y * s[:, None, None, :].  (hipBLASLt cannot scale a GEMM's reduction dimension per image: a pass of its own.)
+ * replaces  torch.sigmoid(x_squeezed) * x                      model/modules/efficientnet_custom.py:119
+ * ------------------------------------------------------------------------------------------- */
+int mcd_channel_scale(float* y, int64_t B, int64_t HW, int64_t C, const float* s, mcd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * K0n  K0 for a channels-last [B, C, H, W] (memory [B, HW, C]): mean (MCD_POOL_AVG) or amax (MCD_POOL_MAX) over HW
+ *      into dst exactly as mcd_hook_pool writes it, BIT-IDENTICAL to mcd_hook_pool on the NCHW-contiguous copy (K0's
+ *      per-lane partials -- its float4 grouping when HW % 4 == 0, its scalar walk otherwise -- combined in K0's
+ *      xor-butterfly order; a NaN in a plane makes its max NaN).  MCD_POOL_SILU_AVG: mean over HW of SiLU(x), the
+ *      tower's head (mcd_hook_pool rejects that mode).
+ * replaces  output.mean/amax(dim=[2,3]) of the hook body        concept_vit/utils.py:37-47
+ *           head swish + average pooling                       model/modules/efficientnet_custom.py:257, :301
+ * ------------------------------------------------------------------------------------------- */
+int mcd_hook_pool_nhwc(const float* x, int64_t B, int64_t C, int64_t HW, int mode, float* dst, int64_t row0,
+                       int64_t col0, int64_t stride_n, int64_t stride_u, mcd_stream_t stream);
 
 #ifdef __cplusplus
 }

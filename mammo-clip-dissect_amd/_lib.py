@@ -41,8 +41,14 @@ SIGNATURES = {
     "mcd_vit_attention_long": (_int, [_p, _i64, _i64, _i64, _p, _p]),
     "mcd_layer_norm": (_int, [_p, _i64, _i64, _p, _p, _f, _p, _p]),
     "mcd_patchify": (_int, [_p, _i64, _i64, _i64, _i64, _i64, _p, _p]),
+    "mcd_conv_stem_nhwc": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _i64, _p, _p]),
+    "mcd_dwconv_bn_silu": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _int, _int, _int, _p, _p, _i64, _p]),
+    "mcd_se_gate": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _i64, _p, _p, _p, _p]),
+    "mcd_channel_scale": (_int, [_p, _i64, _i64, _i64, _p, _p]),
+    "mcd_hook_pool_nhwc": (_int, [_p, _i64, _i64, _i64, _int, _p, _i64, _i64, _i64, _i64, _p]),
 }
 
+MCD_E_ARG = -1
 MCD_E_RANGE = -2
 MCD_E_UNSUPPORTED = -5
 

@@ -40,6 +40,11 @@ FUSED_RESIDUAL = os.environ.get("MCD_NO_FUSED_RESIDUAL", "0") != "1"
 
 # nn.LayerNorm of the towers on the HIP kernel K10 (csrc/k_ln.hip); MCD_NO_HIP_LAYER_NORM=1 keeps ATen's.
 HIP_LAYER_NORM = os.environ.get("MCD_NO_HIP_LAYER_NORM", "0") != "1"
+# The EfficientNet-B5 tower's inference route (mbconv_route): channels-last activations, batch norm folded into the
+# weights, every 1x1 convolution one hipBLASLt GEMM (core.linear_residual) and K12-K15 / K0n (csrc/k_mbconv.hip) for the
+# rest.  MCD_NO_HIP_MBCONV=1 (or setting this to False) keeps the ATen route: MIOpen convolutions, ATen batch norm,
+# SiLU, mean, sigmoid-multiply and add -- the tests' reference and the other side of the timing A/B.
+HIP_MBCONV = os.environ.get("MCD_NO_HIP_MBCONV", "0") != "1"
 
 
 class _LayerNorm(nn.LayerNorm):
@@ -242,10 +247,89 @@ class _SameConv(nn.Conv2d):
         return F.conv2d(x, self.weight, self.bias, self.stride, 0, self.dilation, self.groups)
 
 
+def fold_bn(weight, bn):
+    """(W', b'): the eval-mode batch norm `bn` folded into the bias-free convolution weight [Cout, ...] in front of it,
+    W' = W * g / sqrt(var + eps) per output channel, b' = beta - mean * g / sqrt(var + eps).  Computed in float64,
+    returned in the weight's dtype."""
+    scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+    w = weight.detach().double() * scale.view(-1, *([1] * (weight.dim() - 1)))
+    b = bn.bias.detach().double() - bn.running_mean.detach().double() * scale
+    return w.to(weight.dtype), b.to(weight.dtype)
+
+
+def _folded(module, names, build):
+    """build(module) -> dict of folded tensors, computed once and cached in the module's __dict__ (no parameter or buffer
+    is registered: state_dict() and the module tree stay as they are).  The cache is keyed on the version counter and the
+    storage of every tensor of the named submodules, and on the device, like ViTTower._embed_residual's."""
+    srcs = [t for n in names for m in (getattr(module, n, None),) if m is not None
+            for t in list(m.parameters(recurse=False)) + list(m.buffers(recurse=False))]
+    key = tuple((t._version, t.data_ptr()) for t in srcs) + (srcs[0].device, srcs[0].dtype)
+    cache = module.__dict__.setdefault("_mbconv_fold", {})
+    if cache.get("key") != key:
+        with torch.no_grad():
+            cache["val"] = build(module)
+        cache["key"] = key
+    return cache["val"]
+
+
+_MBCONV_SKIPPED = ("_expand_conv", "_bn0", "_depthwise_conv", "_bn1", "_se_reduce", "_se_expand", "_project_conv", "_bn2")
+_TOWER_SKIPPED = ("_conv_stem", "_bn0", "_conv_head", "_bn1")
+
+
+def _hooks_on(module, names):
+    """A global module hook, or a forward (pre-)hook on one of the named submodules (which the HIP route does not call)."""
+    from torch.nn.modules import module as M
+    if M._global_forward_hooks or M._global_forward_pre_hooks:
+        return True
+    return any(m is not None and (m._forward_hooks or m._forward_pre_hooks)
+               for m in (getattr(module, n, None) for n in names))
+
+
+def _same_out(n, s):
+    return -(-n // s)
+
+
+def mbconv_route(module, x):
+    """'hip' when the B5 tower (an EfficientNetB5Tower with its NCHW-contiguous input image) or one of its blocks (an
+    _MBConv with a channels_last-contiguous input) can take the HIP route: HIP_MBCONV on, a CUDA fp32 tensor, inference
+    (no autograd, eval mode), libmcd_blaslt.so loaded, channel counts that are multiples of 4 (the SE width may be
+    anything), one image's tensors under 2^31 bytes, and no hook on a submodule the route does not call (--target_layers
+    may name any module path: a hook on _blocks[5]._depthwise_conv must fire, so that block takes ATen).  'aten'
+    otherwise."""
+    if not (HIP_MBCONV and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and not torch.is_grad_enabled() and not module.training and x.shape[0] <= 65535):
+        return "aten"
+    from .. import core
+    if not core.linear_residual_available():
+        return "aten"
+    B, C, H, W = x.shape
+    if isinstance(module, _MBConv):
+        if (C != module.cin or module.cin % 4 or module.mid % 4 or module.cout % 4 or module.k not in (3, 5)
+                or module.s not in (1, 2) or not x.is_contiguous(memory_format=torch.channels_last)
+                or x.data_ptr() % 16 or module.mid * H * W * 4 >= 2 ** 31 or module.cin * H * W * 4 >= 2 ** 31):
+            return "aten"
+        names = _MBCONV_SKIPPED
+    elif isinstance(module, EfficientNetB5Tower):
+        stem, head = module._conv_stem, module._conv_head
+        h, w = H, W
+        for _ in range(5):                           # the five stride-2 stages: the head's input size
+            h, w = _same_out(h, 2), _same_out(w, 2)
+        if (C != stem.in_channels or C > 4 or stem.out_channels % 4 or stem.kernel_size != (3, 3)
+                or stem.stride != (2, 2) or head.in_channels % 4 or head.out_channels % 4 or not x.is_contiguous()
+                or stem.out_channels * _same_out(H, 2) * _same_out(W, 2) * 4 >= 2 ** 31
+                or head.out_channels * h * w * 4 >= 2 ** 31):
+            return "aten"
+        names = _TOWER_SKIPPED
+    else:
+        return "aten"
+    return "aten" if _hooks_on(module, names) else "hip"
+
+
 class _MBConv(nn.Module):
     def __init__(self, cin, cout, k, s, expand, se_ratio=0.25):
         super().__init__()
         mid = cin * expand
+        self.cin, self.mid, self.cout, self.k, self.s = cin, mid, cout, k, s
         self.expand = expand != 1
         if self.expand:
             self._expand_conv = _SameConv(cin, mid, 1, bias=False)
@@ -260,6 +344,8 @@ class _MBConv(nn.Module):
         self.skip = s == 1 and cin == cout
 
     def forward(self, x):
+        if mbconv_route(self, x) == "hip":
+            return self._forward_hip(x)
         y = x
         if self.expand:
             y = F.silu(self._bn0(self._expand_conv(y)))
@@ -267,6 +353,37 @@ class _MBConv(nn.Module):
         se = self._se_expand(F.silu(self._se_reduce(y.mean(dim=[2, 3], keepdim=True))))
         y = self._bn2(self._project_conv(torch.sigmoid(se) * y))
         return x + y if self.skip else y
+
+    def _forward_hip(self, x):
+        """The block on channels-last activations: expand GEMM (raw, folded BN0 as its bias), K13 (SiLU of the expand
+        output on the way in, depthwise + folded BN1 + SiLU, SE partial sums), K14 (SE gate), K15 (scale, in place),
+        project GEMM (folded BN2 as its bias, the skip as its residual operand: a new tensor, x is left alone).
+        Returns [B, C, H, W] in channels_last memory, the reference's logical shape."""
+        from .. import core
+        f = _folded(self, _MBCONV_SKIPPED, _MBConv._fold)
+        xn = x.permute(0, 2, 3, 1)                                   # [B, H, W, cin], contiguous
+        h = core.linear_residual(None, xn, f["w0"], f["b0"]) if self.expand else xn
+        d, psum = core.dwconv_bn_silu(h, f["wd"], f["bd"], self.k, self.s, self.expand)
+        gate = core.se_gate(psum, d.shape[1] * d.shape[2], f["wr"], f["br"], f["we"], f["be"])
+        core.channel_scale_(d, gate)
+        y = core.linear_residual(xn if self.skip else None, d, f["wp"], f["bp"])
+        return y.permute(0, 3, 1, 2)
+
+    def _fold(self):
+        f = {}
+        if self.expand:
+            w0, f["b0"] = fold_bn(self._expand_conv.weight, self._bn0)
+            f["w0"] = w0.view(self.mid, self.cin).contiguous()
+        wd, f["bd"] = fold_bn(self._depthwise_conv.weight, self._bn1)
+        f["wd"] = wd.view(self.mid, self.k * self.k).t().contiguous()          # tap-major [k*k, mid]
+        sq = self._se_reduce.out_channels
+        f["wr"] = self._se_reduce.weight.detach().reshape(sq, self.mid).contiguous()
+        f["br"] = self._se_reduce.bias.detach().contiguous()
+        f["we"] = self._se_expand.weight.detach().reshape(self.mid, sq).t().contiguous()       # transposed: [sq, mid]
+        f["be"] = self._se_expand.bias.detach().contiguous()
+        wp, f["bp"] = fold_bn(self._project_conv.weight, self._bn2)
+        f["wp"] = wp.view(self.cout, self.mid).contiguous()
+        return f
 
 
 def _round_filters(f, width, divisor=8):
@@ -301,11 +418,31 @@ class EfficientNetB5Tower(nn.Module):
         self._fc = nn.Linear(self.out_dim, num_classes)
 
     def forward(self, x):
+        if mbconv_route(self, x) == "hip":
+            return self._forward_hip(x)
         x = F.silu(self._bn0(self._conv_stem(x)))
         for b in self._blocks:
             x = b(x)
         x = F.silu(self._bn1(self._conv_head(x)))
         return x.mean(dim=[2, 3])
+
+    def _forward_hip(self, x):
+        """Stem by K12 (NCHW image -> channels-last), the blocks called as modules (hooks on _blocks[i] fire; each block
+        picks its own route), the head as one GEMM (folded BN1 as its bias) and K0n's mean of SiLU."""
+        from .. import core
+        f = _folded(self, _TOWER_SKIPPED, EfficientNetB5Tower._fold)
+        x = core.conv_stem_nhwc(x, f["ws"], f["bs"]).permute(0, 3, 1, 2)
+        for b in self._blocks:
+            # a block that took ATen (a hook inside it, say) may hand on NCHW memory: back to channels-last for the next
+            x = b(x).contiguous(memory_format=torch.channels_last)
+        xn = x.permute(0, 2, 3, 1)
+        return core.silu_avg_pool_nhwc(core.linear_residual(None, xn, f["wh"], f["bh"]))
+
+    def _fold(self):
+        ws, bs = fold_bn(self._conv_stem.weight, self._bn0)
+        wh, bh = fold_bn(self._conv_head.weight, self._bn1)
+        return {"ws": ws.permute(1, 2, 3, 0).contiguous(), "bs": bs.contiguous(),      # tap-major [Cin, 3, 3, Cout]
+                "wh": wh.view(self.out_dim, -1).contiguous(), "bh": bh.contiguous()}
 
 
 # ------------------------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@ from . import _lib
 from ._lib import McdError, check  # noqa: F401
 
 POOL_MODES = {"avg": 0, "max": 1, "cls": 2, "none": 3}
+POOL_SILU_AVG = 4      # mcd_hook_pool_nhwc only
 GEMM_MODES = {"f32": 0, "bf16x3": 1, "bf16": 2}
 
 
@@ -463,6 +464,116 @@ def patchify(x, patch):
     return out
 
 
+# ---- K12 - K15: the EfficientNet-B5 tower on channels-last activations (csrc/k_mbconv.hip) ----------------------
+DWCONV_TILE = 8      # K13's SE partial sums: one per 8 x 8 tile of output pixels
+
+
+def _nhwc(t, name):
+    _need_gpu(t)
+    if t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous():
+        raise TypeError("%s must be a contiguous float32 [B, H, W, C] tensor" % name)
+    return t
+
+
+def _vec(t, n, name):
+    _need_gpu(t)
+    if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
+        raise TypeError("%s must be %d contiguous float32 values" % (name, n))
+    return t
+
+
+def same_pad(n, k, s):
+    """TF-SAME padding of one axis (data_utils._SameConv): (output size, pad in front, pad behind)."""
+    o = -(-n // s)
+    p = max((o - 1) * s + k - n, 0)
+    return o, p // 2, p - p // 2
+
+
+def dwconv_tiles(Ho, Wo):
+    """T, the number of K13's SE partial-sum tiles of an Ho x Wo output."""
+    return -(-Ho // DWCONV_TILE) * -(-Wo // DWCONV_TILE)
+
+
+@_on_device
+def conv_stem_nhwc(x, w_tap, bias):
+    """K12: SiLU(conv3x3/2(x) + bias) with TF-SAME padding: x NCHW [B, Cin, H, W] (Cin <= 4), w_tap [Cin, 3, 3, Cout]
+    (the folded weight, tap-major) -> NHWC [B, ceil(H/2), ceil(W/2), Cout]."""
+    _need_gpu(x)
+    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
+        raise TypeError("conv_stem_nhwc: x must be a contiguous float32 [B, Cin, H, W] tensor")
+    B, Cin, H, W = x.shape
+    Cout = w_tap.shape[-1]
+    _vec(w_tap, Cin * 9 * Cout, "w_tap")
+    _vec(bias, Cout, "bias")
+    y = torch.empty((B, -(-H // 2), -(-W // 2), Cout), dtype=torch.float32, device=x.device)
+    L = _lib.load()
+    check(L.mcd_conv_stem_nhwc(x.data_ptr(), B, Cin, H, W, w_tap.data_ptr(), bias.data_ptr(), Cout, y.data_ptr(), _stream()))
+    return y
+
+
+@_on_device
+def dwconv_bn_silu(x, w_tap, bias, k, stride, silu_in):
+    """K13: depthwise k x k / stride on NHWC x [B, H, W, C] with the folded weight w_tap [k*k, C] and bias [C]:
+    y = SiLU(conv(a(x)) + bias), a = SiLU if silu_in else the identity.  Returns (y [B, Ho, Wo, C], psum [B, T, C]) with
+    psum the per-tile sums of y (dwconv_tiles(Ho, Wo) tiles)."""
+    x = _nhwc(x, "x")
+    B, H, W, C = x.shape
+    _vec(w_tap, k * k * C, "w_tap")
+    _vec(bias, C, "bias")
+    Ho, Wo = -(-H // stride), -(-W // stride)
+    T = dwconv_tiles(Ho, Wo)
+    y = torch.empty((B, Ho, Wo, C), dtype=torch.float32, device=x.device)
+    psum = torch.empty((B, T, C), dtype=torch.float32, device=x.device)
+    L = _lib.load()
+    check(L.mcd_dwconv_bn_silu(x.data_ptr(), B, H, W, C, w_tap.data_ptr(), bias.data_ptr(), int(k), int(stride),
+                               1 if silu_in else 0, y.data_ptr(), psum.data_ptr(), T, _stream()))
+    return y, psum
+
+
+@_on_device
+def se_gate(psum, hw, w_r, b_r, w_et, b_e):
+    """K14: s [B, C] = sigmoid(b_e + w_et^T . SiLU(b_r + w_r . mean)), mean = psum summed over its tiles / hw;
+    w_r [sq, C] (the reduce convolution's weight), w_et [sq, C] (the expand convolution's weight, transposed)."""
+    _need_gpu(psum)
+    if psum.dtype != torch.float32 or psum.dim() != 3 or not psum.is_contiguous():
+        raise TypeError("psum must be a contiguous float32 [B, T, C] tensor")
+    B, T, C = psum.shape
+    sq = b_r.numel()
+    _vec(w_r, sq * C, "w_r")
+    _vec(b_r, sq, "b_r")
+    _vec(w_et, C * sq, "w_et")
+    _vec(b_e, C, "b_e")
+    s = torch.empty((B, C), dtype=torch.float32, device=psum.device)
+    L = _lib.load()
+    check(L.mcd_se_gate(psum.data_ptr(), B, T, C, int(hw), w_r.data_ptr(), b_r.data_ptr(), sq, w_et.data_ptr(),
+                        b_e.data_ptr(), s.data_ptr(), _stream()))
+    return s
+
+
+@_on_device
+def channel_scale_(y, s):
+    """K15: y [B, H, W, C] *= s[:, None, None, :] in place; returns y."""
+    y = _nhwc(y, "y")
+    B, H, W, C = y.shape
+    _need_gpu(s)
+    if s.dtype != torch.float32 or tuple(s.shape) != (B, C) or not s.is_contiguous():
+        raise TypeError("s must be a contiguous float32 [B, C] tensor")
+    L = _lib.load()
+    check(L.mcd_channel_scale(y.data_ptr(), B, H * W, C, s.data_ptr(), _stream()))
+    return y
+
+
+@_on_device
+def silu_avg_pool_nhwc(x):
+    """K0n's MCD_POOL_SILU_AVG: x NHWC [B, H, W, C] -> [B, C] = mean over H, W of SiLU(x) (the tower's head)."""
+    x = _nhwc(x, "x")
+    B, H, W, C = x.shape
+    out = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    L = _lib.load()
+    check(L.mcd_hook_pool_nhwc(x.data_ptr(), B, C, H * W, POOL_SILU_AVG, out.data_ptr(), 0, 0, C, 1, _stream()))
+    return out
+
+
 # ---- encoder-side linear + bias + residual on hipBLASLt (libmcd_blaslt.so) ------------------------
 _blaslt_ws = {}
 # bench.py sets this to a list to time the library GEMMs inside the forwards: every call then appends
@@ -548,7 +659,12 @@ def hook_pool(x, mode, dst, row0, col0, neuron_major):
     _need_gpu(x, dst)
     if x.dtype != torch.float32:
         x = x.float()
-    x = x.contiguous()
+    # a channels-last 4-D output (the B5 tower's HIP route) is pooled where it lies by K0n: the same bits as K0 on the
+    # NCHW-contiguous copy, without the copy
+    nhwc = x.dim() == 4 and mode in ("avg", "max") and not x.is_contiguous() \
+        and x.is_contiguous(memory_format=torch.channels_last)
+    if not nhwc:
+        x = x.contiguous()
     if x.dim() == 4:
         B, Cout, HW = x.shape[0], x.shape[1], x.shape[2] * x.shape[3]
         m = POOL_MODES[mode]
@@ -572,5 +688,8 @@ def hook_pool(x, mode, dst, row0, col0, neuron_major):
     else:
         sn, su = dst.stride(0), 1
     L = _lib.load()
+    if nhwc:
+        check(L.mcd_hook_pool_nhwc(x.data_ptr(), B, Cout, HW, m, dst.data_ptr(), int(row0), int(col0), sn, su, _stream()))
+        return Cout
     check(L.mcd_hook_pool(x.data_ptr(), B, Cout, HW, m, dst.data_ptr(), int(row0), int(col0), sn, su, _stream()))
     return Cout
