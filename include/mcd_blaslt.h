@@ -33,13 +33,22 @@ int mcd_linear_residual(const float* h, int64_t ldh, const float* W, int64_t ldw
                         int64_t ldr, float* out, int64_t ldo, int64_t M, int64_t N, int64_t K, void* ws, size_t ws_bytes,
                         mcd_blaslt_stream_t stream);
 
+/* out[M,N] = relu(res[M,N] + h[M,K] . W[N,K]^T + bias[N]): mcd_linear_residual with hipBLASLt's ReLU epilogue
+ * (HIPBLASLT_EPILOGUE_RELU_BIAS, or ..._RELU without a bias), applied to the whole sum, residual included.  Same
+ * arguments and rules.  Plans and picks are kept apart from mcd_linear_residual's: in the records of get_picks / set_pick
+ * bit 1 of has_res marks this entry (has_res = 2 without a residual, 3 with one).
+ * replaces  conv3 + bn3 (folded) + the skip add + relu of a torchvision Bottleneck on channels-last rows. */
+int mcd_linear_residual_relu(const float* h, int64_t ldh, const float* W, int64_t ldw, const float* bias, const float* res,
+                             int64_t ldr, float* out, int64_t ldo, int64_t M, int64_t N, int64_t K, void* ws,
+                             size_t ws_bytes, mcd_blaslt_stream_t stream);
+
 /* average time (ms) of the algorithm kept for shape (M, N, K) and the number of candidates that were timed */
 int mcd_linear_residual_plan_info(int64_t M, int64_t N, int64_t K, float* ms, int* tried);
 
 /* Reproducible algorithm choice.  A timed pick may differ between processes (and different algorithms sum in different
  * orders); the env MCD_BLASLT_PICK=heuristic takes the first usable heuristic candidate instead, and these two calls let
  * one process's picks be forced in another (the multi-rank host code broadcasts rank 0's):
- *   get_picks: up to `cap` records of 5 int64 {M, N, K, has_res, pick} into `out` (host memory); returns the number held.
+ *   get_picks: up to `cap` records of 5 int64 {M, N, K, has_res (bit 0 residual, bit 1 ReLU), pick} into `out` (host memory); returns the number held.
  *   set_pick:  force `pick` (index into the heuristic's candidate list; < 0 un-forces) for a shape; an existing plan for
  *              it is rebuilt on the next call. */
 int mcd_linear_residual_get_picks(int64_t* out, int cap);

@@ -348,6 +348,47 @@ int mcd_channel_scale(float* y, int64_t B, int64_t HW, int64_t C, const float* s
 int mcd_hook_pool_nhwc(const float* x, int64_t B, int64_t C, int64_t HW, int mode, float* dst, int64_t row0,
                        int64_t col0, int64_t stride_n, int64_t stride_u, mcd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ResNet-50 target, inference route (K16-K18): channels-last (NHWC) activations, batch norm (eval, running statistics)
+ * folded as for the B5 tower; the stride-1 1x1 convolutions are GEMMs on libmcd_blaslt.so.  fp32.  ResNet's symmetric
+ * padding: for n input rows, kernel k, stride s and pad p the output has (n + 2p - k) / s + 1 rows (floor).  One image's
+ * tensor of 2^31 bytes or more, B > 65535 or a width a kernel does not take is MCD_E_UNSUPPORTED (the caller takes the
+ * ATen route).  No atomics and no split reduction: every output element is one fmaf chain in a fixed order, so an
+ * image's bits depend neither on the batch it is in nor on its place in it.  Float pointers 16-byte aligned.
+ *
+ * K16  stem, raw: x NCHW [B, Cin, H, W] (Cin <= 4) -> y NHWC [B, Ho, Wo, Cout] = conv7x7/2, pad 3 (x, w); no bias, no
+ *      batch norm, no ReLU (conv1 is a hook point: the hook sees the convolution's own output).  w tap-major
+ *      [Cin, 7, 7, Cout], Cout % 4 == 0.
+ * replaces  conv1 of the torchvision ResNet-50                    concept_vit/data_utils.py:85-93
+ * ------------------------------------------------------------------------------------------- */
+int mcd_conv7x7s2_nhwc(const float* x, int64_t B, int64_t Cin, int64_t H, int64_t W, const float* w, int64_t Cout,
+                       float* y, mcd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * K17  NHWC x [B, H, W, C] (C % 4 == 0) -> y [B, Ho, Wo, C]: max over the 3x3 / stride 2 / pad 1 window of
+ *      relu(fma(x, scale[c], shift[c])); the padding never wins (the window always holds a real pixel).  With
+ *      scale = 1, shift = 0 bit-equal to max_pool2d(relu(x), 3, 2, 1).
+ * replaces  bn1 + relu + maxpool of the torchvision ResNet-50     concept_vit/data_utils.py:85-93
+ * ------------------------------------------------------------------------------------------- */
+int mcd_bn_relu_maxpool_nhwc(const float* x, int64_t B, int64_t H, int64_t W, int64_t C, const float* scale,
+                             const float* shift, float* y, mcd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * K18  implicit-GEMM convolution on v_mfma_f32_32x32x2_f32 (exact fp32), no im2col buffer: x NHWC [B, H, W, Cin],
+ *      w [Cout, k*k*Cin] tap-major then channel, bias [Cout], y NHWC [B, Ho, Wo, Cout]:
+ *        y = act_out( bias + sum over (tap, cin) of w * act_in(x) ),  act_in / act_out = ReLU when relu_in / relu_out
+ *      (relu(0) = 0: the zero padding commutes with relu_in).  k = 3 with stride 1 or 2 (pad 1), k = 1 with stride 2
+ *      (pad 0); Cin % 32 == 0 and Cout % 32 == 0; anything else is MCD_E_UNSUPPORTED.  GEMM rows are the flattened
+ *      output pixels B*Ho*Wo (a tile may span images).  The reduction of every output element runs tap-major, then
+ *      channel, in ascending order: chunks of 256 consecutive k, each a k-ordered fmaf chain from 0 (the MFMA's
+ *      arithmetic), the chunks' partial sums added in ascending order, the bias last -- the same order for every
+ *      element whatever its tile, image or batch (a single chain over k = 4 608 is 8 x less accurate than ATen).
+ * replaces  Bottleneck.conv2 + bn2 + relu (and the relu after bn1 on the way in), downsample[0] + downsample[1] of a
+ *           stride-2 block                                        concept_vit/data_utils.py:85-93
+ * ------------------------------------------------------------------------------------------- */
+int mcd_conv_igemm_nhwc(const float* x, int64_t B, int64_t H, int64_t W, int64_t Cin, const float* w, const float* bias,
+                        int64_t Cout, int k, int stride, int relu_in, int relu_out, float* y, mcd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

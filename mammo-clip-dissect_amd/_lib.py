@@ -46,6 +46,9 @@ SIGNATURES = {
     "mcd_se_gate": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _i64, _p, _p, _p, _p]),
     "mcd_channel_scale": (_int, [_p, _i64, _i64, _i64, _p, _p]),
     "mcd_hook_pool_nhwc": (_int, [_p, _i64, _i64, _i64, _int, _p, _i64, _i64, _i64, _i64, _p]),
+    "mcd_conv7x7s2_nhwc": (_int, [_p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p]),
+    "mcd_bn_relu_maxpool_nhwc": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
+    "mcd_conv_igemm_nhwc": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _i64, _int, _int, _int, _int, _p, _p]),
 }
 
 MCD_E_ARG = -1
@@ -92,6 +95,7 @@ BLASLT_SIGNATURES = {
     "mcd_blaslt_last_error": (ctypes.c_char_p, []),
     "mcd_linear_residual_workspace": (_sz, []),
     "mcd_linear_residual": (_int, [_p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _sz, _p]),
+    "mcd_linear_residual_relu": (_int, [_p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _sz, _p]),
     "mcd_linear_residual_plan_info": (_int, [_i64, _i64, _i64, ctypes.POINTER(_f), ctypes.POINTER(_int)]),
     "mcd_linear_residual_get_picks": (_int, [ctypes.POINTER(_i64), _int]),
     "mcd_linear_residual_set_pick": (_int, [_i64, _i64, _i64, _int, _int]),

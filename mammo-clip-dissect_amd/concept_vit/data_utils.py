@@ -45,6 +45,10 @@ HIP_LAYER_NORM = os.environ.get("MCD_NO_HIP_LAYER_NORM", "0") != "1"
 # rest.  MCD_NO_HIP_MBCONV=1 (or setting this to False) keeps the ATen route: MIOpen convolutions, ATen batch norm,
 # SiLU, mean, sigmoid-multiply and add -- the tests' reference and the other side of the timing A/B.
 HIP_MBCONV = os.environ.get("MCD_NO_HIP_MBCONV", "0") != "1"
+# The ResNet-50 target's inference route on channels-last activations with folded batch norm (core.conv7x7s2_nhwc,
+# bn_relu_maxpool_nhwc, conv_igemm_nhwc: K16-K18, and the 1x1 convolutions as hipBLASLt GEMMs with the skip add and the
+# ReLU in their epilogue).  MCD_NO_HIP_RESNET=1 restores the ATen NCHW route everywhere.
+HIP_RESNET = os.environ.get("MCD_NO_HIP_RESNET", "0") != "1"
 
 
 class _LayerNorm(nn.LayerNorm):
@@ -257,12 +261,13 @@ def fold_bn(weight, bn):
     return w.to(weight.dtype), b.to(weight.dtype)
 
 
-def _folded(module, names, build):
+def _folded(module, names, build, own=False):
     """build(module) -> dict of folded tensors, computed once and cached in the module's __dict__ (no parameter or buffer
     is registered: state_dict() and the module tree stay as they are).  The cache is keyed on the version counter and the
-    storage of every tensor of the named submodules, and on the device, like ViTTower._embed_residual's."""
-    srcs = [t for n in names for m in (getattr(module, n, None),) if m is not None
-            for t in list(m.parameters(recurse=False)) + list(m.buffers(recurse=False))]
+    storage of every tensor of the named submodules (all of their tensors, nested ones included; own=True: of the module
+    itself), and on the device, like ViTTower._embed_residual's."""
+    mods = [module] if own else [getattr(module, n, None) for n in names]
+    srcs = [t for m in mods if m is not None for t in list(m.parameters()) + list(m.buffers())]
     key = tuple((t._version, t.data_ptr()) for t in srcs) + (srcs[0].device, srcs[0].dtype)
     cache = module.__dict__.setdefault("_mbconv_fold", {})
     if cache.get("key") != key:
@@ -575,10 +580,77 @@ class ClipViT(nn.Module):
 # ------------------------------------------------------------------------------------------------------
 # ResNet-50 (torchvision layout: conv1, bn1, layer1..4, fc)
 # ------------------------------------------------------------------------------------------------------
+_BOTTLENECK_SKIPPED = ("conv1", "bn1", "conv2", "bn2", "conv3", "bn3", "downsample")
+_RESNET_SKIPPED = ("bn1",)
+
+
+def _conv_out(n, k, s, p):
+    return (n + 2 * p - k) // s + 1
+
+
+def resnet_route(module, x):
+    """'hip' when the ResNet-50 target (a ResNet50 or its stem convolution, with the NCHW-contiguous input image) or one
+    of its blocks (a _Bottleneck with a channels_last-contiguous input) can take the HIP route: HIP_RESNET on, a CUDA fp32
+    tensor, inference (no autograd, eval mode), libmcd_blaslt.so loaded, widths K16-K18 take (stem: Cin <= 4, Cout a
+    multiple of 4, 7x7 / 2 / pad 3; block: every width a multiple of 32, stride 1 or 2), one image's tensors under 2^31
+    bytes, at most 65535 images, and no hook on a submodule the route does not call (a hook on layer2[0].conv2 must fire,
+    so that block takes ATen; the hook points of the tower itself -- conv1 and layer1..4 -- are called as modules on
+    either route).  'aten' otherwise."""
+    if not (HIP_RESNET and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and not torch.is_grad_enabled() and not module.training and x.shape[0] <= 65535):
+        return "aten"
+    from .. import core
+    if not core.linear_residual_available():
+        return "aten"
+    B, C, H, W = x.shape
+    if H < 1 or W < 1:
+        return "aten"
+    if isinstance(module, _Bottleneck):
+        cin, width, cout, s = module.conv1.in_channels, module.conv2.in_channels, module.conv3.out_channels, module.stride
+        ho, wo = _conv_out(H, 3, s, 1), _conv_out(W, 3, s, 1)
+        if (C != cin or cin % 32 or width % 32 or cout % 32 or s not in (1, 2)
+                or not x.is_contiguous(memory_format=torch.channels_last) or x.data_ptr() % 16
+                or max(cin, width) * H * W * 4 >= 2 ** 31 or cout * ho * wo * 4 >= 2 ** 31
+                or 9 * width * width * 4 >= 2 ** 31):
+            return "aten"
+        names = _BOTTLENECK_SKIPPED
+        if module.downsample is not None and _hooks_on(module.downsample, ("0", "1")):
+            return "aten"
+    elif isinstance(module, (ResNet50, _StemConv)):
+        stem = module.conv1 if isinstance(module, ResNet50) else module
+        ho, wo = _conv_out(H, 7, 2, 3), _conv_out(W, 7, 2, 3)
+        if (C != stem.in_channels or C > 4 or stem.out_channels % 4 or stem.kernel_size != (7, 7)
+                or stem.stride != (2, 2) or stem.padding != (3, 3) or stem.dilation != (1, 1) or stem.groups != 1
+                or stem.bias is not None or not x.is_contiguous() or x.data_ptr() % 16
+                or C * H * W * 4 >= 2 ** 31 or stem.out_channels * ho * wo * 4 >= 2 ** 31):
+            return "aten"
+        if isinstance(module, _StemConv):
+            return "hip"                                # nothing inside it is skipped; its own hooks fire
+        if ho < 1 or wo < 1 or not isinstance(stem, _StemConv):
+            return "aten"
+        names = _RESNET_SKIPPED
+    else:
+        return "aten"
+    return "aten" if _hooks_on(module, names) else "hip"
+
+
+class _StemConv(nn.Conv2d):
+    """ResNet-50's conv1.  On the HIP route K16 computes it and the result comes back as a [B, Cout, Ho, Wo] view of
+    channels-last memory; it is still called as a module, so a hook on conv1 sees the raw convolution output."""
+
+    def forward(self, x):
+        if resnet_route(self, x) == "hip":
+            from .. import core
+            w = _folded(self, (), lambda m: m.weight.detach().permute(1, 2, 3, 0).contiguous(), own=True)   # tap-major
+            return core.conv7x7s2_nhwc(x, w).permute(0, 3, 1, 2)
+        return super().forward(x)
+
+
 class _Bottleneck(nn.Module):
     def __init__(self, cin, width, stride):
         super().__init__()
         cout = width * 4
+        self.stride = stride
         self.conv1 = nn.Conv2d(cin, width, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(width)
         self.conv2 = nn.Conv2d(width, width, 3, stride, 1, bias=False)
@@ -590,16 +662,75 @@ class _Bottleneck(nn.Module):
             self.downsample = nn.Sequential(nn.Conv2d(cin, cout, 1, stride, bias=False), nn.BatchNorm2d(cout))
 
     def forward(self, x):
+        if resnet_route(self, x) == "hip":
+            return self._forward_hip(x)
         y = F.relu(self.bn1(self.conv1(x)))
         y = F.relu(self.bn2(self.conv2(y)))
         y = self.bn3(self.conv3(y))
         return F.relu(y + (x if self.downsample is None else self.downsample(x)))
 
+    def _forward_hip(self, x):
+        """The block on channels-last activations: conv1 as a GEMM (raw, folded bn1 as its bias; its ReLU is K18's
+        relu_in), conv2 by K18 (3x3, folded bn2, ReLU on the way in and out), the downsample as a GEMM (stride 1) or
+        K18 1x1 / 2 (stride 2) with folded BN, conv3 as one GEMM with folded bn3 as its bias, the skip as its residual
+        operand and the ReLU as its epilogue.  Returns [B, C, H, W] in channels_last memory."""
+        from .. import core
+        f = _folded(self, _BOTTLENECK_SKIPPED, _Bottleneck._fold)
+        xn = x.permute(0, 2, 3, 1)                                   # [B, H, W, cin], contiguous
+        h = core.linear_residual(None, xn, f["w1"], f["b1"])
+        h = core.conv_igemm_nhwc(h, f["w2"], f["b2"], 3, self.stride, relu_in=True, relu_out=True)
+        if self.downsample is None:
+            res = xn
+        elif self.stride == 1:
+            res = core.linear_residual(None, xn, f["wd"], f["bd"])
+        else:
+            res = core.conv_igemm_nhwc(xn, f["wd"], f["bd"], 1, 2)
+        return core.linear_residual(res, h, f["w3"], f["b3"], relu=True).permute(0, 3, 1, 2)
+
+    def _fold(self):
+        f = {}
+        w1, f["b1"] = fold_bn(self.conv1.weight, self.bn1)
+        f["w1"] = w1.flatten(1).contiguous()
+        w2, f["b2"] = fold_bn(self.conv2.weight, self.bn2)
+        f["w2"] = igemm_weight(w2)
+        w3, f["b3"] = fold_bn(self.conv3.weight, self.bn3)
+        f["w3"] = w3.flatten(1).contiguous()
+        if self.downsample is not None:
+            wd, f["bd"] = fold_bn(self.downsample[0].weight, self.downsample[1])
+            f["wd"] = igemm_weight(wd)                               # 1x1: [Cout, Cin] either way
+        return f
+
+
+def igemm_weight(w):
+    """K18's weight layout: [Cout, Cin, kh, kw] -> [Cout, kh*kw*Cin], tap-major then channel."""
+    return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
+
+
+def bn_scale_shift(bn):
+    """(scale, shift) of an eval-mode batch norm as y = x * scale + shift, computed in float64 like fold_bn."""
+    scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+    shift = bn.bias.detach().double() - bn.running_mean.detach().double() * scale
+    return scale.to(bn.weight.dtype).contiguous(), shift.to(bn.weight.dtype).contiguous()
+
+
+class _Stage(nn.Sequential):
+    """layer1..4: a Sequential that keeps handing on channels-last memory when it was given channels-last memory (a
+    block that took ATen, for a hook inside it, say, may hand back NCHW memory, which the next block's HIP route
+    refuses).  On NCHW input it is a plain Sequential."""
+
+    def forward(self, x):
+        keep = x.dim() == 4 and not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last)
+        for b in self:
+            x = b(x)
+            if keep:
+                x = x.contiguous(memory_format=torch.channels_last)
+        return x
+
 
 class ResNet50(nn.Module):
     def __init__(self, num_classes=1000):
         super().__init__()
-        self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
+        self.conv1 = _StemConv(3, 64, 7, 2, 3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         cin = 64
         for i, (w, n, s) in enumerate([(64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2)], 1):
@@ -607,13 +738,28 @@ class ResNet50(nn.Module):
             for j in range(n):
                 blocks.append(_Bottleneck(cin, w, s if j == 0 else 1))
                 cin = w * 4
-            setattr(self, "layer%d" % i, nn.Sequential(*blocks))
+            setattr(self, "layer%d" % i, _Stage(*blocks))
         self.fc = nn.Linear(cin, num_classes)
 
     def forward(self, x):
+        if resnet_route(self, x) == "hip":
+            return self._forward_hip(x)
         x = F.max_pool2d(F.relu(self.bn1(self.conv1(x))), 3, 2, 1)
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         return self.fc(x.mean(dim=[2, 3]))
+
+    def _forward_hip(self, x):
+        """conv1 called as a module (K16 inside; a hook on it fires on the raw output), bn1 + ReLU + max pooling by K17,
+        layer1..4 called as modules (hooks on them fire; each block picks its own route), the mean over the pixels by
+        K0n, fc."""
+        from .. import core
+        scale, shift = _folded(self, _RESNET_SKIPPED, lambda m: bn_scale_shift(m.bn1))
+        x = self.conv1(x).contiguous(memory_format=torch.channels_last)     # a no-op copy on the HIP route
+        x = core.bn_relu_maxpool_nhwc(x.permute(0, 2, 3, 1), scale, shift).permute(0, 3, 1, 2)
+        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))         # _Stage keeps the memory channels-last
+        pooled = torch.empty((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
+        core.hook_pool(x, "avg", pooled, 0, 0, False)                      # K0n: the mean over the pixels, batch-invariant
+        return self.fc(pooled)
 
     encode_image = forward  # describe_og_neurons.py calls encode_image on every target (SURVEY.md section 3C)
 

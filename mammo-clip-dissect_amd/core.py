@@ -574,6 +574,81 @@ def silu_avg_pool_nhwc(x):
     return out
 
 
+# ---- K16 - K18: the ResNet-50 target on channels-last activations (csrc/k_resnet.hip) ---------------------------
+def conv_out(n, k, s, p):
+    """Output size of one axis under ResNet's symmetric padding: (n + 2p - k) // s + 1."""
+    return (n + 2 * p - k) // s + 1
+
+
+@_on_device
+def conv7x7s2_nhwc(x, w_tap):
+    """K16: the raw stem convolution conv7x7/2, pad 3 (no bias, no batch norm, no ReLU): x NCHW [B, Cin, H, W]
+    (Cin <= 4), w_tap [Cin, 7, 7, Cout] (tap-major, Cout % 4 == 0) -> NHWC [B, Ho, Wo, Cout]."""
+    _need_gpu(x)
+    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
+        raise TypeError("conv7x7s2_nhwc: x must be a contiguous float32 [B, Cin, H, W] tensor")
+    B, Cin, H, W = x.shape
+    if w_tap.dim() != 4 or tuple(w_tap.shape[:3]) != (Cin, 7, 7) or Cin > 4 or w_tap.shape[3] % 4:
+        raise ValueError("conv7x7s2_nhwc: w_tap must be [Cin, 7, 7, Cout] with Cin = %d <= 4 and Cout %% 4 == 0, got %s"
+                         % (Cin, tuple(w_tap.shape)))
+    if H < 1 or W < 1:
+        raise ValueError("conv7x7s2_nhwc: empty image")
+    Cout = w_tap.shape[3]
+    _vec(w_tap, Cin * 49 * Cout, "w_tap")
+    if w_tap.data_ptr() % 16:
+        raise ValueError("conv7x7s2_nhwc: w_tap must be 16-byte aligned")
+    y = torch.empty((B, conv_out(H, 7, 2, 3), conv_out(W, 7, 2, 3), Cout), dtype=torch.float32, device=x.device)
+    L = _lib.load()
+    check(L.mcd_conv7x7s2_nhwc(x.data_ptr(), B, Cin, H, W, w_tap.data_ptr(), Cout, y.data_ptr(), _stream()))
+    return y
+
+
+@_on_device
+def bn_relu_maxpool_nhwc(x, scale, shift):
+    """K17: max over the 3x3 / stride 2 / pad 1 window of relu(x * scale[c] + shift[c]): NHWC [B, H, W, C] (C % 4 == 0)
+    -> [B, Ho, Wo, C]."""
+    x = _nhwc(x, "x")
+    B, H, W, C = x.shape
+    if C % 4 or H < 1 or W < 1:
+        raise ValueError("bn_relu_maxpool_nhwc: C = %d must be a multiple of 4 and the image non-empty" % C)
+    _vec(scale, C, "scale")
+    _vec(shift, C, "shift")
+    if x.data_ptr() % 16 or scale.data_ptr() % 16 or shift.data_ptr() % 16:
+        raise ValueError("bn_relu_maxpool_nhwc: tensors must be 16-byte aligned")
+    y = torch.empty((B, conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1), C), dtype=torch.float32, device=x.device)
+    L = _lib.load()
+    check(L.mcd_bn_relu_maxpool_nhwc(x.data_ptr(), B, H, W, C, scale.data_ptr(), shift.data_ptr(), y.data_ptr(), _stream()))
+    return y
+
+
+@_on_device
+def conv_igemm_nhwc(x, w_tap, bias, k, stride, relu_in=False, relu_out=False):
+    """K18: implicit-GEMM convolution on the exact-fp32 MFMA: x NHWC [B, H, W, Cin], w_tap [Cout, k*k*Cin] (tap-major,
+    then channel), bias [Cout] -> NHWC [B, Ho, Wo, Cout] = act_out(bias + conv(act_in(x))), act = ReLU where the flag is
+    set.  k = 3 with stride 1 or 2 (pad 1), or k = 1 with stride 2 (pad 0); Cin and Cout multiples of 32."""
+    x = _nhwc(x, "x")
+    B, H, W, Cin = x.shape
+    if (k, stride) not in ((3, 1), (3, 2), (1, 2)):
+        raise ValueError("conv_igemm_nhwc: k = %r, stride = %r (3x3 / 1, 3x3 / 2 or 1x1 / 2)" % (k, stride))
+    if w_tap.dim() != 2 or w_tap.shape[1] != k * k * Cin:
+        raise ValueError("conv_igemm_nhwc: w_tap must be [Cout, %d], got %s" % (k * k * Cin, tuple(w_tap.shape)))
+    Cout = w_tap.shape[0]
+    if Cin % 32 or Cout % 32 or H < 1 or W < 1:
+        raise ValueError("conv_igemm_nhwc: Cin = %d and Cout = %d must be multiples of 32 and the image non-empty"
+                         % (Cin, Cout))
+    _vec(w_tap, Cout * k * k * Cin, "w_tap")
+    _vec(bias, Cout, "bias")
+    if x.data_ptr() % 16 or w_tap.data_ptr() % 16 or bias.data_ptr() % 16:
+        raise ValueError("conv_igemm_nhwc: tensors must be 16-byte aligned")
+    pad = 1 if k == 3 else 0
+    y = torch.empty((B, conv_out(H, k, stride, pad), conv_out(W, k, stride, pad), Cout), dtype=torch.float32,
+                    device=x.device)
+    L = _lib.load()
+    check(L.mcd_conv_igemm_nhwc(x.data_ptr(), B, H, W, Cin, w_tap.data_ptr(), bias.data_ptr(), Cout, int(k), int(stride),
+                                1 if relu_in else 0, 1 if relu_out else 0, y.data_ptr(), _stream()))
+    return y
+
+
 # ---- encoder-side linear + bias + residual on hipBLASLt (libmcd_blaslt.so) ------------------------
 _blaslt_ws = {}
 # bench.py sets this to a list to time the library GEMMs inside the forwards: every call then appends
@@ -587,7 +662,7 @@ def linear_residual_available():
 
 def encoder_gemm_picks():
     """[(M, N, K, has_res, pick)]: the hipBLASLt algorithm (index into the heuristic's list) this process keeps for every
-    encoder GEMM shape it has run through linear_residual."""
+    encoder GEMM shape it has run through linear_residual.  has_res: bit 0 = a residual operand, bit 1 = relu=True."""
     L = _lib.load_blaslt()
     if L is None:
         return []
@@ -608,10 +683,12 @@ def set_encoder_gemm_picks(picks):
 
 
 @_on_device
-def linear_residual(res, h, weight, bias=None, out=None):
+def linear_residual(res, h, weight, bias=None, out=None, relu=False):
     """out = res + h @ weight.T + bias in ONE hipBLASLt GEMM (bias epilogue + beta*C), instead of nn.Linear followed
     by an elementwise add over the whole residual stream.  res, h: [..., N] / [..., K] contiguous fp32 with the same
-    leading shape; weight [N, K]; out defaults to a new tensor (pass out=res for in place).  res may be None."""
+    leading shape; weight [N, K]; out defaults to a new tensor (pass out=res for in place).  res may be None.
+    relu=True: out = relu(res + h @ weight.T + bias), the library's ReLU epilogue (mcd_linear_residual_relu; its plans
+    and picks are kept apart from the plain entry's)."""
     L = _lib.load_blaslt()
     if L is None:
         raise ImportError("libmcd_blaslt.so is not available (make -C mammo-clip-dissect_amd/csrc)")
@@ -636,9 +713,9 @@ def linear_residual(res, h, weight, bias=None, out=None):
     if ev is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    rc = L.mcd_linear_residual(h.data_ptr(), K, weight.data_ptr(), K, bias.data_ptr() if bias is not None else None,
-                               res.data_ptr() if res is not None else None, N, out.data_ptr(), N, M, N, K,
-                               ws.data_ptr(), ws.numel(), _stream())
+    fn = L.mcd_linear_residual_relu if relu else L.mcd_linear_residual
+    rc = fn(h.data_ptr(), K, weight.data_ptr(), K, bias.data_ptr() if bias is not None else None,
+            res.data_ptr() if res is not None else None, N, out.data_ptr(), N, M, N, K, ws.data_ptr(), ws.numel(), _stream())
     if ev is not None:
         e1.record()
         ev.append((e0, e1, M, N, K))

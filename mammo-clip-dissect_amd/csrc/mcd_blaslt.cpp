@@ -6,6 +6,8 @@
 // re-writes the whole residual stream (454 MB per add at 250 images: 69 us, twice per block = 2.4 % of the headline
 // step).  hipBLASLt's own epilogue takes the bias AND beta * C in the same kernel: the residual is read once inside
 // the GEMM (hidden under the MFMAs) and the sum is written once.
+// mcd_linear_residual_relu is the same call with the library's ReLU epilogue on the whole sum: a ResNet Bottleneck's
+// conv3 + folded bn3 + skip add + relu on channels-last rows.
 // A plain library GEMM (no hand-written kernel here); kept in its own shared object so that libmcd_hip.so carries no
 // dependency on hipBLASLt -- the Python side loads this one lazily and keeps PyTorch's two-kernel path if it is absent.
 //
@@ -59,6 +61,8 @@ struct Plan {
 constexpr int kMaxDev = 64;
 using Key = std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int, int>;   // ..., device
 using ShapeKey = std::tuple<int64_t, int64_t, int64_t, int>;                                            // M, N, K, has_res
+// The has_res field of both keys (and of the get_picks / set_pick records): bit 0 = a residual operand, bit 1 = the ReLU
+// epilogue of mcd_linear_residual_relu.  The two entries never share a plan or a pick.
 std::mutex g_mu;
 hipblasLtHandle_t g_handles[kMaxDev] = {};
 std::map<Key, Plan> g_plans;
@@ -127,12 +131,13 @@ extern "C" int mcd_linear_residual_get_picks(int64_t* out, int cap) {
 // already made for the shape is dropped and rebuilt with the forced pick on the next call.
 extern "C" int mcd_linear_residual_set_pick(int64_t M, int64_t N, int64_t K, int has_res, int pick) {
     std::lock_guard<std::mutex> lk(g_mu);
-    const ShapeKey sk{M, N, K, has_res ? 1 : 0};
+    const int flags = has_res & 3;
+    const ShapeKey sk{M, N, K, flags};
     if (pick < 0) g_forced.erase(sk);
     else g_forced[sk] = pick;
     for (auto it = g_plans.begin(); it != g_plans.end();) {
         if (std::get<0>(it->first) == M && std::get<1>(it->first) == N && std::get<2>(it->first) == K &&
-            std::get<7>(it->first) == (has_res ? 1 : 0)) {
+            std::get<7>(it->first) == flags) {
             destroy_plan(it->second);
             it = g_plans.erase(it);
         } else {
@@ -142,9 +147,11 @@ extern "C" int mcd_linear_residual_set_pick(int64_t M, int64_t N, int64_t K, int
     return MCD_OK;
 }
 
-extern "C" int mcd_linear_residual(const float* h, int64_t ldh, const float* W, int64_t ldw, const float* bias,
-                                   const float* res, int64_t ldr, float* out, int64_t ldo, int64_t M, int64_t N, int64_t K,
-                                   void* ws, size_t ws_bytes, mcd_blaslt_stream_t stream) {
+namespace {
+
+int linear_residual(const float* h, int64_t ldh, const float* W, int64_t ldw, const float* bias, const float* res,
+                    int64_t ldr, float* out, int64_t ldo, int64_t M, int64_t N, int64_t K, void* ws, size_t ws_bytes,
+                    mcd_blaslt_stream_t stream, bool relu) {
     if (!h || !W || !out) return fail(MCD_E_ARG, "mcd_linear_residual: NULL pointer");
     if (M < 0 || N <= 0 || K <= 0 || ldh < K || ldw < K || ldo < N || (res && ldr < N))
         return fail(MCD_E_ARG, "mcd_linear_residual: bad shape M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
@@ -154,7 +161,8 @@ extern "C" int mcd_linear_residual(const float* h, int64_t ldh, const float* W, 
     const int dev = cur_device();
     if (!g_handles[dev]) LT(hipblasLtCreate(&g_handles[dev]));
     hipblasLtHandle_t g_handle = g_handles[dev];
-    const Key key{M, N, K, ldh, ldw, res ? ldr : 0, ldo, res ? 1 : 0, bias ? 1 : 0, dev};
+    const int flags = (res ? 1 : 0) | (relu ? 2 : 0);
+    const Key key{M, N, K, ldh, ldw, res ? ldr : 0, ldo, flags, bias ? 1 : 0, dev};
     auto it = g_plans.find(key);
     const float one = 1.f, zero = 0.f;
     const float* beta = res ? &one : &zero;
@@ -166,10 +174,10 @@ extern "C" int mcd_linear_residual(const float* h, int64_t ldh, const float* W, 
         const int32_t ta = HIPBLAS_OP_T, tb = HIPBLAS_OP_N;
         LT(hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_TRANSA, &ta, sizeof(ta)));
         LT(hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_TRANSB, &tb, sizeof(tb)));
-        if (bias) {
-            const uint32_t ep = HIPBLASLT_EPILOGUE_BIAS;
+        if (bias || relu) {
+            const uint32_t ep = bias ? (relu ? HIPBLASLT_EPILOGUE_RELU_BIAS : HIPBLASLT_EPILOGUE_BIAS) : HIPBLASLT_EPILOGUE_RELU;
             LT(hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_EPILOGUE, &ep, sizeof(ep)));
-            LT(hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_BIAS_POINTER, &bias, sizeof(bias)));
+            if (bias) LT(hipblasLtMatmulDescSetAttribute(p.desc, HIPBLASLT_MATMUL_DESC_BIAS_POINTER, &bias, sizeof(bias)));
         }
         LT(hipblasLtMatrixLayoutCreate(&p.a, HIP_R_32F, (uint64_t)K, (uint64_t)N, ldw));
         LT(hipblasLtMatrixLayoutCreate(&p.b, HIP_R_32F, (uint64_t)K, (uint64_t)M, ldh));
@@ -194,7 +202,7 @@ extern "C" int mcd_linear_residual(const float* h, int64_t ldh, const float* W, 
         // a forced pick (mcd_linear_residual_set_pick) or MCD_BLASLT_PICK=heuristic: nothing is timed
         int forced = -1;
         {
-            auto f = g_forced.find(ShapeKey{M, N, K, res ? 1 : 0});
+            auto f = g_forced.find(ShapeKey{M, N, K, flags});
             if (f != g_forced.end()) forced = f->second < n ? f->second : 0;
             else if (const char* e = getenv("MCD_BLASLT_PICK")) {
                 if (e[0] == 'h') {
@@ -251,4 +259,20 @@ extern "C" int mcd_linear_residual(const float* h, int64_t ldh, const float* W, 
     if (p.ws > (ws ? ws_bytes : 0)) return fail(MCD_E_ARG, "mcd_linear_residual: workspace of %zu bytes needed", p.ws);
     LT(hipblasLtMatmul(g_handle, p.desc, &one, W, p.a, h, p.b, beta, cptr, p.c, out, p.d, &p.algo, ws, p.ws, st));
     return MCD_OK;
+}
+
+}  // namespace
+
+extern "C" int mcd_linear_residual(const float* h, int64_t ldh, const float* W, int64_t ldw, const float* bias,
+                                   const float* res, int64_t ldr, float* out, int64_t ldo, int64_t M, int64_t N, int64_t K,
+                                   void* ws, size_t ws_bytes, mcd_blaslt_stream_t stream) {
+    return linear_residual(h, ldh, W, ldw, bias, res, ldr, out, ldo, M, N, K, ws, ws_bytes, stream, false);
+}
+
+// out = relu(res + h . W^T + bias): the same call with hipBLASLt's ReLU epilogue (RELU_BIAS, or RELU without a bias),
+// which the library applies to the whole sum alpha*A.B + beta*C + bias.
+extern "C" int mcd_linear_residual_relu(const float* h, int64_t ldh, const float* W, int64_t ldw, const float* bias,
+                                        const float* res, int64_t ldr, float* out, int64_t ldo, int64_t M, int64_t N,
+                                        int64_t K, void* ws, size_t ws_bytes, mcd_blaslt_stream_t stream) {
+    return linear_residual(h, ldh, W, ldw, bias, res, ldr, out, ldo, M, N, K, ws, ws_bytes, stream, true);
 }

@@ -1,0 +1,179 @@
+"""The ResNet-50 target's HIP route (K16-K18, csrc/k_resnet.hip) measured.  Dev tool.
+
+  --kernels [B]   K16, K17 and K18 at every ResNet-50 shape of a 224 x 224 input (batch B, default 250): device events
+                  after a warm-up; flop, ms, TFLOP/s and the fraction of the fp32 peak (157.3 TFLOP/s, the MFMA's and the
+                  packed VALU's alike), and beside each convolution ATen's F.conv2d on the NCHW tensor (MIOpen, the route
+                  the kernel replaces) on the same device.
+  --driver [N]    describe_clip_neurons.main() on synthetic_<N>_224 (default 10000), batch --batch (default 250), conv1 +
+                  layer1..4, after a warm-up run on 2 batches: prints one JSON line with images/s.  --keep DIR copies the
+                  CSV there (for --compare).
+  --forwards [N]  N (default 4) forwards of the tower at batch 250, for a rocprofv3 --kernel-trace --stats pass.
+  --compare A B   two descriptions.csv: how many neurons agree on the top-1 concept and on the top-5 images.
+
+Every measurement of --kernels / --driver runs in a fresh child process of this script (the route flag MCD_NO_HIP_RESNET
+is read at import, and MIOpen / hipBLASLt keep per-process state); the child is started with subprocess, nothing replaces
+a process image.  The script only needs what the parent of the route had, so it can be copied into an older tree."""
+import json
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PEAK = 157.3
+LAYERS = "conv1,layer1,layer2,layer3,layer4"
+# (name, Cin, Cout, H, W, k, stride, how many of them in the network)
+CONVS = [("layer1 3x3", 64, 64, 56, 56, 3, 1, 3), ("layer2 3x3/2", 128, 128, 56, 56, 3, 2, 1),
+         ("layer2 3x3", 128, 128, 28, 28, 3, 1, 3), ("layer3 3x3/2", 256, 256, 28, 28, 3, 2, 1),
+         ("layer3 3x3", 256, 256, 14, 14, 3, 1, 5), ("layer4 3x3/2", 512, 512, 14, 14, 3, 2, 1),
+         ("layer4 3x3", 512, 512, 7, 7, 3, 1, 2), ("layer2 ds 1x1/2", 256, 512, 56, 56, 1, 2, 1),
+         ("layer3 ds 1x1/2", 512, 1024, 28, 28, 1, 2, 1), ("layer4 ds 1x1/2", 1024, 2048, 14, 14, 1, 2, 1)]
+
+
+def arg_n(flag, default):
+    i = sys.argv.index(flag)
+    return int(sys.argv[i + 1]) if len(sys.argv) > i + 1 and sys.argv[i + 1].isdigit() else default
+
+
+def opt(flag, default):
+    return sys.argv[sys.argv.index(flag) + 1] if flag in sys.argv else default
+
+
+def child(args, timeout):
+    """Run this script again with `args` in a fresh process and pass its output through."""
+    r = subprocess.run([sys.executable, os.path.abspath(__file__)] + args, timeout=timeout)
+    if r.returncode != 0:
+        sys.exit(r.returncode)
+
+
+def timeit(fn, n=10):
+    import torch
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(n):
+        fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / n
+
+
+def kernels_child(B, which):
+    sys.path.insert(0, ROOT)
+    import torch
+    import torch.nn.functional as F
+    import mammo_clip_dissect_amd  # noqa: F401
+    from mammo_clip_dissect_amd import core
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+
+    def line(name, flop, ms, ms_aten):
+        tf = flop / ms / 1e9
+        print("B=%d %-16s %8.2f GFLOP  %8.3f ms  %6.1f TFLOP/s  %.3f of peak   ATen %8.3f ms  ATen / HIP %.2f"
+              % (B, name, flop / 1e9, ms, tf, tf / PEAK, ms_aten, ms_aten / ms), flush=True)
+    if which == "stem":
+        x = torch.randn(B, 3, 224, 224, device=dev, generator=g)
+        w = torch.randn(64, 3, 7, 7, device=dev, generator=g) / 12
+        wt = w.permute(1, 2, 3, 0).contiguous()
+        ms = timeit(lambda: core.conv7x7s2_nhwc(x, wt))
+        ms_a = timeit(lambda: F.conv2d(x, w, None, 2, 3))
+        line("K16 stem 7x7/2", 2.0 * B * 112 * 112 * 64 * 147, ms, ms_a)
+        y = torch.randn(B, 112, 112, 64, device=dev, generator=g)
+        sc, sh = torch.rand(64, device=dev, generator=g) + 0.5, torch.randn(64, device=dev, generator=g)
+        ms = timeit(lambda: core.bn_relu_maxpool_nhwc(y, sc, sh))
+        yn = y.permute(0, 3, 1, 2).contiguous()
+        ms_a = timeit(lambda: F.max_pool2d(F.relu(yn * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1)), 3, 2, 1))
+        gb = 4.0 * B * 64 * (112 * 112 + 56 * 56) / 1e9
+        print("B=%d %-16s %8.2f GB     %8.3f ms  %6.2f TB/s                       ATen %8.3f ms  ATen / HIP %.2f"
+              % (B, "K17 bn+relu+pool", gb, ms, gb / ms, ms_a, ms_a / ms), flush=True)
+        return
+    name, Cin, Cout, H, W, k, s, count = CONVS[int(which)]
+    pad = 1 if k == 3 else 0
+    Ho, Wo = (H + 2 * pad - k) // s + 1, (W + 2 * pad - k) // s + 1
+    x = torch.randn(B, H, W, Cin, device=dev, generator=g)
+    w = torch.randn(Cout, Cin, k, k, device=dev, generator=g) / (Cin * k * k) ** 0.5
+    b = torch.randn(Cout, device=dev, generator=g)
+    wt = w.permute(0, 2, 3, 1).reshape(Cout, -1).contiguous()
+    relu = k == 3
+    ms = timeit(lambda: core.conv_igemm_nhwc(x, wt, b, k, s, relu_in=relu, relu_out=relu))
+    xn = x.permute(0, 3, 1, 2).contiguous()
+    ms_a = timeit(lambda: F.conv2d(xn, w, None, s, pad))             # the convolution alone: bn and relu are extra kernels
+    line("K18 %s (x%d)" % (name, count), 2.0 * B * Ho * Wo * Cout * k * k * Cin, ms, ms_a)
+
+
+def driver_child(n, batch, keep):
+    sys.path.insert(0, ROOT)
+    import torch
+    import mammo_clip_dissect_amd as m
+    from mammo_clip_dissect_amd.concept_vit import data_utils, describe_clip_neurons as drv
+    concepts = os.path.join(os.path.dirname(m.__file__), "Concepts", "Specific_concepts_sorted.txt")
+    route = "hip" if getattr(data_utils, "HIP_RESNET", False) else "aten"
+    for count in (2 * batch, n):
+        tmp = tempfile.mkdtemp()
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = drv.main(["--target_model", "resnet50", "--target_layers", LAYERS, "--d_probe",
+                            "synthetic_%d_224" % count, "--concept_set", concepts, "--batch_size", str(batch), "--device",
+                            "cuda:0", "--activation_dir", tmp + "/acts", "--result_dir", tmp + "/results"])
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            if keep and count == n:
+                os.makedirs(keep, exist_ok=True)
+                shutil.copy(os.path.join(out, "descriptions.csv"), os.path.join(keep, "descriptions_%s.csv" % route))
+        finally:
+            shutil.rmtree(tmp, ignore_errors=True)
+    print(json.dumps({"tool": "scripts/resnet_timing.py --driver", "route": route, "images": n, "batch": batch,
+                      "layers": LAYERS, "seconds": round(dt, 3), "images_per_s": round(n / dt, 1)}), flush=True)
+
+
+def forwards_child(n):
+    sys.path.insert(0, ROOT)
+    import torch
+    import mammo_clip_dissect_amd  # noqa: F401
+    from mammo_clip_dissect_amd.concept_vit import data_utils
+    dev = torch.device("cuda:0")
+    net, _ = data_utils.get_target_model("resnet50", dev)
+    x = torch.randn(250, 3, 224, 224, device=dev)
+    with torch.no_grad():
+        for _ in range(n):
+            net(x)
+    torch.cuda.synchronize()
+    print("%d forwards done, route %s" % (n, "hip" if getattr(data_utils, "HIP_RESNET", False) else "aten"))
+
+
+def compare(a, b):
+    import pandas as pd
+    da, db = pd.read_csv(a), pd.read_csv(b)
+    assert len(da) == len(db) and (da.layer == db.layer).all() and (da.unit == db.unit).all()
+    same_c = da.description == db.description
+    same_i = da.images.astype(str) == db.images.astype(str)
+    print("neurons %d  top-1 concept agrees %d  top-5 images agree %d" % (len(da), int(same_c.sum()), int(same_i.sum())))
+    for i in da.index[~same_c][:40]:
+        print("  %s[%d]: %r (%.6f) vs %r (%.6f)" % (da.layer[i], da.unit[i], da.description[i], da.similarity[i],
+                                                      db.description[i], db.similarity[i]))
+
+
+if __name__ == "__main__":
+    if "--child-kernels" in sys.argv:
+        kernels_child(int(sys.argv[2]), sys.argv[3])
+    elif "--child-driver" in sys.argv:
+        driver_child(int(sys.argv[2]), int(sys.argv[3]), sys.argv[4] if len(sys.argv) > 4 else None)
+    elif "--kernels" in sys.argv:
+        B = arg_n("--kernels", 250)
+        for which in ["stem"] + [str(i) for i in range(len(CONVS))]:
+            child(["--child-kernels", str(B), which], 300)
+    elif "--driver" in sys.argv:
+        keep = opt("--keep", None)
+        child(["--child-driver", str(arg_n("--driver", 10000)), opt("--batch", "250")] + ([keep] if keep else []), 900)
+    elif "--forwards" in sys.argv:
+        forwards_child(arg_n("--forwards", 4))
+    elif "--compare" in sys.argv:
+        i = sys.argv.index("--compare")
+        compare(sys.argv[i + 1], sys.argv[i + 2])
+    else:
+        print(__doc__)
