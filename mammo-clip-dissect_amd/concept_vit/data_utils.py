@@ -22,6 +22,9 @@ import zlib
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.nn.modules import module as _nn_module
+
+from .. import core
 
 PROJ_DIM = 512
 # The image tower's mask-free fp32 attention runs on the HIP kernels K9 (T <= 256) and K9L (longer sequences, the
@@ -49,6 +52,31 @@ HIP_MBCONV = os.environ.get("MCD_NO_HIP_MBCONV", "0") != "1"
 # bn_relu_maxpool_nhwc, conv_igemm_nhwc: K16-K18, and the 1x1 convolutions as hipBLASLt GEMMs with the skip add and the
 # ReLU in their epilogue).  MCD_NO_HIP_RESNET=1 restores the ATen NCHW route everywhere.
 HIP_RESNET = os.environ.get("MCD_NO_HIP_RESNET", "0") != "1"
+MAX_BATCH = 65535      # the images of one call that the K12-K18 entries accept
+
+
+# ---- the gate: when a forward may leave ATen for the HIP kernels ---------------------------------------------------------
+def _hip_eligible(on_gpu, dtype, grad):
+    """The base of every route: a call may leave ATen when it is fp32 on the GPU and autograd does not record it."""
+    return bool(on_gpu) and dtype == torch.float32 and not grad
+
+
+def _eligible(x):
+    """_hip_eligible for the tensor a module was called with, under the current grad mode."""
+    return isinstance(x, torch.Tensor) and _hip_eligible(x.is_cuda, x.dtype, torch.is_grad_enabled())
+
+
+def _tower_gate(flag, module, x):
+    """What mbconv_route and resnet_route ask before they look at shapes: the route's flag, an eligible 4-D tensor, eval
+    mode, at most MAX_BATCH images, and libmcd_blaslt.so loaded (the 1x1 convolutions are its GEMMs)."""
+    return bool(flag and _eligible(x) and x.dim() == 4 and not module.training and x.shape[0] <= MAX_BATCH
+                and core.linear_residual_available())
+
+
+def _under_2g(*elements):
+    """Every one of these fp32 element counts (one image's tensors) is under 2^31 bytes: the kernels index an image
+    with 32-bit byte offsets."""
+    return all(n * 4 < 2 ** 31 for n in elements)
 
 
 class _LayerNorm(nn.LayerNorm):
@@ -56,10 +84,8 @@ class _LayerNorm(nn.LayerNorm):
 
     def forward(self, x):
         D = x.shape[-1]
-        if (HIP_LAYER_NORM and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and not torch.is_grad_enabled()
-                and len(self.normalized_shape) == 1 and D % 4 == 0 and D <= 2048 and self.weight is not None
-                and self.bias is not None):
-            from .. import core
+        if (HIP_LAYER_NORM and _eligible(x) and x.is_contiguous() and len(self.normalized_shape) == 1 and D % 4 == 0
+                and D <= 2048 and self.weight is not None and self.bias is not None):
             return core.layer_norm(x, self.weight, self.bias, self.eps)
         return super().forward(x)
 
@@ -68,16 +94,12 @@ def _linear(mod, x):
     """mod(x) for an nn.Linear; on the fused path through libmcd_blaslt.so as well (res = None: same hipBLASLt GEMM with
     the bias epilogue as PyTorch's, but with this process's own best-of-32 pick instead of the library default)."""
     if _fused_residual_ok(x) and x.is_contiguous() and mod.bias is not None:
-        from .. import core
         return core.linear_residual(None, x, mod.weight, mod.bias)
     return mod(x)
 
 
 def _fused_residual_ok(x):
-    if not (FUSED_RESIDUAL and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()):
-        return False
-    from .. import core
-    return core.linear_residual_available()
+    return bool(FUSED_RESIDUAL and _eligible(x) and core.linear_residual_available())
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -87,12 +109,11 @@ def attention_route(T, D, heads, masked, on_gpu, dtype, needs_grad):
     """Which attention _Attention.heads_out takes for T tokens of width D = 64 * heads: 'k9' (T <= 256), 'long' (K9L,
     up to core.VIT_ATTENTION_LONG_MAX_T tokens and one image's qkv under 2^31 bytes) or 'sdpa' (masked, autograd,
     non-fp32 or off-GPU calls, HIP_ATTENTION off, other head widths, and anything past K9L's limits)."""
-    from .. import core
-    if not (HIP_ATTENTION and not masked and on_gpu and dtype == torch.float32 and D == 64 * heads and not needs_grad):
+    if not (HIP_ATTENTION and not masked and _hip_eligible(on_gpu, dtype, needs_grad) and D == 64 * heads):
         return "sdpa"
     if T <= core.VIT_ATTENTION_MAX_T:
         return "k9"
-    if T <= core.VIT_ATTENTION_LONG_MAX_T and T * 3 * D * 4 < 2 ** 31:
+    if T <= core.VIT_ATTENTION_LONG_MAX_T and _under_2g(T * 3 * D):
         return "long"
     return "sdpa"
 
@@ -115,7 +136,6 @@ class _Attention(nn.Module):
                                 torch.is_grad_enabled() and qkv.requires_grad)
         if route == "k9":
             # K9 (csrc/k_attn.hip): one launch, reads the fused projection's layout, writes the proj input's
-            from .. import core
             global _attention_calls
             _attention_calls += 1
             if ATTENTION_EVENTS is not None and _attention_calls % 8 == 0:
@@ -128,7 +148,6 @@ class _Attention(nn.Module):
             return core.vit_attention(qkv, self.heads)
         if route == "long":
             # K9L (csrc/k_attn.hip): the same layouts, one workgroup per 256 queries of a head, no T x T buffer
-            from .. import core
             return core.vit_attention_long(qkv, self.heads)
         q, k, v = qkv.view(B, T, 3, self.heads, D // self.heads).permute(2, 0, 3, 1, 4)
         o = F.scaled_dot_product_attention(q, k, v, attn_mask=mask)
@@ -146,7 +165,6 @@ class _Block(nn.Module):
 
     def forward(self, x, mask=None):
         if _fused_residual_ok(x):
-            from .. import core
             x = x.contiguous()
             # x1 is a new tensor (the block's input is left alone); the second update is in place on x1
             x1 = core.linear_residual(x, self.attn.heads_out(self.norm1(x), mask).contiguous(), self.attn.proj.weight,
@@ -215,22 +233,18 @@ class ViTTower(nn.Module):
             # patch pixels (a zero row in every image's class-token slot) times the conv weight, plus the bias, plus a
             # residual operand that holds the position embedding (and cls + pos[0] - bias in the class-token rows).
             # No MIOpen call (its choice of algorithm varied between 0.5 and 1.2 ms from box to box), no cat, no add.
-            from .. import core
-            B = x.shape[0]
-            return core.linear_residual(self._embed_residual(B), core.patchify(x, P),
+            return core.linear_residual(self._embed_residual(x.shape[0]), core.patchify(x, P),
                                         self.patch_embed.weight.view(self.patch_embed.out_channels, -1), self.patch_embed.bias)
         x = self.patch_embed(x).flatten(2).transpose(1, 2)
         return torch.cat([self.cls_token.expand(x.shape[0], -1, -1), x], dim=1) + self.pos_embed
 
     def _embed_residual(self, B):
         """[B, 1 + n, dim]: pos_embed, with cls_token + pos_embed[0] - bias in row 0 (the GEMM adds the bias back)."""
-        key = (B, self.pos_embed._version, self.cls_token._version, self.patch_embed.bias._version, self.pos_embed.device)
-        cache = self.__dict__.setdefault("_embed_res_cache", {})
-        if cache.get("key") != key:
-            r = self.pos_embed.detach().expand(B, -1, -1).contiguous()
-            r[:, 0] = self.cls_token.detach()[0, 0] + self.pos_embed.detach()[0, 0] - self.patch_embed.bias.detach()
-            cache["key"], cache["res"] = key, r
-        return cache["res"]
+        def build(m):
+            r = m.pos_embed.detach().expand(B, -1, -1).contiguous()
+            r[:, 0] = m.cls_token.detach()[0, 0] + m.pos_embed.detach()[0, 0] - m.patch_embed.bias.detach()
+            return r
+        return _folded(self, ("pos_embed", "cls_token", "patch_embed"), build, extra=(B,))
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -241,35 +255,47 @@ class _SameConv(nn.Conv2d):
     """TensorFlow 'SAME' padding (asymmetric for stride 2), as the b5 'tf_' weights expect."""
 
     def forward(self, x):
-        ih, iw = x.shape[-2:]
-        kh, kw = self.kernel_size
-        sh, sw = self.stride
-        ph = max((math.ceil(ih / sh) - 1) * sh + kh - ih, 0)
-        pw = max((math.ceil(iw / sw) - 1) * sw + kw - iw, 0)
-        if ph or pw:
-            x = F.pad(x, [pw // 2, pw - pw // 2, ph // 2, ph - ph // 2])
+        (_, pt, pb), (_, pl, pr) = (core.same_pad(n, k, s) for n, k, s in zip(x.shape[-2:], self.kernel_size, self.stride))
+        if pt or pb or pl or pr:
+            x = F.pad(x, [pl, pr, pt, pb])
         return F.conv2d(x, self.weight, self.bias, self.stride, 0, self.dilation, self.groups)
+
+
+def _bn_affine64(bn):
+    """(scale, shift) in float64 of an eval-mode batch norm as y = x * scale + shift: g / sqrt(var + eps) and
+    beta - mean * scale."""
+    scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+    return scale, bn.bias.detach().double() - bn.running_mean.detach().double() * scale
+
+
+def bn_scale_shift(bn):
+    """(scale, shift) of an eval-mode batch norm as y = x * scale + shift, computed in float64, returned in its dtype."""
+    scale, shift = _bn_affine64(bn)
+    return scale.to(bn.weight.dtype).contiguous(), shift.to(bn.weight.dtype).contiguous()
 
 
 def fold_bn(weight, bn):
     """(W', b'): the eval-mode batch norm `bn` folded into the bias-free convolution weight [Cout, ...] in front of it,
-    W' = W * g / sqrt(var + eps) per output channel, b' = beta - mean * g / sqrt(var + eps).  Computed in float64,
-    returned in the weight's dtype."""
-    scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+    W' = W * scale per output channel, b' = shift (_bn_affine64).  Computed in float64, returned in the weight's dtype."""
+    scale, shift = _bn_affine64(bn)
     w = weight.detach().double() * scale.view(-1, *([1] * (weight.dim() - 1)))
-    b = bn.bias.detach().double() - bn.running_mean.detach().double() * scale
-    return w.to(weight.dtype), b.to(weight.dtype)
+    return w.to(weight.dtype), shift.to(weight.dtype)
 
 
-def _folded(module, names, build, own=False):
-    """build(module) -> dict of folded tensors, computed once and cached in the module's __dict__ (no parameter or buffer
-    is registered: state_dict() and the module tree stay as they are).  The cache is keyed on the version counter and the
-    storage of every tensor of the named submodules (all of their tensors, nested ones included; own=True: of the module
-    itself), and on the device, like ViTTower._embed_residual's."""
-    mods = [module] if own else [getattr(module, n, None) for n in names]
-    srcs = [t for m in mods if m is not None for t in list(m.parameters()) + list(m.buffers())]
-    key = tuple((t._version, t.data_ptr()) for t in srcs) + (srcs[0].device, srcs[0].dtype)
-    cache = module.__dict__.setdefault("_mbconv_fold", {})
+def _folded(module, names, build, own=False, extra=()):
+    """build(module) -> the tensors derived from the module's weights (folded, relaid), computed once and cached in the
+    module's __dict__ (no parameter or buffer is registered: state_dict() and the module tree stay as they are).  The
+    cache is keyed on the version counter and the storage of every source tensor -- the named parameters, and all tensors
+    of the named submodules, nested ones included (own=True: of the module itself) -- on the device and dtype, and on
+    `extra` (whatever else build depends on)."""
+    srcs = []
+    for m in [module] if own else [getattr(module, n, None) for n in names]:
+        if isinstance(m, torch.Tensor):
+            srcs.append(m)
+        elif m is not None:
+            srcs += list(m.parameters()) + list(m.buffers())
+    key = tuple((t._version, t.data_ptr()) for t in srcs) + (srcs[0].device, srcs[0].dtype) + tuple(extra)
+    cache = module.__dict__.setdefault("_fold_cache", {})
     if cache.get("key") != key:
         with torch.no_grad():
             cache["val"] = build(module)
@@ -281,17 +307,18 @@ _MBCONV_SKIPPED = ("_expand_conv", "_bn0", "_depthwise_conv", "_bn1", "_se_reduc
 _TOWER_SKIPPED = ("_conv_stem", "_bn0", "_conv_head", "_bn1")
 
 
+def _hooked(m):
+    """A forward (pre-)hook on the module m or on any module inside it."""
+    return bool(m._forward_hooks or m._forward_pre_hooks
+                or (m._modules and any(_hooked(c) for c in m._modules.values() if c is not None)))
+
+
 def _hooks_on(module, names):
-    """A global module hook, or a forward (pre-)hook on one of the named submodules (which the HIP route does not call)."""
-    from torch.nn.modules import module as M
-    if M._global_forward_hooks or M._global_forward_pre_hooks:
+    """A global module hook, or a forward (pre-)hook on one of the named submodules or on a module inside one (a
+    ResNet downsample's convolution, say): the HIP route calls none of them."""
+    if _nn_module._global_forward_hooks or _nn_module._global_forward_pre_hooks:
         return True
-    return any(m is not None and (m._forward_hooks or m._forward_pre_hooks)
-               for m in (getattr(module, n, None) for n in names))
-
-
-def _same_out(n, s):
-    return -(-n // s)
+    return any(m is not None and _hooked(m) for m in (getattr(module, n, None) for n in names))
 
 
 def mbconv_route(module, x):
@@ -301,33 +328,27 @@ def mbconv_route(module, x):
     anything), one image's tensors under 2^31 bytes, and no hook on a submodule the route does not call (--target_layers
     may name any module path: a hook on _blocks[5]._depthwise_conv must fire, so that block takes ATen).  'aten'
     otherwise."""
-    if not (HIP_MBCONV and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-            and not torch.is_grad_enabled() and not module.training and x.shape[0] <= 65535):
-        return "aten"
-    from .. import core
-    if not core.linear_residual_available():
+    if not _tower_gate(HIP_MBCONV, module, x):
         return "aten"
     B, C, H, W = x.shape
     if isinstance(module, _MBConv):
-        if (C != module.cin or module.cin % 4 or module.mid % 4 or module.cout % 4 or module.k not in (3, 5)
-                or module.s not in (1, 2) or not x.is_contiguous(memory_format=torch.channels_last)
-                or x.data_ptr() % 16 or module.mid * H * W * 4 >= 2 ** 31 or module.cin * H * W * 4 >= 2 ** 31):
-            return "aten"
+        ok = (C == module.cin and not (module.cin % 4 or module.mid % 4 or module.cout % 4) and module.k in (3, 5)
+              and module.s in (1, 2) and core.channels_last(x) and not x.data_ptr() % 16
+              and _under_2g(module.mid * H * W, module.cin * H * W))
         names = _MBCONV_SKIPPED
     elif isinstance(module, EfficientNetB5Tower):
         stem, head = module._conv_stem, module._conv_head
-        h, w = H, W
-        for _ in range(5):                           # the five stride-2 stages: the head's input size
-            h, w = _same_out(h, 2), _same_out(w, 2)
-        if (C != stem.in_channels or C > 4 or stem.out_channels % 4 or stem.kernel_size != (3, 3)
-                or stem.stride != (2, 2) or head.in_channels % 4 or head.out_channels % 4 or not x.is_contiguous()
-                or stem.out_channels * _same_out(H, 2) * _same_out(W, 2) * 4 >= 2 ** 31
-                or head.out_channels * h * w * 4 >= 2 ** 31):
-            return "aten"
+        sizes = [(H, W)]
+        for _ in range(5):                           # the five stride-2 stages (the output size does not depend on k)
+            sizes.append(tuple(core.same_pad(n, 3, 2)[0] for n in sizes[-1]))
+        (hs, ws), (hh, wh) = sizes[1], sizes[5]      # the stem's output and the head's input
+        ok = (C == stem.in_channels and C <= 4 and not stem.out_channels % 4 and stem.kernel_size == (3, 3)
+              and stem.stride == (2, 2) and not (head.in_channels % 4 or head.out_channels % 4) and x.is_contiguous()
+              and _under_2g(stem.out_channels * hs * ws, head.out_channels * hh * wh))
         names = _TOWER_SKIPPED
     else:
         return "aten"
-    return "aten" if _hooks_on(module, names) else "hip"
+    return "hip" if ok and not _hooks_on(module, names) else "aten"
 
 
 class _MBConv(nn.Module):
@@ -364,7 +385,6 @@ class _MBConv(nn.Module):
         output on the way in, depthwise + folded BN1 + SiLU, SE partial sums), K14 (SE gate), K15 (scale, in place),
         project GEMM (folded BN2 as its bias, the skip as its residual operand: a new tensor, x is left alone).
         Returns [B, C, H, W] in channels_last memory, the reference's logical shape."""
-        from .. import core
         f = _folded(self, _MBCONV_SKIPPED, _MBConv._fold)
         xn = x.permute(0, 2, 3, 1)                                   # [B, H, W, cin], contiguous
         h = core.linear_residual(None, xn, f["w0"], f["b0"]) if self.expand else xn
@@ -434,7 +454,6 @@ class EfficientNetB5Tower(nn.Module):
     def _forward_hip(self, x):
         """Stem by K12 (NCHW image -> channels-last), the blocks called as modules (hooks on _blocks[i] fire; each block
         picks its own route), the head as one GEMM (folded BN1 as its bias) and K0n's mean of SiLU."""
-        from .. import core
         f = _folded(self, _TOWER_SKIPPED, EfficientNetB5Tower._fold)
         x = core.conv_stem_nhwc(x, f["ws"], f["bs"]).permute(0, 3, 1, 2)
         for b in self._blocks:
@@ -584,10 +603,6 @@ _BOTTLENECK_SKIPPED = ("conv1", "bn1", "conv2", "bn2", "conv3", "bn3", "downsamp
 _RESNET_SKIPPED = ("bn1",)
 
 
-def _conv_out(n, k, s, p):
-    return (n + 2 * p - k) // s + 1
-
-
 def resnet_route(module, x):
     """'hip' when the ResNet-50 target (a ResNet50 or its stem convolution, with the NCHW-contiguous input image) or one
     of its blocks (a _Bottleneck with a channels_last-contiguous input) can take the HIP route: HIP_RESNET on, a CUDA fp32
@@ -596,42 +611,32 @@ def resnet_route(module, x):
     bytes, at most 65535 images, and no hook on a submodule the route does not call (a hook on layer2[0].conv2 must fire,
     so that block takes ATen; the hook points of the tower itself -- conv1 and layer1..4 -- are called as modules on
     either route).  'aten' otherwise."""
-    if not (HIP_RESNET and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
-            and not torch.is_grad_enabled() and not module.training and x.shape[0] <= 65535):
-        return "aten"
-    from .. import core
-    if not core.linear_residual_available():
+    if not _tower_gate(HIP_RESNET, module, x):
         return "aten"
     B, C, H, W = x.shape
     if H < 1 or W < 1:
         return "aten"
     if isinstance(module, _Bottleneck):
         cin, width, cout, s = module.conv1.in_channels, module.conv2.in_channels, module.conv3.out_channels, module.stride
-        ho, wo = _conv_out(H, 3, s, 1), _conv_out(W, 3, s, 1)
-        if (C != cin or cin % 32 or width % 32 or cout % 32 or s not in (1, 2)
-                or not x.is_contiguous(memory_format=torch.channels_last) or x.data_ptr() % 16
-                or max(cin, width) * H * W * 4 >= 2 ** 31 or cout * ho * wo * 4 >= 2 ** 31
-                or 9 * width * width * 4 >= 2 ** 31):
-            return "aten"
-        names = _BOTTLENECK_SKIPPED
-        if module.downsample is not None and _hooks_on(module.downsample, ("0", "1")):
-            return "aten"
+        ok = (C == cin and not (cin % 32 or width % 32 or cout % 32) and s in (1, 2) and core.channels_last(x)
+              and not x.data_ptr() % 16
+              and _under_2g(max(cin, width) * H * W, cout * core.conv_out(H, 3, s, 1) * core.conv_out(W, 3, s, 1),
+                            9 * width * width))
+        names = _BOTTLENECK_SKIPPED                     # "downsample" covers the convolution and the batch norm in it
     elif isinstance(module, (ResNet50, _StemConv)):
         stem = module.conv1 if isinstance(module, ResNet50) else module
-        ho, wo = _conv_out(H, 7, 2, 3), _conv_out(W, 7, 2, 3)
-        if (C != stem.in_channels or C > 4 or stem.out_channels % 4 or stem.kernel_size != (7, 7)
-                or stem.stride != (2, 2) or stem.padding != (3, 3) or stem.dilation != (1, 1) or stem.groups != 1
-                or stem.bias is not None or not x.is_contiguous() or x.data_ptr() % 16
-                or C * H * W * 4 >= 2 ** 31 or stem.out_channels * ho * wo * 4 >= 2 ** 31):
-            return "aten"
+        ho, wo = core.conv_out(H, 7, 2, 3), core.conv_out(W, 7, 2, 3)
+        ok = (C == stem.in_channels and C <= 4 and not stem.out_channels % 4 and stem.kernel_size == (7, 7)
+              and stem.stride == (2, 2) and stem.padding == (3, 3) and stem.dilation == (1, 1) and stem.groups == 1
+              and stem.bias is None and x.is_contiguous() and not x.data_ptr() % 16
+              and _under_2g(C * H * W, stem.out_channels * ho * wo))
         if isinstance(module, _StemConv):
-            return "hip"                                # nothing inside it is skipped; its own hooks fire
-        if ho < 1 or wo < 1 or not isinstance(stem, _StemConv):
-            return "aten"
+            return "hip" if ok else "aten"              # nothing inside it is skipped; its own hooks fire
+        ok = ok and ho >= 1 and wo >= 1 and isinstance(stem, _StemConv)
         names = _RESNET_SKIPPED
     else:
         return "aten"
-    return "aten" if _hooks_on(module, names) else "hip"
+    return "hip" if ok and not _hooks_on(module, names) else "aten"
 
 
 class _StemConv(nn.Conv2d):
@@ -640,7 +645,6 @@ class _StemConv(nn.Conv2d):
 
     def forward(self, x):
         if resnet_route(self, x) == "hip":
-            from .. import core
             w = _folded(self, (), lambda m: m.weight.detach().permute(1, 2, 3, 0).contiguous(), own=True)   # tap-major
             return core.conv7x7s2_nhwc(x, w).permute(0, 3, 1, 2)
         return super().forward(x)
@@ -674,7 +678,6 @@ class _Bottleneck(nn.Module):
         relu_in), conv2 by K18 (3x3, folded bn2, ReLU on the way in and out), the downsample as a GEMM (stride 1) or
         K18 1x1 / 2 (stride 2) with folded BN, conv3 as one GEMM with folded bn3 as its bias, the skip as its residual
         operand and the ReLU as its epilogue.  Returns [B, C, H, W] in channels_last memory."""
-        from .. import core
         f = _folded(self, _BOTTLENECK_SKIPPED, _Bottleneck._fold)
         xn = x.permute(0, 2, 3, 1)                                   # [B, H, W, cin], contiguous
         h = core.linear_residual(None, xn, f["w1"], f["b1"])
@@ -706,20 +709,13 @@ def igemm_weight(w):
     return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
 
 
-def bn_scale_shift(bn):
-    """(scale, shift) of an eval-mode batch norm as y = x * scale + shift, computed in float64 like fold_bn."""
-    scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
-    shift = bn.bias.detach().double() - bn.running_mean.detach().double() * scale
-    return scale.to(bn.weight.dtype).contiguous(), shift.to(bn.weight.dtype).contiguous()
-
-
 class _Stage(nn.Sequential):
     """layer1..4: a Sequential that keeps handing on channels-last memory when it was given channels-last memory (a
     block that took ATen, for a hook inside it, say, may hand back NCHW memory, which the next block's HIP route
     refuses).  On NCHW input it is a plain Sequential."""
 
     def forward(self, x):
-        keep = x.dim() == 4 and not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last)
+        keep = core.channels_last(x, only=True)
         for b in self:
             x = b(x)
             if keep:
@@ -752,7 +748,6 @@ class ResNet50(nn.Module):
         """conv1 called as a module (K16 inside; a hook on it fires on the raw output), bn1 + ReLU + max pooling by K17,
         layer1..4 called as modules (hooks on them fire; each block picks its own route), the mean over the pixels by
         K0n, fc."""
-        from .. import core
         scale, shift = _folded(self, _RESNET_SKIPPED, lambda m: bn_scale_shift(m.bn1))
         x = self.conv1(x).contiguous(memory_format=torch.channels_last)     # a no-op copy on the HIP route
         x = core.bn_relu_maxpool_nhwc(x.permute(0, 2, 3, 1), scale, shift).permute(0, 3, 1, 2)

@@ -83,6 +83,26 @@ def _ld(t):
     return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
 
 
+def _nchw_image(x, message):
+    """x must be a contiguous fp32 NCHW image batch on the GPU; TypeError(message) otherwise."""
+    _need_gpu(x)
+    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
+        raise TypeError(message)
+    return x
+
+
+def _aligned16(message, *tensors):
+    """The kernels read these with 16-byte vector loads; ValueError(message) if one of them cannot be."""
+    if any(t.data_ptr() % 16 for t in tensors):
+        raise ValueError(message)
+
+
+def channels_last(x, only=False):
+    """x is a 4-D tensor whose memory is channels-last contiguous.  only=True: and not NCHW-contiguous as well (one
+    channel, or one pixel, is both), i.e. the layout has to be handled as channels-last."""
+    return x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) and not (only and x.is_contiguous())
+
+
 def sum_split(C):
     """ATen torch.sum(dim=0) CPU rule: columns below use the cascade order, the rest row_sum."""
     return (C // 32) * 32 if C >= 8 else (C // 4) * 4
@@ -390,10 +410,8 @@ def rank_reorder(P, tvals, tidx, perms, p=3, scale_p=0.5, out=None):
 VIT_ATTENTION_MAX_T = 256
 
 
-@_on_device
-def vit_attention(qkv, heads, out=None):
-    """softmax(q k^T / 8) v per head for the ViT tower: qkv [B, T, 3*heads*64] (the fused projection's output,
-    q | k | v along the last axis, heads inside each) -> [B, T, heads*64].  fp32, head dimension 64, T <= 256."""
+def _attention(entry, qkv, heads, out):
+    """The argument checks and the output of K9 and K9L, then the library entry `entry`."""
     _need_gpu(qkv)
     if qkv.dtype != torch.float32 or qkv.dim() != 3 or not qkv.is_contiguous():
         raise TypeError("qkv must be a contiguous float32 [B, T, 3*heads*64] tensor")
@@ -404,9 +422,15 @@ def vit_attention(qkv, heads, out=None):
         out = torch.empty((B, T, heads * 64), dtype=torch.float32, device=qkv.device)
     elif out.dtype != torch.float32 or tuple(out.shape) != (B, T, heads * 64) or not out.is_contiguous():
         raise TypeError("out must be a contiguous float32 [B, T, heads*64] tensor")
-    L = _lib.load()
-    check(L.mcd_vit_attention(qkv.data_ptr(), B, T, heads, out.data_ptr(), _stream()))
+    check(getattr(_lib.load(), entry)(qkv.data_ptr(), B, T, heads, out.data_ptr(), _stream()))
     return out
+
+
+@_on_device
+def vit_attention(qkv, heads, out=None):
+    """softmax(q k^T / 8) v per head for the ViT tower: qkv [B, T, 3*heads*64] (the fused projection's output,
+    q | k | v along the last axis, heads inside each) -> [B, T, heads*64].  fp32, head dimension 64, T <= 256."""
+    return _attention("mcd_vit_attention", qkv, heads, out)
 
 
 VIT_ATTENTION_LONG_MAX_T = 32768
@@ -417,19 +441,7 @@ def vit_attention_long(qkv, heads, out=None):
     """vit_attention for any T from 1 to VIT_ATTENTION_LONG_MAX_T (K9L): the same layout and arithmetic, one workgroup
     per 256 queries of a head; for T <= 256 the same bits as vit_attention.  Allocates only the [B, T, heads*64] output
     (no T x T scores)."""
-    _need_gpu(qkv)
-    if qkv.dtype != torch.float32 or qkv.dim() != 3 or not qkv.is_contiguous():
-        raise TypeError("qkv must be a contiguous float32 [B, T, 3*heads*64] tensor")
-    B, T, W = qkv.shape
-    if W != 3 * heads * 64:
-        raise ValueError("qkv last dimension %d is not 3 * %d heads * 64" % (W, heads))
-    if out is None:
-        out = torch.empty((B, T, heads * 64), dtype=torch.float32, device=qkv.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, T, heads * 64) or not out.is_contiguous():
-        raise TypeError("out must be a contiguous float32 [B, T, heads*64] tensor")
-    L = _lib.load()
-    check(L.mcd_vit_attention_long(qkv.data_ptr(), B, T, heads, out.data_ptr(), _stream()))
-    return out
+    return _attention("mcd_vit_attention_long", qkv, heads, out)
 
 
 # ---- K10 -----------------------------------------------------------------------------------------
@@ -452,10 +464,7 @@ def layer_norm(x, weight, bias, eps):
 def patchify(x, patch):
     """[B, Cin, H, W] -> [B, 1 + (H/patch)(W/patch), Cin*patch*patch]: row 0 of every image zero (class-token slot),
     then the patches in (c, dy, dx) order -- the operand of the patch embedding written as a GEMM."""
-    _need_gpu(x)
-    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
-        raise TypeError("patchify: contiguous float32 [B, Cin, H, W]")
-    B, Cin, H, W = x.shape
+    B, Cin, H, W = _nchw_image(x, "patchify: contiguous float32 [B, Cin, H, W]").shape
     if H % patch or W % patch:
         raise ValueError("patchify: %dx%d is not a multiple of the %d-pixel patch" % (H, W, patch))
     out = torch.empty((B, 1 + (H // patch) * (W // patch), Cin * patch * patch), dtype=torch.float32, device=x.device)
@@ -498,14 +507,11 @@ def dwconv_tiles(Ho, Wo):
 def conv_stem_nhwc(x, w_tap, bias):
     """K12: SiLU(conv3x3/2(x) + bias) with TF-SAME padding: x NCHW [B, Cin, H, W] (Cin <= 4), w_tap [Cin, 3, 3, Cout]
     (the folded weight, tap-major) -> NHWC [B, ceil(H/2), ceil(W/2), Cout]."""
-    _need_gpu(x)
-    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
-        raise TypeError("conv_stem_nhwc: x must be a contiguous float32 [B, Cin, H, W] tensor")
-    B, Cin, H, W = x.shape
+    B, Cin, H, W = _nchw_image(x, "conv_stem_nhwc: x must be a contiguous float32 [B, Cin, H, W] tensor").shape
     Cout = w_tap.shape[-1]
     _vec(w_tap, Cin * 9 * Cout, "w_tap")
     _vec(bias, Cout, "bias")
-    y = torch.empty((B, -(-H // 2), -(-W // 2), Cout), dtype=torch.float32, device=x.device)
+    y = torch.empty((B, same_pad(H, 3, 2)[0], same_pad(W, 3, 2)[0], Cout), dtype=torch.float32, device=x.device)
     L = _lib.load()
     check(L.mcd_conv_stem_nhwc(x.data_ptr(), B, Cin, H, W, w_tap.data_ptr(), bias.data_ptr(), Cout, y.data_ptr(), _stream()))
     return y
@@ -520,7 +526,7 @@ def dwconv_bn_silu(x, w_tap, bias, k, stride, silu_in):
     B, H, W, C = x.shape
     _vec(w_tap, k * k * C, "w_tap")
     _vec(bias, C, "bias")
-    Ho, Wo = -(-H // stride), -(-W // stride)
+    Ho, Wo = same_pad(H, k, stride)[0], same_pad(W, k, stride)[0]
     T = dwconv_tiles(Ho, Wo)
     y = torch.empty((B, Ho, Wo, C), dtype=torch.float32, device=x.device)
     psum = torch.empty((B, T, C), dtype=torch.float32, device=x.device)
@@ -584,10 +590,7 @@ def conv_out(n, k, s, p):
 def conv7x7s2_nhwc(x, w_tap):
     """K16: the raw stem convolution conv7x7/2, pad 3 (no bias, no batch norm, no ReLU): x NCHW [B, Cin, H, W]
     (Cin <= 4), w_tap [Cin, 7, 7, Cout] (tap-major, Cout % 4 == 0) -> NHWC [B, Ho, Wo, Cout]."""
-    _need_gpu(x)
-    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
-        raise TypeError("conv7x7s2_nhwc: x must be a contiguous float32 [B, Cin, H, W] tensor")
-    B, Cin, H, W = x.shape
+    B, Cin, H, W = _nchw_image(x, "conv7x7s2_nhwc: x must be a contiguous float32 [B, Cin, H, W] tensor").shape
     if w_tap.dim() != 4 or tuple(w_tap.shape[:3]) != (Cin, 7, 7) or Cin > 4 or w_tap.shape[3] % 4:
         raise ValueError("conv7x7s2_nhwc: w_tap must be [Cin, 7, 7, Cout] with Cin = %d <= 4 and Cout %% 4 == 0, got %s"
                          % (Cin, tuple(w_tap.shape)))
@@ -595,8 +598,7 @@ def conv7x7s2_nhwc(x, w_tap):
         raise ValueError("conv7x7s2_nhwc: empty image")
     Cout = w_tap.shape[3]
     _vec(w_tap, Cin * 49 * Cout, "w_tap")
-    if w_tap.data_ptr() % 16:
-        raise ValueError("conv7x7s2_nhwc: w_tap must be 16-byte aligned")
+    _aligned16("conv7x7s2_nhwc: w_tap must be 16-byte aligned", w_tap)
     y = torch.empty((B, conv_out(H, 7, 2, 3), conv_out(W, 7, 2, 3), Cout), dtype=torch.float32, device=x.device)
     L = _lib.load()
     check(L.mcd_conv7x7s2_nhwc(x.data_ptr(), B, Cin, H, W, w_tap.data_ptr(), Cout, y.data_ptr(), _stream()))
@@ -613,8 +615,7 @@ def bn_relu_maxpool_nhwc(x, scale, shift):
         raise ValueError("bn_relu_maxpool_nhwc: C = %d must be a multiple of 4 and the image non-empty" % C)
     _vec(scale, C, "scale")
     _vec(shift, C, "shift")
-    if x.data_ptr() % 16 or scale.data_ptr() % 16 or shift.data_ptr() % 16:
-        raise ValueError("bn_relu_maxpool_nhwc: tensors must be 16-byte aligned")
+    _aligned16("bn_relu_maxpool_nhwc: tensors must be 16-byte aligned", x, scale, shift)
     y = torch.empty((B, conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1), C), dtype=torch.float32, device=x.device)
     L = _lib.load()
     check(L.mcd_bn_relu_maxpool_nhwc(x.data_ptr(), B, H, W, C, scale.data_ptr(), shift.data_ptr(), y.data_ptr(), _stream()))
@@ -638,8 +639,7 @@ def conv_igemm_nhwc(x, w_tap, bias, k, stride, relu_in=False, relu_out=False):
                          % (Cin, Cout))
     _vec(w_tap, Cout * k * k * Cin, "w_tap")
     _vec(bias, Cout, "bias")
-    if x.data_ptr() % 16 or w_tap.data_ptr() % 16 or bias.data_ptr() % 16:
-        raise ValueError("conv_igemm_nhwc: tensors must be 16-byte aligned")
+    _aligned16("conv_igemm_nhwc: tensors must be 16-byte aligned", x, w_tap, bias)
     pad = 1 if k == 3 else 0
     y = torch.empty((B, conv_out(H, k, stride, pad), conv_out(W, k, stride, pad), Cout), dtype=torch.float32,
                     device=x.device)
@@ -738,8 +738,7 @@ def hook_pool(x, mode, dst, row0, col0, neuron_major):
         x = x.float()
     # a channels-last 4-D output (the B5 tower's HIP route) is pooled where it lies by K0n: the same bits as K0 on the
     # NCHW-contiguous copy, without the copy
-    nhwc = x.dim() == 4 and mode in ("avg", "max") and not x.is_contiguous() \
-        and x.is_contiguous(memory_format=torch.channels_last)
+    nhwc = mode in ("avg", "max") and channels_last(x, only=True)
     if not nhwc:
         x = x.contiguous()
     if x.dim() == 4:

@@ -11,14 +11,12 @@
 import glob
 import io
 import os
-import socket
 import sys
 
 import numpy as np
 import pandas as pd
 import pytest
 import torch
-import torch.multiprocessing as mp
 
 import util
 
@@ -30,10 +28,6 @@ CONCEPTS = os.path.join(ROOT, "mammo-clip-dissect_amd", "Concepts", "Specific_co
 def _words():
     with open(CONCEPTS) as f:
         return f.read().split("\n")
-
-
-def _free_port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
 
 # ---- (a) CSV bytes -------------------------------------------------------------------------------------
@@ -68,17 +62,6 @@ def _shared2_csvs(world, rank):
     return out
 
 
-def _csv_worker(rank, world, port, q):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    out = _shared2_csvs(world, rank)
-    if rank == 0:
-        q.put(out)
-    dist.barrier()
-    dist.destroy_process_group()
-
-
 def _diff_report(got, want):
     g, w = got.splitlines(), want.splitlines()
     bad = [i for i, (a, b) in enumerate(zip(g, w)) if a != b]
@@ -94,16 +77,7 @@ def test_hip_csv_bytes_equal_reference_csv(world):
     if world == 1:
         out = _shared2_csvs(1, 0)
     else:
-        ctx = mp.get_context("spawn")
-        q = ctx.Queue()
-        port = _free_port()
-        procs = [ctx.Process(target=_csv_worker, args=(r, world, port, q)) for r in range(world)]
-        for p in procs:
-            p.start()
-        out = q.get(timeout=600)
-        for p in procs:
-            p.join(timeout=120)
-            assert p.exitcode == 0
+        out = util.run_ranks(world, _shared2_csvs, timeout=600)[0]
     zm, z2 = util.golden("main"), util.golden("shared2")
     ref_sim = np.concatenate([zm["soft_wpmi"], z2["soft_wpmi1"]])
     d = np.abs(out["sim"].astype(np.float64) - ref_sim)

@@ -4,13 +4,14 @@ invariance, one block of every stage and the whole tower against a float64 CPU f
 multi-rank form through the new route."""
 import glob
 import os
-import socket
 import sys
 
 import pytest
 import torch
-import torch.multiprocessing as mp
 import torch.nn.functional as F
+
+import util
+from util import mild_bn as _mild_bn, nerr as _nerr
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,13 +28,6 @@ def core(mcd):
 def du(mcd):
     from mammo_clip_dissect_amd.concept_vit import data_utils
     return data_utils
-
-
-def _nerr(got, ref):
-    """max |got - ref| / max |ref| in float64."""
-    got = got.detach().double().cpu()
-    ref = ref.detach().double().cpu()
-    return float((got - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
 
 
 def _dw_ref(x64, w_tap, bias, k, s, silu_in):
@@ -176,29 +170,7 @@ def test_k0n_silu_avg_against_float64(core, dev):
 
 
 # ---- blocks and the tower ---------------------------------------------------------------------------------------------
-def _mild_bn(mod, seed):
-    """Random BN statistics, gamma and beta that keep 39 blocks' activations in range (the defaults hide folding errors)."""
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for m in mod.modules():
-            if isinstance(m, torch.nn.BatchNorm2d):
-                n = m.num_features
-                m.running_mean.copy_(torch.randn(n, generator=g) * 0.1)
-                m.running_var.copy_(torch.rand(n, generator=g) + 0.5)
-                m.weight.copy_(1 + 0.2 * torch.randn(n, generator=g))
-                m.bias.copy_(0.1 * torch.randn(n, generator=g))
-
-
-class _Counter:
-    def __init__(self, core, monkeypatch):
-        self.n = {}
-        for name in ("conv_stem_nhwc", "dwconv_bn_silu", "se_gate", "channel_scale_", "silu_avg_pool_nhwc"):
-            fn = getattr(core, name)
-
-            def wrap(*a, _fn=fn, _name=name, **kw):
-                self.n[_name] = self.n.get(_name, 0) + 1
-                return _fn(*a, **kw)
-            monkeypatch.setattr(core, name, wrap)
+B5_WRAPPERS = ("conv_stem_nhwc", "dwconv_bn_silu", "se_gate", "channel_scale_", "silu_avg_pool_nhwc")
 
 
 def _block_cases(du):
@@ -233,7 +205,7 @@ def test_blocks_against_float64(du, core, dev, monkeypatch, size):
     for h in hs:
         h.remove()
     tower.to(dev)
-    cnt = _Counter(core, monkeypatch)
+    cnt = util.CallCounter(core, monkeypatch, B5_WRAPPERS)
     for i, first in cases:
         blk = tower._blocks[i]
         C, H, W = sizes[i]
@@ -279,7 +251,7 @@ def test_tower_against_float64(du, core, dev, monkeypatch, size):
     monkeypatch.setattr(du, "HIP_MBCONV", False)
     aten, aten_outs = hooked(tower, x.to(dev))
     monkeypatch.setattr(du, "HIP_MBCONV", True)
-    cnt = _Counter(core, monkeypatch)
+    cnt = util.CallCounter(core, monkeypatch, B5_WRAPPERS)
     xg = x.to(dev)
     got, got_outs = hooked(tower, xg)
     assert cnt.n == {"conv_stem_nhwc": 1, "dwconv_bn_silu": 39, "se_gate": 39, "channel_scale_": 39,
@@ -319,7 +291,7 @@ def _run_b5_driver(dev, tmp, tag, n=160, batch=40):
 
 def test_driver_b5_all_blocks_through_the_route(du, core, dev, oracle, tmp_path, monkeypatch):
     import test_gpu_pipeline as tp
-    cnt = _Counter(core, monkeypatch)
+    cnt = util.CallCounter(core, monkeypatch, B5_WRAPPERS)
     layers, act, csv = _run_b5_driver(dev, str(tmp_path), "hip")
     assert cnt.n.get("dwconv_bn_silu", 0) >= 39 * 4 and cnt.n.get("conv_stem_nhwc", 0) >= 4
     words = open(CONCEPTS).read().split("\n")
@@ -339,15 +311,10 @@ def test_driver_b5_all_blocks_through_the_route(du, core, dev, oracle, tmp_path,
         assert _nerr(ta, tb) < 1e-4, (os.path.basename(a), _nerr(ta, tb))
 
 
-def _free_port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
-
-
 def _b5_driver_csv(world, rank, tmp, n_images, batch):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import mammo_clip_dissect_amd  # noqa: F401
-    import util
     from mammo_clip_dissect_amd.concept_vit import data_utils, describe_broad_neurons, utils
     from mammo_clip_dissect_amd.pipeline import shard_bounds
     dev = torch.device("cuda:0")
@@ -366,17 +333,6 @@ def _b5_driver_csv(world, rank, tmp, n_images, batch):
     return out
 
 
-def _b5_worker(rank, world, port, tmp, n_images, batch, q):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    os.environ["WORLD_SIZE"] = str(world); os.environ["RANK"] = str(rank); os.environ["LOCAL_RANK"] = "0"
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    out = _b5_driver_csv(world, rank, tmp, n_images, batch)
-    q.put((rank, out))
-    dist.barrier()
-    dist.destroy_process_group()
-
-
 def test_b5_driver_csv_bytes_one_vs_two_ranks(mcd, tmp_path, monkeypatch):
     """The whole B5 job through the HIP route at 1 rank and at 2 ranks (equal batch shapes, the heuristic hipBLASLt pick):
     rank 0's CSV is the same bytes -- an image's activations do not depend on which rank or batch encodes it."""
@@ -384,15 +340,6 @@ def test_b5_driver_csv_bytes_one_vs_two_ranks(mcd, tmp_path, monkeypatch):
     tmp = str(tmp_path)
     csv = {}
     for world in (1, 2):        # fresh processes: this one may keep timed GEMM picks for these shapes from other tests
-        ctx = mp.get_context("spawn")
-        q = ctx.Queue()
-        port = _free_port()
-        procs = [ctx.Process(target=_b5_worker, args=(r, world, port, tmp, 160, 40, q)) for r in range(world)]
-        for p in procs:
-            p.start()
-        got = dict(q.get(timeout=900) for _ in range(world))
-        for p in procs:
-            p.join(timeout=120)
-            assert p.exitcode == 0
+        got = util.run_ranks(world, _b5_driver_csv, (tmp, 160, 40), timeout=900, env=util.TORCHRUN_ENV)
         csv[world] = open(glob.glob(os.path.join(got[0], "*.csv"))[0], "rb").read()
     assert csv[1] == csv[2] and len(csv[1]) > 10000

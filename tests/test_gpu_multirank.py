@@ -5,21 +5,17 @@ ranks on one device, so the ranks rendezvous over gloo and the TEST injects a ho
 import glob
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
+
+import util
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
 
 def _problem(N, widths, C, D, seed):
@@ -31,7 +27,6 @@ def _run(world, rank, N, widths, C, D, K, seed, gemm_mode="f32"):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import mammo_clip_dissect_amd  # noqa: F401
-    import util
     from mammo_clip_dissect_amd.pipeline import Dissector, shard_bounds
     dev = torch.device("cuda:0")
     At, E_img, E_txt = _problem(N, widths, C, D, seed)
@@ -47,16 +42,6 @@ def _run(world, rank, N, widths, C, D, K, seed, gemm_mode="f32"):
     return [t.cpu().numpy() for t in (r.sim, r.vals, r.ids, r.top_ids, r.top_vals)]
 
 
-def _worker(rank, world, port, case, q):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    out = _run(world, rank, *case)
-    q.put((rank, out))
-    dist.barrier()
-    dist.destroy_process_group()
-
-
 @pytest.mark.parametrize("world,case", [(2, (1200, [96, 40, 7], 763, 512, 100, 21)), (3, (900, [64, 130], 763, 512, 100, 22)),
                                         (3, (1001, [64, 33], 763, 512, 100, 23)),    # 334 + 334 + 333 images
                                         (4, (250, [40], 763, 512, 100, 24)),         # 63+63+62+62: every shard < top_k
@@ -66,16 +51,7 @@ def _worker(rank, world, port, case, q):
                                         (3, (1001, [64, 33], 1500, 512, 100, 25, "bf16"))])
 def test_ranks_on_hip_bit_identical_to_one(world, case):
     single = _run(1, 0, *case)
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, case, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = dict(q.get(timeout=600) for _ in range(world))
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    got = util.run_ranks(world, _run, case, timeout=600)
     for r in range(world):
         for a, b in zip(single, got[r]):
             assert np.array_equal(a, b)
@@ -86,7 +62,7 @@ def test_bench_two_ranks_protocol():
     whole-job value = images of both ranks / max-over-ranks time."""
     env = dict(os.environ, MCD_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
+           "--master-port", str(util.free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
            "--images", "500", "--batch", "250", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -147,7 +123,7 @@ def test_bench_strong_scaling_uneven_shards():
     (334 + 334 + 333), through the drop-in driver."""
     env = dict(os.environ, MCD_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "1", "--warmup", "0",
+           "--master-port", str(util.free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "1", "--warmup", "0",
            "--global-images", "1001", "--batch", "167", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -162,7 +138,6 @@ def _driver_csv(world, rank, tmp, n_images, batch):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import mammo_clip_dissect_amd  # noqa: F401
-    import util
     from mammo_clip_dissect_amd.concept_vit import data_utils, describe_broad_neurons, utils
     from mammo_clip_dissect_amd.pipeline import shard_bounds
     dev = torch.device("cuda:0")
@@ -182,17 +157,6 @@ def _driver_csv(world, rank, tmp, n_images, batch):
     return out
 
 
-def _driver_worker(rank, world, port, tmp, n_images, batch, q):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    os.environ["WORLD_SIZE"] = str(world); os.environ["RANK"] = str(rank); os.environ["LOCAL_RANK"] = "0"
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    out = _driver_csv(world, rank, tmp, n_images, batch)
-    q.put((rank, out))
-    dist.barrier()
-    dist.destroy_process_group()
-
-
 def test_driver_encoder_to_csv_bytes_one_vs_two_ranks(tmp_path, monkeypatch):
     """The WHOLE job -- encoder forwards included -- at 1 rank and at 2 ranks: the CSV rank 0 writes must be the same
     bytes.  The encoder GEMMs run through hipBLASLt, whose algorithm this build normally picks by timing (per process);
@@ -202,16 +166,7 @@ def test_driver_encoder_to_csv_bytes_one_vs_two_ranks(tmp_path, monkeypatch):
     tmp = str(tmp_path)
     one = _driver_csv(1, 0, tmp, 200, 50)
     csv1 = open(glob.glob(os.path.join(one, "*.csv"))[0], "rb").read()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_driver_worker, args=(r, 2, port, tmp, 200, 50, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = dict(q.get(timeout=900) for _ in range(2))
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    got = util.run_ranks(2, _driver_csv, (tmp, 200, 50), timeout=900, env=util.TORCHRUN_ENV)
     csv2 = open(glob.glob(os.path.join(got[0], "*.csv"))[0], "rb").read()
     assert csv1 == csv2 and len(csv1) > 100000
 
@@ -241,20 +196,18 @@ assert obj[0] == {"qkv": 3, "fc1": 17}
 torch.cuda.synchronize()
 dist.destroy_process_group()
 print("rccl ok")
-""" % _free_port()
+""" % util.free_port()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "rccl ok" in r.stdout, r.stderr[-2000:]
 
 
-def _fuzz_worker(rank, world, port, n_cases, seed, q):
+def _fuzz(world, rank, n_cases, seed):
+    """The list of failing cases on rank 0 (None on the others)."""
     import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import mammo_clip_dissect_amd  # noqa: F401
-    import util
     from mammo_clip_dissect_amd.pipeline import Dissector, shard_bounds
     dev = torch.device("cuda:0")
     groups = {g: dist.new_group(list(range(g))) for g in range(1, world + 1)}
@@ -286,26 +239,13 @@ def _fuzz_worker(rank, world, port, n_cases, seed, q):
             single = run(1, 0, *case)
             if not all(torch.equal(a, b) for a, b in zip(single, out)):
                 bad.append((g,) + case)
-    if rank == 0:
-        q.put(bad)
-    dist.barrier()
-    dist.destroy_process_group()
+    return bad if rank == 0 else None
 
 
 def test_ranks_on_hip_fuzz():
     """Random probe-set sizes, 2..4 ranks (sub-groups of one 4-process world sharing the GPU), layer widths, concept counts,
     top_k, fp32 and bf16 chains: the sharded HIP result equals the one-rank HIP result bit for bit."""
-    world = 4
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_fuzz_worker, args=(r, world, port, 16, 9, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    bad = q.get(timeout=900)
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    bad = util.run_ranks(4, _fuzz, (16, 9), timeout=900)[0]
     assert bad == []
 
 
@@ -319,16 +259,7 @@ def test_driver_encoder_to_csv_bytes_one_vs_three_ranks_uneven(tmp_path, monkeyp
     tmp = str(tmp_path)
     one = _driver_csv(1, 0, tmp, 260, 50)
     csv1 = open(glob.glob(os.path.join(one, "*.csv"))[0], "rb").read()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_driver_worker, args=(r, 3, port, tmp, 260, 50, q)) for r in range(3)]
-    for p in procs:
-        p.start()
-    got = dict(q.get(timeout=900) for _ in range(3))
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    got = util.run_ranks(3, _driver_csv, (tmp, 260, 50), timeout=900, env=util.TORCHRUN_ENV)
     csv3 = open(glob.glob(os.path.join(got[0], "*.csv"))[0], "rb").read()
     assert csv1 == csv3
 
@@ -343,16 +274,7 @@ def test_driver_encoder_to_csv_bytes_one_vs_four_ranks_cfg2_preset(tmp_path, mon
     tmp = str(tmp_path)
     one = _driver_csv(1, 0, tmp, 250, 25)
     csv1 = open(glob.glob(os.path.join(one, "*.csv"))[0], "rb").read()
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_driver_worker, args=(r, 4, port, tmp, 250, 25, q)) for r in range(4)]
-    for p in procs:
-        p.start()
-    got = dict(q.get(timeout=900) for _ in range(4))
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    got = util.run_ranks(4, _driver_csv, (tmp, 250, 25), timeout=900, env=util.TORCHRUN_ENV)
     csv4 = open(glob.glob(os.path.join(got[0], "*.csv"))[0], "rb").read()
     assert csv1 == csv4
 

@@ -8,13 +8,14 @@ ATen's fp32 result on the same inputs (measured in the same test) plus 1e-6; the
 a different summation order."""
 import glob
 import os
-import socket
 import sys
 
 import pytest
 import torch
-import torch.multiprocessing as mp
 import torch.nn.functional as F
+
+import util
+from util import mild_bn as _mild_bn, nerr as _nerr
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,13 +33,6 @@ def core(mcd):
 def du(mcd):
     from mammo_clip_dissect_amd.concept_vit import data_utils
     return data_utils
-
-
-def _nerr(got, ref):
-    """max |got - ref| / max |ref| in float64."""
-    got = got.detach().double().cpu()
-    ref = ref.detach().double().cpu()
-    return float((got - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
 
 
 def _bound(e_hip, e_aten, what):
@@ -269,40 +263,7 @@ def test_linear_residual_plain_bits_do_not_depend_on_the_relu_entry(core, dev, m
 
 
 # ---- 5. blocks and the tower ------------------------------------------------------------------------------------------
-def _mild_bn(mod, seed):
-    """Random BN statistics, gamma and beta that keep 16 blocks' activations in range (the defaults hide folding errors)."""
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for m in mod.modules():
-            if isinstance(m, torch.nn.BatchNorm2d):
-                n = m.num_features
-                m.running_mean.copy_(torch.randn(n, generator=g) * 0.1)
-                m.running_var.copy_(torch.rand(n, generator=g) + 0.5)
-                m.weight.copy_(1 + 0.2 * torch.randn(n, generator=g))
-                m.bias.copy_(0.1 * torch.randn(n, generator=g))
-
-
 NEW_WRAPPERS = ("conv7x7s2_nhwc", "bn_relu_maxpool_nhwc", "conv_igemm_nhwc")
-
-
-class _Counter:
-    def __init__(self, core, monkeypatch):
-        self.n = {}
-        self.relu_gemms = 0
-        for name in NEW_WRAPPERS:
-            fn = getattr(core, name)
-
-            def wrap(*a, _fn=fn, _name=name, **kw):
-                self.n[_name] = self.n.get(_name, 0) + 1
-                return _fn(*a, **kw)
-            monkeypatch.setattr(core, name, wrap)
-        lr = core.linear_residual
-
-        def lin(*a, **kw):
-            if kw.get("relu"):
-                self.relu_gemms += 1
-            return lr(*a, **kw)
-        monkeypatch.setattr(core, "linear_residual", lin)
 
 
 @pytest.mark.parametrize("size", [(224, 224), (160, 96)])
@@ -319,7 +280,7 @@ def test_blocks_against_float64(du, core, dev, monkeypatch, size):
         net(torch.zeros(1, 3, *size))
     for h in hs:
         h.remove()
-    cnt = _Counter(core, monkeypatch)
+    cnt = util.CallCounter(core, monkeypatch, NEW_WRAPPERS)
     for li, bi, blk in blocks:
         C, H, W = sizes[(li, bi)]
         g = torch.Generator().manual_seed(10 * li + bi)
@@ -364,7 +325,7 @@ def test_tower_against_float64_and_routing(du, core, dev, monkeypatch, size):
     x = torch.randn(2, 3, *size, generator=g)
     ref, ref_outs = _hooked(net.double(), x.double())
     net.float().to(dev)
-    cnt = _Counter(core, monkeypatch)
+    cnt = util.CallCounter(core, monkeypatch, NEW_WRAPPERS)
     monkeypatch.setattr(du, "HIP_RESNET", False)
     aten, aten_outs = _hooked(net, x.to(dev))
     assert cnt.n == {} and cnt.relu_gemms == 0                        # the flag off: no new kernel is called
@@ -421,7 +382,7 @@ def test_two_extractions_give_the_same_bytes(du, core, dev, tmp_path, monkeypatc
     For the deeper layers batch-size independence holds only where hipBLASLt's pick is the same for both GEMM heights,
     which this test does not assert."""
     monkeypatch.setenv("MCD_BLASLT_PICK", "heuristic")
-    cnt = _Counter(core, monkeypatch)
+    cnt = util.CallCounter(core, monkeypatch, NEW_WRAPPERS)
     act1, csv1 = _run_driver(dev, str(tmp_path), "one")
     assert cnt.n.get("conv_igemm_nhwc", 0) >= 19 * 4 and cnt.n.get("conv7x7s2_nhwc", 0) >= 4
     act2, csv2 = _run_driver(dev, str(tmp_path), "two")
@@ -438,15 +399,10 @@ def test_two_extractions_give_the_same_bytes(du, core, dev, tmp_path, monkeypatc
 
 
 # ---- 8. one rank against two ------------------------------------------------------------------------------------------
-def _free_port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
-
-
 def _rank_driver(world, rank, tmp, n_images, batch):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import mammo_clip_dissect_amd  # noqa: F401
-    import util
     from mammo_clip_dissect_amd import pipeline
     from mammo_clip_dissect_amd.concept_vit import describe_clip_neurons
     if world > 1:   # one GPU holds every rank: the RCCL transport cannot, the host-staged rehearsal of it can
@@ -460,17 +416,6 @@ def _rank_driver(world, rank, tmp, n_images, batch):
     return out
 
 
-def _rank_worker(rank, world, port, tmp, n_images, batch, q):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    os.environ["WORLD_SIZE"] = str(world); os.environ["RANK"] = str(rank); os.environ["LOCAL_RANK"] = "0"
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    out = _rank_driver(world, rank, tmp, n_images, batch)
-    q.put((rank, out))
-    dist.barrier()
-    dist.destroy_process_group()
-
-
 def test_driver_csv_bytes_one_vs_two_ranks(mcd, dev, tmp_path, monkeypatch):
     """The whole ResNet-50 job through the HIP route at 1 rank and at 2 ranks (spawned processes on one GPU, gloo, equal
     batch shapes, the heuristic hipBLASLt pick): rank 0's CSV is the same bytes -- an image's activations do not depend
@@ -480,15 +425,6 @@ def test_driver_csv_bytes_one_vs_two_ranks(mcd, dev, tmp_path, monkeypatch):
     tmp = str(tmp_path)
     csv = {}
     for world in (1, 2):        # fresh processes: this one may keep timed GEMM picks for these shapes from other tests
-        ctx = mp.get_context("spawn")
-        q = ctx.Queue()
-        port = _free_port()
-        procs = [ctx.Process(target=_rank_worker, args=(r, world, port, tmp, 160, 40, q)) for r in range(world)]
-        for p in procs:
-            p.start()
-        got = dict(q.get(timeout=900) for _ in range(world))
-        for p in procs:
-            p.join(timeout=120)
-            assert p.exitcode == 0
+        got = util.run_ranks(world, _rank_driver, (tmp, 160, 40), timeout=900, env=util.TORCHRUN_ENV)
         csv[world] = open(glob.glob(os.path.join(got[0], "*.csv"))[0], "rb").read()
     assert csv[1] == csv[2] and len(csv[1]) > 10000

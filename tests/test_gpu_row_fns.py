@@ -7,13 +7,11 @@
     where the per-layer route has no cache files to read; the broad driver still raises the reference's TypeError."""
 import glob
 import os
-import socket
 import sys
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
 import util
 
@@ -170,10 +168,6 @@ def test_fused_row_fns_against_goldens(mcd, dev):
 
 
 # ---- 3. ranks == one rank ------------------------------------------------------------------------------------------
-def _free_port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
-
-
 def _run(world, rank, N, widths, C, D, seed, top_fraction):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -202,36 +196,12 @@ def _run(world, rank, N, widths, C, D, seed, top_fraction):
     return out
 
 
-def _worker(rank, world, port, case, q):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    out = _run(world, rank, *case)
-    q.put((rank, out))
-    dist.barrier()
-    dist.destroy_process_group()
-
-
-def _spawn(world, target, args, timeout=600):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=target, args=(r, world, port) + tuple(args) + (q,)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = dict(q.get(timeout=timeout) for _ in range(world))
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
-    return got
-
-
 @pytest.mark.parametrize("world,case", [(2, (1200, [96, 40, 7], 763, 512, 21, 0.05)),
                                         (3, (1001, [64, 33], 763, 512, 23, 0.05)),    # 334 + 334 + 333 images
                                         (4, (250, [40, 9], 763, 512, 24, 0.5))])      # top_n = 125 > every shard (63)
 def test_row_fns_ranks_on_hip_bit_identical_to_one(mcd, world, case):
     single = _run(1, 0, *case)
-    got = _spawn(world, _worker, (case,))
+    got = util.run_ranks(world, _run, case, timeout=600)
     for r in range(world):
         for fn in ROW_FNS:
             for a, b in zip(single[fn], got[r][fn]):
@@ -284,17 +254,6 @@ def _og_driver(world, rank, tmp, fn):
     return out
 
 
-def _og_worker(rank, world, port, tmp, fn, q):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    os.environ["WORLD_SIZE"] = str(world); os.environ["RANK"] = str(rank); os.environ["LOCAL_RANK"] = "0"
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    out = _og_driver(world, rank, tmp, fn)
-    q.put((rank, out))
-    dist.barrier()
-    dist.destroy_process_group()
-
-
 @pytest.mark.parametrize("fn", ["cos_similarity", "rank_reorder"])
 def test_og_driver_two_ranks_equal_one(mcd, dev, tmp_path, monkeypatch, fn):
     """describe_og_neurons under two ranks with cos_similarity / rank_reorder: a multi-rank run writes no activation cache,
@@ -304,7 +263,7 @@ def test_og_driver_two_ranks_equal_one(mcd, dev, tmp_path, monkeypatch, fn):
     monkeypatch.setenv("MCD_SHARD_ALIGN", "50")
     tmp = str(tmp_path)
     one = _csv_bytes(_og_driver(1, 0, tmp, fn))
-    got = _spawn(2, _og_worker, (tmp, fn), timeout=900)
+    got = util.run_ranks(2, _og_driver, (tmp, fn), timeout=900, env=util.TORCHRUN_ENV)
     assert _csv_bytes(got[0]) == one and len(one) > 10000
     assert not glob.glob(os.path.join(tmp, "acts2_*", "**", "*.pt"), recursive=True)     # no cache files at two ranks
 

@@ -2,14 +2,14 @@
 the hook bookkeeping, and the image-sharded multi-rank path under gloo (world_size 2) with the
 oracle-backed test backend (tests/cpu_ops.py)."""
 import io
+import multiprocessing
 import os
-import socket
 import sys
+import time
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
 import util
 
@@ -203,10 +203,6 @@ def test_hooks_fill_the_activation_matrix(mcd):
 
 
 # ---- world_size 2 under gloo ------------------------------------------------------------------------
-def _free_port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
-
-
 def _make_problem(N, widths, C, D, seed):
     g = torch.Generator().manual_seed(seed)
     U = sum(widths)
@@ -235,14 +231,8 @@ def _run_dissect(world, rank, N, widths, C, D, K, seed, group=None):
     return r.sim, r.vals, r.ids, r.top_ids, r.top_vals
 
 
-def _worker(rank, world, port, args, q):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    out = _run_dissect(world, rank, *args)
-    q.put((rank, [o.numpy() for o in out]))
-    dist.barrier()
-    dist.destroy_process_group()
+def _run_dissect_np(world, rank, *case):
+    return [o.numpy() for o in _run_dissect(world, rank, *case)]
 
 
 @pytest.mark.parametrize("world,case", [(2, (240, [7, 12], 37, 16, 50, 5)), (2, (200, [5], 763, 32, 100, 9)),
@@ -255,17 +245,8 @@ def test_ranks_bit_identical_to_one(mcd, world, case):
     neurons split for scoring, prob_d_given_e all-gathered.  No float is reduced across ranks, so the G-rank
     result must equal the 1-rank result bit for bit -- for any N, divisible by G or not (the reference walks any
     N, utils.py:174-181)."""
-    single = [o.numpy() for o in _run_dissect(1, 0, *case)]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, case, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = dict(q.get(timeout=300) for _ in range(world))
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    single = _run_dissect_np(1, 0, *case)
+    got = util.run_ranks(world, _run_dissect_np, case, timeout=300)
     for r in range(world):
         for a, b in zip(single, got[r]):
             assert np.array_equal(a, b)
@@ -387,10 +368,9 @@ def test_vit_tower_host_structure(mcd):
         assert torch.equal(t(x), t.layernorm(t.encoder(e)))
 
 
-def _fuzz_worker(rank, world, port, n_cases, seed, q):
+def _fuzz(world, rank, n_cases, seed):
+    """The list of failing cases on rank 0 (None on the others)."""
     import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     groups = {g: dist.new_group(list(range(g))) for g in range(1, world + 1)}   # every rank creates every group
     rng = np.random.default_rng(seed)                                           # same stream on every rank
     bad = []
@@ -406,28 +386,43 @@ def _fuzz_worker(rank, world, port, n_cases, seed, q):
             single = _run_dissect(1, 0, *case, group=groups[1])
             if not all(torch.equal(a, b) for a, b in zip(single, out)):
                 bad.append((g,) + case)
-    if rank == 0:
-        q.put(bad)
-    dist.barrier()
-    dist.destroy_process_group()
+    return bad if rank == 0 else None
 
 
 def test_ranks_fuzz(mcd):
     """Random probe-set sizes, rank counts (2..4, as sub-groups of one 4-process gloo world), layer widths, concept counts and
     top_k -- shards smaller than top_k, ranks without images or without neurons included: the sharded result equals the
     one-rank result bit for bit in every case."""
-    world = 4
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_fuzz_worker, args=(r, world, port, 30, 5, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    bad = q.get(timeout=600)
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    bad = util.run_ranks(4, _fuzz, (30, 5), timeout=600)[0]
     assert bad == []
+
+
+# ---- the rank-spawn harness itself (tests/util.py: run_ranks) ----------------------------------------------------------
+def _rank_of(world, rank):
+    return rank
+
+
+def _rank_one_exits(world, rank):
+    if rank == 1:
+        sys.exit(3)        # before the barrier in which the ranks meet: rank 0 is left waiting there for good
+    return rank
+
+
+def test_run_ranks_returns_every_ranks_result():
+    assert util.run_ranks(2, _rank_of, timeout=120) == {0: 0, 1: 1}
+    assert not multiprocessing.active_children()
+
+
+def test_run_ranks_fails_fast_when_a_rank_dies():
+    """One rank exits non-zero while the other waits for it in a collective: the helper names the rank and its exit code,
+    comes back long before its timeout (under a quarter of it: the time is spent starting the processes, not waiting for
+    the dead rank) and leaves no process behind."""
+    timeout = 120
+    t0 = time.monotonic()
+    with pytest.raises(AssertionError, match=r"rank 1 exited with code 3"):
+        util.run_ranks(2, _rank_one_exits, timeout=timeout)
+    assert time.monotonic() - t0 < timeout / 4
+    assert not multiprocessing.active_children()
 
 
 def test_bench_refuses_to_run_fewer_ranks_than_asked():

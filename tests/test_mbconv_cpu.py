@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from util import FakeCuda as _FakeCuda, entry_rc as _rc, nhwc_input as _nhwc_input, randomise_bn as _randomise_bn
+
 NULL = None
 P = 4096            # a non-NULL pointer value that no rejected call may dereference
 
@@ -14,17 +16,6 @@ P = 4096            # a non-NULL pointer value that no rejected call may derefer
 def du(mcd):
     from mammo_clip_dissect_amd.concept_vit import data_utils
     return data_utils
-
-
-def _randomise_bn(mod, g):
-    """Random running statistics, gamma and beta on every BatchNorm2d (the defaults make BN nearly an identity)."""
-    for m in mod.modules():
-        if isinstance(m, torch.nn.BatchNorm2d):
-            n = m.num_features
-            m.running_mean.copy_(torch.randn(n, generator=g, dtype=m.running_mean.dtype))
-            m.running_var.copy_(torch.rand(n, generator=g, dtype=m.running_var.dtype) * 2 + 0.05)
-            m.weight.data.copy_(torch.randn(n, generator=g, dtype=m.weight.dtype))
-            m.bias.data.copy_(torch.randn(n, generator=g, dtype=m.bias.dtype))
 
 
 @pytest.mark.parametrize("cin,cout,k,s,expand", [(48, 24, 3, 1, 1), (24, 40, 5, 2, 6), (64, 64, 3, 1, 6)])
@@ -81,7 +72,7 @@ def test_fold_cache_follows_the_parameters(du):
         blk._bn1.running_var.mul_(4.0)
     b = du._folded(blk, du._MBCONV_SKIPPED, du._MBConv._fold)
     assert b is not a and not torch.equal(a["wd"], b["wd"]) and torch.equal(a["wp"], b["wp"])
-    assert list(blk.state_dict().keys()) == keys and "_mbconv_fold" not in dict(blk.named_buffers())
+    assert list(blk.state_dict().keys()) == keys and "_fold_cache" not in dict(blk.named_buffers())
 
 
 def _core():
@@ -110,19 +101,6 @@ def test_same_padding_matches_sameconv(du, k, s):
             assert core.dwconv_tiles(o, o) == (-(-o // 8)) ** 2
     assert core.same_pad(112, 3, 2) == (56, 0, 1)               # stride 2 is asymmetric: 0 on top, 1 at the bottom
     assert core.same_pad(224, 3, 2) == (112, 0, 1) and core.same_pad(57, 5, 2) == (29, 2, 2)
-
-
-class _FakeCuda(torch.Tensor):
-    """A host tensor that says it is on the GPU: lets the route's other conditions be checked one at a time here."""
-
-    @property
-    def is_cuda(self):
-        return True
-
-
-def _nhwc_input(c, h=9, w=7):
-    x = torch.randn(2, c, h, w).contiguous(memory_format=torch.channels_last)
-    return x.as_subclass(_FakeCuda)
 
 
 def test_route_fallbacks(du, monkeypatch):
@@ -200,11 +178,6 @@ def test_block_modules_and_state_dict_unchanged(du):
 
 
 # ---- argument checks of the C entries (no device call happens on a rejected call) ------------------------------
-def _rc(mcd, name, *args):
-    L = mcd._lib.load()
-    return getattr(L, name)(*args)
-
-
 E_ARG, E_UNS = -1, -5
 
 

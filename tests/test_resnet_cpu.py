@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from util import FakeCuda as _FakeCuda, entry_rc as _rc, nhwc_input as _nhwc_input, randomise_bn as _randomise_bn
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL = None
 P = 4096            # a non-NULL, 16-byte aligned pointer value that no rejected call may dereference
@@ -24,29 +26,6 @@ def du(mcd):
 def _core():
     from mammo_clip_dissect_amd import core
     return core
-
-
-def _randomise_bn(mod, g):
-    """Random running statistics, gamma and beta on every BatchNorm2d (the defaults make BN nearly an identity)."""
-    for m in mod.modules():
-        if isinstance(m, torch.nn.BatchNorm2d):
-            n = m.num_features
-            m.running_mean.copy_(torch.randn(n, generator=g, dtype=m.running_mean.dtype))
-            m.running_var.copy_(torch.rand(n, generator=g, dtype=m.running_var.dtype) * 2 + 0.05)
-            m.weight.data.copy_(torch.randn(n, generator=g, dtype=m.weight.dtype))
-            m.bias.data.copy_(torch.randn(n, generator=g, dtype=m.bias.dtype))
-
-
-class _FakeCuda(torch.Tensor):
-    """A host tensor that says it is on the GPU: lets the route's other conditions be checked one at a time here."""
-
-    @property
-    def is_cuda(self):
-        return True
-
-
-def _nhwc_input(c, h=9, w=7):
-    return torch.randn(2, c, h, w).contiguous(memory_format=torch.channels_last).as_subclass(_FakeCuda)
 
 
 # ---- symbols ------------------------------------------------------------------------------------------------------
@@ -256,10 +235,6 @@ def test_output_size_arithmetic():
 
 
 # ---- argument checks ------------------------------------------------------------------------------------------------
-def _rc(mcd, name, *args):
-    return getattr(mcd._lib.load(), name)(*args)
-
-
 def test_entries_reject_bad_arguments(mcd):
     s = None
     # K16 mcd_conv7x7s2_nhwc(x, B, Cin, H, W, w, Cout, y, stream)

@@ -3,13 +3,13 @@
 under gloo with an oracle-backed stand-in for the kernels: G ranks give the one-rank bits, the permutation stream and
 the generator state are the per-layer loop's, the argument checks raise what the drop-in raises."""
 import os
-import socket
 import sys
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
+
+import util
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROW_FNS = ("rank_reorder", "cos_similarity", "cos_similarity_cubed")
@@ -117,19 +117,6 @@ def _run_all(world, rank, N, widths, C, D, seed, top_fraction, group=None):
     return out
 
 
-def _free_port():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
-
-
-def _worker(rank, world, port, case, q):
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    q.put((rank, _run_all(world, rank, *case)))
-    dist.barrier()
-    dist.destroy_process_group()
-
-
 @pytest.mark.parametrize("world,case", [(2, (240, [7, 12], 37, 16, 5, 0.05)),
                                         (3, (130, [9, 4], 37, 16, 7, 0.5)),       # 44 + 43 + 43 images, top_n = 65: every shard < top_n
                                         (4, (201, [13, 8, 3], 40, 16, 9, 0.1)),   # 51 + 50 + 50 + 50
@@ -139,16 +126,7 @@ def test_row_fns_ranks_bit_identical_to_one(mcd, world, case):
     """Every output of the three functions at G ranks equals the one-rank output bit for bit, and every rank's CPU generator
     ends where the one-rank run's does (each rank draws the whole permutation stream)."""
     single = _run_all(1, 0, *case)
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, case, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    got = dict(q.get(timeout=300) for _ in range(world))
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
+    got = util.run_ranks(world, _run_all, case, timeout=300)
     for r in range(world):
         for fn in ROW_FNS:
             for a, b in zip(single[fn], got[r][fn]):

@@ -1,7 +1,13 @@
-"""Shared helpers for the parity tests: golden loading and the stated tolerances."""
+"""Shared helpers for the tests: golden loading and the stated tolerances, the rank-spawn harness of the multi-rank
+tests, and the helpers the two tower test files (EfficientNet-B5, ResNet-50) share."""
 import os
+import socket
+import sys
+import time
+from multiprocessing.connection import wait
 
 import numpy as np
+import torch
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = ["tiny", "main", "relu", "kfull", "one_neuron", "n1000"]
@@ -32,8 +38,6 @@ def regen_n1000():
     """Inputs of the n1000 case are regenerated from the seed (make_golden.py: make_inputs).  P is recomputed with
     the oracle's restatement of the fixture host's normalise + matmul order (bit-identical to every stored P): torch's
     own matmul on the host running the tests may cut K differently (MKL picks per CPU model)."""
-    import sys
-    import torch
     sys.path.insert(0, os.path.join(os.path.dirname(GOLDEN), os.pardir, "oracle"))
     import oracle as O
     N, C, U, D, seed = 1000, 763, 48, 512, 61
@@ -50,8 +54,6 @@ def regen_n1000():
 def regen_inputs(N, C, U, D, seed):
     """make_golden.py: make_inputs(..., act="gauss") regenerated from the seed; P by the oracle's restatement of the
     fixture host's normalise + matmul order."""
-    import sys
-    import torch
     sys.path.insert(0, os.path.join(os.path.dirname(GOLDEN), os.pardir, "oracle"))
     import oracle as O
     E_img = torch.randn(N, D, generator=torch.Generator().manual_seed(seed)).numpy()
@@ -189,7 +191,6 @@ def host_staged_gather(group=None):
     """A `gather` for pipeline.Dissector that rehearses several ranks on ONE GPU: RCCL cannot put two ranks on one
     device, so the ranks rendezvous over gloo and the payload is staged through the host.  Test/bench rehearsal only --
     the package's own transport is rccl_all_gather_rows (device memory, backend "nccl")."""
-    import torch
     import torch.distributed as dist
 
     def gather(t):
@@ -214,7 +215,6 @@ def fuzz_cases():
 def fuzz_case(i):
     """Case i of tests/golden/sim_fuzz.npz: inputs regenerated from the stored recipe (torch's CPU generator; every byte checked
     against the sha256 the generator script stored), the reference's soft_wpmi / wpmi outputs and top-10 lists."""
-    import torch
     if "z" not in _FUZZ:
         _FUZZ["z"] = np.load(os.path.join(GOLDEN, "sim_fuzz.npz"))
         _FUZZ["meta"] = fuzz_cases()
@@ -256,3 +256,149 @@ def fuzz_compare(got, ref_full, what, stats):
         assert not bad[:, 0].any(), "%s: the top concept differs on %d neurons whose reference gap exceeds %.2g" % (what, int(bad[:, 0].sum()), FUZZ_TOP1_GAP)
         assert n_bad == 0, "%s: %d decided top-10 ranks differ" % (what, n_bad)
     stats.append((what, int(d.size), int((got == ref).sum()), float(d.max()), n_dec))
+
+
+# ---- the rank-spawn harness ---------------------------------------------------------------------------------------------
+RANK_EXIT_GRACE = 120     # seconds the ranks get to leave the barrier and exit once every result is in
+TORCHRUN_ENV = {"WORLD_SIZE": "{world}", "RANK": "{rank}", "LOCAL_RANK": "0"}    # what the drivers read (all ranks on cuda:0)
+
+
+def free_port():
+    s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
+
+
+def _rank_main(rank, world, port, body, args, env, conn):
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), **{k: str(v).format(world=world, rank=rank)
+                                                                          for k, v in (env or {}).items()})
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    conn.send(body(world, rank, *args))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def run_ranks(world, body, args=(), timeout=600, env=None):
+    """body(world, rank, *args) in `world` spawned processes that form one gloo group; returns {rank: result}.
+
+    Each process sets the rendezvous variables and `env` ("{world}" / "{rank}" in a value are filled in; TORCHRUN_ENV is
+    the set the drivers read), joins the group, sends body's result, then meets the others in a barrier and leaves.  The
+    parent waits on the result pipes and on the processes together: `timeout` seconds for the results, RANK_EXIT_GRACE
+    more for the exits.  The moment a process exits non-zero or the time is up, the remaining ones -- blocked in a
+    collective that can no longer complete, each with its device open -- are terminated (killed after 5 s), joined, and
+    the call fails with the rank and its exit code."""
+    import torch.multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    port = free_port()
+    procs, pipes = [], {}
+    for r in range(world):
+        rd, wr = ctx.Pipe(duplex=False)
+        procs.append(ctx.Process(target=_rank_main, args=(r, world, port, body, tuple(args), env, wr)))
+        procs[-1].start()
+        wr.close()
+        pipes[rd] = r
+    running = {p.sentinel: r for r, p in enumerate(procs)}
+    results, failed, t0 = {}, [], time.monotonic()
+    try:
+        while not failed and (running or pipes):
+            left = t0 + timeout + (RANK_EXIT_GRACE if len(results) == world else 0) - time.monotonic()
+            ready = wait(list(pipes) + list(running), max(left, 0))
+            if not ready:
+                failed.append("rank(s) %s still running after %d s" % (sorted(running.values()), time.monotonic() - t0))
+            for x in ready:
+                if x in pipes:
+                    r = pipes.pop(x)
+                    try:
+                        results[r] = x.recv()
+                    except EOFError:          # the process ended without a result: its exit code says why
+                        pass
+                else:
+                    r = running.pop(x)
+                    procs[r].join()
+                    if procs[r].exitcode != 0:
+                        failed.append("rank %d exited with code %s" % (r, procs[r].exitcode))
+        if not failed and len(results) < world:
+            failed.append("rank(s) %s exited with code 0 without a result" % sorted(set(range(world)) - set(results)))
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.terminate()
+        for p in procs:
+            p.join(5)
+            if p.is_alive():
+                p.kill()
+                p.join()
+    assert not failed, "run_ranks(%d ranks, %s): %s" % (world, getattr(body, "__name__", body), "; ".join(failed))
+    return results
+
+
+# ---- shared by the EfficientNet-B5 and ResNet-50 tower tests ------------------------------------------------------------
+def nerr(got, ref):
+    """max |got - ref| / max |ref| in float64."""
+    got = got.detach().double().cpu()
+    ref = ref.detach().double().cpu()
+    return float((got - ref).abs().max() / ref.abs().max().clamp_min(1e-30))
+
+
+def mild_bn(mod, seed):
+    """Random BN statistics, gamma and beta that keep a whole tower's activations in range (the defaults hide folding
+    errors)."""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for m in mod.modules():
+            if isinstance(m, torch.nn.BatchNorm2d):
+                n = m.num_features
+                m.running_mean.copy_(torch.randn(n, generator=g) * 0.1)
+                m.running_var.copy_(torch.rand(n, generator=g) + 0.5)
+                m.weight.copy_(1 + 0.2 * torch.randn(n, generator=g))
+                m.bias.copy_(0.1 * torch.randn(n, generator=g))
+
+
+def randomise_bn(mod, g):
+    """Random running statistics, gamma and beta on every BatchNorm2d (the defaults make BN nearly an identity)."""
+    for m in mod.modules():
+        if isinstance(m, torch.nn.BatchNorm2d):
+            n = m.num_features
+            m.running_mean.copy_(torch.randn(n, generator=g, dtype=m.running_mean.dtype))
+            m.running_var.copy_(torch.rand(n, generator=g, dtype=m.running_var.dtype) * 2 + 0.05)
+            m.weight.data.copy_(torch.randn(n, generator=g, dtype=m.weight.dtype))
+            m.bias.data.copy_(torch.randn(n, generator=g, dtype=m.bias.dtype))
+
+
+class CallCounter:
+    """Counts the calls of the named core wrappers (n[name], absent until the first call) and the core.linear_residual
+    calls with relu=True (relu_gemms), by monkeypatching the module attributes the routes call through."""
+
+    def __init__(self, core, monkeypatch, names):
+        self.n = {}
+        self.relu_gemms = 0
+        for name in names:
+            fn = getattr(core, name)
+
+            def wrap(*a, _fn=fn, _name=name, **kw):
+                self.n[_name] = self.n.get(_name, 0) + 1
+                return _fn(*a, **kw)
+            monkeypatch.setattr(core, name, wrap)
+        lr = core.linear_residual
+
+        def lin(*a, **kw):
+            if kw.get("relu"):
+                self.relu_gemms += 1
+            return lr(*a, **kw)
+        monkeypatch.setattr(core, "linear_residual", lin)
+
+
+class FakeCuda(torch.Tensor):
+    """A host tensor that says it is on the GPU: lets the route's other conditions be checked one at a time on the CPU."""
+
+    @property
+    def is_cuda(self):
+        return True
+
+
+def nhwc_input(c, h=9, w=7):
+    return torch.randn(2, c, h, w).contiguous(memory_format=torch.channels_last).as_subclass(FakeCuda)
+
+
+def entry_rc(mcd, name, *args):
+    """The return code of the C entry `name` called with raw arguments (the argument checks: no device call happens)."""
+    return getattr(mcd._lib.load(), name)(*args)
