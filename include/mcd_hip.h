@@ -269,6 +269,22 @@ int mcd_vit_attention(const float* qkv, int64_t B, int64_t T, int64_t H, float* 
 int mcd_vit_attention_long(const float* qkv, int64_t B, int64_t T, int64_t H, float* out, mcd_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * K9C  the same attention for ONE query row per image (the class token of the last encoder block, whose other rows
+ *      nothing reads): out[b, h, :] = softmax_j(q[b,h].k[b,j,h] / 8) v[b,j,h], fp32 throughout, head dimension 64,
+ *      1 <= T <= 32 768.  q is one row of H*64 floats per image, q_img floats apart; token j of image b of k (of v) is
+ *      at k + b*k_img + j*k_row (v + b*v_img + j*v_row), H*64 floats; out is [B, H*64], contiguous.  So a
+ *      [B, T, 2, H, 64] K|V projection (k_row = 2*H*64, v = k + H*64) and a plain [B, T, 3, H, 64] qkv (q_img = T*3*H*64,
+ *      k = qkv + H*64, v = qkv + 2*H*64, rows 3*H*64 apart) are both read in place.  Every stride >= H*64 and a multiple
+ *      of 4 floats, all pointers 16-byte aligned (MCD_E_ARG), T past the limit MCD_E_UNSUPPORTED.
+ *      A streaming kernel: every K and V head row is read once (2*B*T*H*256 bytes), 16 lanes x float4 per row, online
+ *      softmax per 16-lane row, no T-sized scratch.  K9's accuracy contract; not K9's bits (another summation order).
+ * replaces  row 0 of the attention inside the last ViTLayer                 model/modules/image_encoder.py:37
+ *           (all that output[:, 0] / encode_image read)                     concept_vit/utils.py:39-49, model/clip.py:49-52
+ * ------------------------------------------------------------------------------------------- */
+int mcd_vit_attention_cls(const float* q, int64_t q_img, const float* k, int64_t k_row, int64_t k_img, const float* v,
+                          int64_t v_row, int64_t v_img, int64_t B, int64_t T, int64_t H, float* out, mcd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K10  fp32 LayerNorm over the last dimension (biased variance, like torch): rows x D contiguous, D a multiple of 4
  *      up to 2048, pointers 16-byte aligned.  One wave per row, the row register-resident, two-pass statistics.
  *      Encoder-side op, fp32-accurate (<= 1e-6 relative from torch's), no bit-exactness claim.

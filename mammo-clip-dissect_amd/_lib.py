@@ -39,6 +39,7 @@ SIGNATURES = {
     "mcd_rank_reorder": (_int, [_p, _i64, _i64, _i64, _p, _p, _i64, _i64, _int, _p, _int, _f, _f, _p, _p, _i64, _p]),
     "mcd_vit_attention": (_int, [_p, _i64, _i64, _i64, _p, _p]),
     "mcd_vit_attention_long": (_int, [_p, _i64, _i64, _i64, _p, _p]),
+    "mcd_vit_attention_cls": (_int, [_p, _i64, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _p, _p]),
     "mcd_layer_norm": (_int, [_p, _i64, _i64, _p, _p, _f, _p, _p]),
     "mcd_patchify": (_int, [_p, _i64, _i64, _i64, _i64, _i64, _p, _p]),
     "mcd_conv_stem_nhwc": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _i64, _p, _p]),

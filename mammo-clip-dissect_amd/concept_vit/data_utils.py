@@ -39,6 +39,11 @@ _attention_calls = 0
 # core.linear_residual) instead of nn.Linear + an elementwise add over the residual stream.  Inference-time fp32 only;
 # MCD_NO_FUSED_RESIDUAL=1 (or False here, or a missing libmcd_blaslt.so) keeps PyTorch's two kernels.
 FUSED_RESIDUAL = os.environ.get("MCD_NO_FUSED_RESIDUAL", "0") != "1"
+# encode_image reads token 0 of the tower's output, and so does every activation hook of the package (core.hook_pool
+# on a 3-D output): of the LAST encoder block only the class-token row is ever used.  With this on, that block computes
+# K and V for all tokens and everything else (q, attention on K9C, proj, the MLP, the final LayerNorm) for the class
+# token alone and returns [B, 1, D] (cls_tail_route).  MCD_NO_CLS_ONLY_TAIL=1 (or False here) keeps the full block.
+CLS_ONLY_TAIL = os.environ.get("MCD_NO_CLS_ONLY_TAIL", "0") != "1"
 
 
 # nn.LayerNorm of the towers on the HIP kernel K10 (csrc/k_ln.hip); MCD_NO_HIP_LAYER_NORM=1 keeps ATen's.
@@ -118,6 +123,22 @@ def attention_route(T, D, heads, masked, on_gpu, dtype, needs_grad):
     return "sdpa"
 
 
+def cls_tail_route(flag, fused_ok, masked, training, T, D, heads, depth, hooks_clear, last_hooks_token0):
+    """Whether a tower forward asked for its class token only may prune its last block to that row: CLS_ONLY_TAIL
+    (`flag`) and HIP_ATTENTION on, the fused-residual path available for the call (fp32 on the GPU, no autograd:
+    `fused_ok`), no mask, eval mode, D = 64 * heads, T within K9C's limit, at least one block, no hook that would see a
+    skipped call or a pruned tensor (`hooks_clear`: no global hooks, none inside the last block, none on the encoder or
+    the final LayerNorm, no pre-hook on the last block) and every forward hook on the last block or on the tower
+    declaring token0_only (`last_hooks_token0`)."""
+    return bool(flag and HIP_ATTENTION and fused_ok and not masked and not training and D == 64 * heads
+                and 1 <= T <= core.VIT_ATTENTION_CLS_MAX_T and depth >= 1 and hooks_clear and last_hooks_token0)
+
+
+def _token0_hooks(m):
+    """Every forward hook on m declares (attribute token0_only) that of a [B, T, D] output it reads token 0 only."""
+    return all(getattr(h, "token0_only", False) for h in m._forward_hooks.values())
+
+
 class _Attention(nn.Module):
     def __init__(self, dim, heads):
         super().__init__()
@@ -163,7 +184,9 @@ class _Block(nn.Module):
         self.fc1 = nn.Linear(dim, mlp)
         self.fc2 = nn.Linear(mlp, dim)
 
-    def forward(self, x, mask=None):
+    def forward(self, x, mask=None, cls_only=False):
+        if cls_only and mask is None:      # a masked call keeps the full block whatever the caller asked for
+            return self._forward_cls(x)
         if _fused_residual_ok(x):
             x = x.contiguous()
             # x1 is a new tensor (the block's input is left alone); the second update is in place on x1
@@ -174,6 +197,23 @@ class _Block(nn.Module):
         x = x + self.attn(self.norm1(x), mask)
         return x + self.fc2(F.gelu(self.fc1(self.norm2(x))))
 
+    def _forward_cls(self, x):
+        """The class-token row of forward(x), as [B, 1, D] (the caller has checked cls_tail_route): K and V need every
+        token -- norm1 and the K|V two thirds of the qkv projection run on all rows -- everything after them is computed
+        for row 0 of each image only.  The weight slices are contiguous views, x[:, 0] and norm1(x)[:, 0] go into the
+        GEMMs as row-strided operands: no copies."""
+        B, T, D = x.shape
+        a = self.attn
+        x = x.contiguous()
+        n = self.norm1(x)
+        w, b = a.qkv.weight, a.qkv.bias
+        kv = core.linear_residual(None, n, w[D:], None if b is None else b[D:]).view(B, T, 2, a.heads, D // a.heads)
+        q = core.linear_residual(None, n[:, 0], w[:D], None if b is None else b[:D])
+        o = core.vit_attention_cls(q, kv[:, :, 0], kv[:, :, 1])                          # K9C
+        x1 = core.linear_residual(x[:, 0], o, a.proj.weight, a.proj.bias)                # [B, D], a new tensor
+        h = F.gelu(core.linear_residual(None, self.norm2(x1), self.fc1.weight, self.fc1.bias))
+        return core.linear_residual(x1, h, self.fc2.weight, self.fc2.bias, out=x1).unsqueeze(1)
+
 
 class _Encoder(nn.Module):
     def __init__(self, depth, dim, heads, mlp, list_name):
@@ -181,9 +221,12 @@ class _Encoder(nn.Module):
         setattr(self, list_name, nn.ModuleList([_Block(dim, heads, mlp) for _ in range(depth)]))
         self._list_name = list_name
 
-    def forward(self, x, mask=None):
-        for blk in getattr(self, self._list_name):
-            x = blk(x, mask)
+    def forward(self, x, mask=None, cls_only=False):
+        """cls_only (ViTTower.forward has checked cls_tail_route): the last block is called, through __call__ so that its
+        hooks fire, for its class-token row alone and the result is [B, 1, D]."""
+        blocks = getattr(self, self._list_name)
+        for i, blk in enumerate(blocks):
+            x = blk(x, mask, cls_only=True) if cls_only and i == len(blocks) - 1 else blk(x, mask)
         return x
 
 
@@ -220,8 +263,29 @@ class ViTTower(nn.Module):
         self.encoder = _Encoder(depth, dim, heads, mlp, list_name)
         self.layernorm = _LayerNorm(dim, eps=1e-12)
 
-    def forward(self, x):
-        return self.layernorm(self.encoder(self.embed(x)))
+    def forward(self, x, cls_only=False):
+        """cls_only=True: the caller reads [:, 0] of the result and nothing else.  Where cls_tail_route allows, the last
+        block and the final LayerNorm then run on the class-token row alone and the result is [B, 1, D]; otherwise (and
+        for every plain tower(x)) the full [B, T, D], computed exactly as before."""
+        x = self.embed(x)
+        if cls_only and self._cls_tail_ok(x):
+            return self.layernorm(self.encoder(x, cls_only=True))
+        return self.layernorm(self.encoder(x))
+
+    def _cls_tail_ok(self, x):
+        """cls_tail_route for the embedded tokens x [B, T, D] and the hooks this tower carries right now."""
+        if not (CLS_ONLY_TAIL and isinstance(x, torch.Tensor) and x.dim() == 3):
+            return False
+        enc = self.encoder
+        blocks = getattr(enc, enc._list_name)
+        if len(blocks) == 0:
+            return False
+        last = blocks[-1]
+        clear = not (_nn_module._global_forward_hooks or _nn_module._global_forward_pre_hooks or last._forward_pre_hooks
+                     or any(_hooked(c) for c in last.children()) or _hooked(self.layernorm)
+                     or enc._forward_hooks or enc._forward_pre_hooks)
+        return cls_tail_route(CLS_ONLY_TAIL, _fused_residual_ok(x), False, self.training or last.training, x.shape[1],
+                              x.shape[2], last.attn.heads, len(blocks), clear, _token0_hooks(last) and _token0_hooks(self))
 
     def embed(self, x):
         """Patch embedding + class token + position embedding -> [B, 1 + n, dim]."""
@@ -542,8 +606,9 @@ class BreastClip(nn.Module):
         self.tokenizer = HashTokenizer()
 
     def encode_image(self, image):
-        f = self.image_encoder(image)
-        return f if self.model_type == "cnn" else f[:, 0]
+        if self.model_type == "cnn":
+            return self.image_encoder(image)
+        return self.image_encoder(image, cls_only=True)[:, 0]
 
     def encode_text(self, text_tokens):
         if not isinstance(text_tokens, dict):
@@ -585,7 +650,7 @@ class ClipViT(nn.Module):
         self.text_projection = nn.Linear(512, PROJ_DIM, bias=False)
 
     def encode_image(self, image):
-        return self.visual_projection(self.vision_model(image)[:, 0])
+        return self.visual_projection(self.vision_model(image, cls_only=True)[:, 0])
 
     def encode_text(self, tokens):
         f = self.text_model(tokens)

@@ -55,6 +55,7 @@ def get_activation(outputs, mode):
         dst = torch.empty((out.shape[0], width), dtype=torch.float32, device=out.device)
         core.hook_pool(out, mode, dst, 0, 0, False)
         outputs.append(dst)
+    hook.token0_only = True   # of a 3-D output only token 0 is read: see data_utils.cls_tail_route
     return hook
 
 

@@ -444,6 +444,40 @@ def vit_attention_long(qkv, heads, out=None):
     return _attention("mcd_vit_attention_long", qkv, heads, out)
 
 
+# ---- K9C -----------------------------------------------------------------------------------------
+VIT_ATTENTION_CLS_MAX_T = 32768
+
+
+@_on_device
+def vit_attention_cls(q, k, v, out=None):
+    """softmax(q k^T / 8) v per head for ONE query row per image (K9C): q [B, heads, 64] or [B, heads*64], k and v
+    [B, T, heads, 64] -> [B, heads*64].  The operands are read where they lie: q rows any distance apart, k and v with
+    any token (dim 1) and image (dim 0) strides, as long as a token's heads*64 floats are adjacent -- views of a
+    [B, T, 2, heads, 64] K|V projection or of a [B, T, 3, heads, 64] qkv.  fp32, 1 <= T <= VIT_ATTENTION_CLS_MAX_T."""
+    _need_gpu(q, k, v, out)
+    if any(t.dtype != torch.float32 for t in (q, k, v)) or k.dim() != 4 or k.shape[3] != 64 or v.shape != k.shape:
+        raise TypeError("vit_attention_cls: float32 k and v of one shape [B, T, heads, 64]")
+    B, T, H, _ = k.shape
+    if q.dim() == 3:
+        if tuple(q.shape) != (B, H, 64) or (H > 1 and q.stride(1) != 64):
+            raise ValueError("vit_attention_cls: q must be [B, heads, 64] with a row's heads adjacent")
+    elif tuple(q.shape) != (B, H * 64):
+        raise ValueError("vit_attention_cls: q has shape %s, k %s" % (tuple(q.shape), tuple(k.shape)))
+    if q.stride(-1) != 1 or any(t.stride(3) != 1 or (H > 1 and t.stride(2) != 64) for t in (k, v)):
+        raise ValueError("vit_attention_cls: the heads*64 floats of a token must be adjacent in q, k and v")
+    if out is None:
+        out = torch.empty((B, H * 64), dtype=torch.float32, device=k.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, H * 64) or not out.is_contiguous():
+        raise TypeError("out must be a contiguous float32 [B, heads*64] tensor")
+    W = H * 64
+    q_img = q.stride(0) if B > 1 else W
+    row = [t.stride(1) if T > 1 else W for t in (k, v)]
+    img = [t.stride(0) if B > 1 else max(T * r, W) for t, r in zip((k, v), row)]
+    check(_lib.load().mcd_vit_attention_cls(q.data_ptr(), q_img, k.data_ptr(), row[0], img[0], v.data_ptr(), row[1], img[1],
+                                            B, T, H, out.data_ptr(), _stream()))
+    return out
+
+
 # ---- K10 -----------------------------------------------------------------------------------------
 @_on_device
 def layer_norm(x, weight, bias, eps):
@@ -682,11 +716,18 @@ def set_encoder_gemm_picks(picks):
         L.mcd_linear_residual_set_pick(int(M), int(N), int(K), int(has_res), int(pick))
 
 
+def _row_strided(t):
+    """A 2-D matrix whose rows are contiguous and at least their width apart (rows picked out of a larger tensor)."""
+    return t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]
+
+
 @_on_device
 def linear_residual(res, h, weight, bias=None, out=None, relu=False):
     """out = res + h @ weight.T + bias in ONE hipBLASLt GEMM (bias epilogue + beta*C), instead of nn.Linear followed
     by an elementwise add over the whole residual stream.  res, h: [..., N] / [..., K] contiguous fp32 with the same
     leading shape; weight [N, K]; out defaults to a new tensor (pass out=res for in place).  res may be None.
+    A 2-D h or res may also be row-strided (unit inner stride, rows at least their width apart, e.g. x[:, 0] of a
+    [B, T, K] tensor): the GEMM reads the rows where they lie, with the true leading dimension.
     relu=True: out = relu(res + h @ weight.T + bias), the library's ReLU epilogue (mcd_linear_residual_relu; its plans
     and picks are kept apart from the plain entry's)."""
     L = _lib.load_blaslt()
@@ -699,9 +740,11 @@ def linear_residual(res, h, weight, bias=None, out=None, relu=False):
         raise ValueError("linear_residual: shapes h %s, weight %s, res %s do not match"
                          % (tuple(h.shape), tuple(weight.shape), None if res is None else tuple(res.shape)))
     for t in (h, weight, bias, res, out):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
-            raise TypeError("linear_residual: contiguous float32 tensors only")
+        if t is not None and (t.dtype != torch.float32 or not (t.is_contiguous() or (t is h or t is res) and _row_strided(t))):
+            raise TypeError("linear_residual: contiguous float32 tensors only (h and res: or 2-D row-strided)")
     M = h.numel() // K
+    ldh = K if h.is_contiguous() else h.stride(0)
+    ldr = N if res is None or res.is_contiguous() else res.stride(0)
     if out is None:
         out = torch.empty(h.shape[:-1] + (N,), dtype=torch.float32, device=h.device)
     elif tuple(out.shape) != tuple(h.shape[:-1]) + (N,):
@@ -714,8 +757,8 @@ def linear_residual(res, h, weight, bias=None, out=None, relu=False):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
     fn = L.mcd_linear_residual_relu if relu else L.mcd_linear_residual
-    rc = fn(h.data_ptr(), K, weight.data_ptr(), K, bias.data_ptr() if bias is not None else None,
-            res.data_ptr() if res is not None else None, N, out.data_ptr(), N, M, N, K, ws.data_ptr(), ws.numel(), _stream())
+    rc = fn(h.data_ptr(), ldh, weight.data_ptr(), K, bias.data_ptr() if bias is not None else None,
+            res.data_ptr() if res is not None else None, ldr, out.data_ptr(), N, M, N, K, ws.data_ptr(), ws.numel(), _stream())
     if ev is not None:
         e1.record()
         ev.append((e0, e1, M, N, K))

@@ -33,6 +33,16 @@
 // (1024 x 1024 at patch 16 is 4 097 tokens, Mammo-CLIP's 1520 x 912 is 5 416): one workgroup per block of 256 queries
 // of a head, each streaming all of the head's key tiles.  At T = 4 097 attention is half of the tower's flops; PyTorch's
 // fp32 SDPA (its memory-efficient kernel) ran the same shapes at 0.56-0.60 of the fp32 MFMA peak, K9L at 0.68-0.71.
+//
+// K9C (mcd_vit_attention_cls): attention for ONE query row per image -- the class token of the last encoder block, the
+// only row of that block anything downstream reads (concept_vit/data_utils.py, cls_tail_route).  2 * 64 flops per 512
+// bytes of K and V: a streaming kernel, bound by reading every K and V head row once (2 * B * T * H * 256 bytes), not
+// by the matrix pipe.  No MFMA, no LDS staging: a 16-lane DPP row holds one 256-byte head row (float4 per lane), so one
+// wave instruction reads four whole rows; the 64-term dot product is 4 fmas per lane and 4 DPP adds inside the row.
+// Each 16-lane row keeps its own online-softmax stream (running max, sum and a float4 of the output) over the key rows
+// it sees, AC_U loads of K and of V in flight per wave; the 4 (T <= 512) or 16 streams of an (image, head) pair meet
+// once, through 4 KB of LDS.  q, k and v come with their own row / image strides: the [B, T, 2, H, 64] output of a
+// K|V-only projection and a plain [B, T, 3, H, 64] qkv are both addressed in place.
 #include "mcd_common.h"
 
 namespace {
@@ -236,6 +246,115 @@ __global__ __launch_bounds__(576, 4) void vit_attention_long_kernel(const float*
     attn_block(qkv, T, H, grp / H, grp % H, (pair - grp * nqb) * 32 * ncw, ncw, out);
 }
 
+// ---- K9C ----------------------------------------------------------------------------------------------------------------
+constexpr int AC_WAVES = 4;        // waves per workgroup
+constexpr int AC_U = 4;            // four-row loads of K (and of V) in flight per wave
+constexpr int AC_SPLIT_T = 512;    // longer sequences: the four waves of a workgroup share one (image, head) pair
+constexpr int AC_MAX_T = 32768;
+
+// x + (x of the lane that the DPP control pairs this one with, inside its 16-lane row)
+template <int CTRL>
+__device__ __forceinline__ float ac_dpp_add(float x) {
+    return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, true));
+}
+
+// The sum over the 16 lanes of a DPP row, in every lane of it: lane ^ 1, lane ^ 2 (quad_perm), then the other quad of the
+// half row (row_half_mirror) and the other half (row_mirror) -- after each step the lanes it pairs hold equal sums.
+__device__ __forceinline__ float ac_row_sum(float x) {
+    x = ac_dpp_add<0xB1>(x);
+    x = ac_dpp_add<0x4E>(x);
+    x = ac_dpp_add<0x141>(x);
+    return ac_dpp_add<0x140>(x);
+}
+
+// One workgroup = AC_WAVES waves; S of them (1 or 4) share an (image, head) pair.  Key row j of a pair belongs to wave
+// slice (j / 4) % S, lane row j % 4; lane `sub` of a row holds floats 4 sub .. 4 sub + 3 of the 64.
+__global__ __launch_bounds__(64 * AC_WAVES) void vit_attention_cls_kernel(
+    const float* __restrict__ q, int64_t q_img, const float* __restrict__ k, int64_t k_row, int64_t k_img,
+    const float* __restrict__ v, int64_t v_row, int64_t v_img, int T, int H, int64_t npairs, int S, float* __restrict__ out) {
+    __shared__ float4 st_acc[AC_WAVES * 4][16];
+    __shared__ float st_m[AC_WAVES * 4], st_l[AC_WAVES * 4];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int sub = lane & 15, g = lane >> 4;
+    const int64_t pair = (int64_t)blockIdx.x * (AC_WAVES / S) + wave / S;   // b * H + h
+    const int slice = wave % S;
+    const bool live = pair < npairs;
+
+    // a finite floor instead of -inf: a stream that has seen no key yet (T < 4 S: it never will) keeps alpha = 2^0 = 1
+    float m = -1e30f, l = 0.f;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (live) {
+        const int64_t b = pair / H;
+        const int h = (int)(pair - b * H);
+        const float qs = 0.125f * 1.44269504088896340736f;   // scores in the log2 domain, like K9
+        float4 qv = *reinterpret_cast<const float4*>(q + b * q_img + (int64_t)h * AT_D + 4 * sub);
+        qv.x *= qs; qv.y *= qs; qv.z *= qs; qv.w *= qs;
+        const int r0 = slice * 4 + g;
+        const float* kp = k + b * k_img + (int64_t)r0 * k_row + (int64_t)h * AT_D + 4 * sub;
+        const float* vp = v + b * v_img + (int64_t)r0 * v_row + (int64_t)h * AT_D + 4 * sub;
+        const int64_t kstep = (int64_t)4 * S * k_row, vstep = (int64_t)4 * S * v_row;
+        for (int rb = slice * 4; rb < T; rb += 4 * S * AC_U) {
+            float4 kk[AC_U], vv[AC_U];
+            bool ok[AC_U];
+#pragma unroll
+            for (int u = 0; u < AC_U; ++u) {
+                ok[u] = rb + u * 4 * S + g < T;
+                kk[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                vv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (ok[u]) {
+                    kk[u] = *reinterpret_cast<const float4*>(kp + u * kstep);
+                    vv[u] = *reinterpret_cast<const float4*>(vp + u * vstep);
+                }
+            }
+            kp += AC_U * kstep;
+            vp += AC_U * vstep;
+            float s[AC_U];
+            float mt = m;
+#pragma unroll
+            for (int u = 0; u < AC_U; ++u) {
+                const float d = fmaf(kk[u].w, qv.w, fmaf(kk[u].z, qv.z, fmaf(kk[u].y, qv.y, kk[u].x * qv.x)));
+                const float r = ac_row_sum(d);     // in every lane: the DPP adds read their row's other lanes
+                s[u] = ok[u] ? r : -INFINITY;      // a row past T gets p = 0
+                mt = fmaxf(mt, s[u]);
+            }
+            const float alpha = __builtin_amdgcn_exp2f(m - mt);
+            m = mt;
+            l *= alpha;
+            acc.x *= alpha; acc.y *= alpha; acc.z *= alpha; acc.w *= alpha;
+#pragma unroll
+            for (int u = 0; u < AC_U; ++u) {
+                const float p = __builtin_amdgcn_exp2f(s[u] - mt);
+                l += p;
+                acc.x = fmaf(p, vv[u].x, acc.x);
+                acc.y = fmaf(p, vv[u].y, acc.y);
+                acc.z = fmaf(p, vv[u].z, acc.z);
+                acc.w = fmaf(p, vv[u].w, acc.w);
+            }
+        }
+    }
+    st_acc[wave * 4 + g][sub] = acc;
+    if (sub == 0) {
+        st_m[wave * 4 + g] = m;
+        st_l[wave * 4 + g] = l;
+    }
+    __syncthreads();
+    if (live && slice == 0) {
+        // this pair's 4 S streams are those of waves wave .. wave + S - 1; lane d of the slice-0 wave finishes float d
+        const int s0 = wave * 4, ns = 4 * S;
+        float mx = st_m[s0];
+        for (int i = 1; i < ns; ++i) mx = fmaxf(mx, st_m[s0 + i]);   // finite: key 0 is in stream s0
+        float num = 0.f, den = 0.f;
+        const float* accf = reinterpret_cast<const float*>(&st_acc[s0][0]);
+        for (int i = 0; i < ns; ++i) {
+            const float w = __builtin_amdgcn_exp2f(st_m[s0 + i] - mx);
+            num = fmaf(accf[i * 64 + lane], w, num);
+            den = fmaf(st_l[s0 + i], w, den);
+        }
+        out[pair * AT_D + lane] = num / den;
+    }
+}
+
 }  // namespace
 
 extern "C" int mcd_vit_attention(const float* qkv, int64_t B, int64_t T, int64_t H, float* out, mcd_stream_t stream) {
@@ -278,5 +397,31 @@ extern "C" int mcd_vit_attention_long(const float* qkv, int64_t B, int64_t T, in
     hipLaunchKernelGGL(vit_attention_long_kernel, dim3((unsigned)(8 * per_xcd)), dim3(64 * (unsigned)(ncw + 1)), 0,
                        (hipStream_t)stream, qkv, (int)T, (int)H, (int)nqb, (int)npairs, (int)per_xcd, out);
     MCD_LAUNCH_CHECK("vit_attention_long_kernel");
+    return MCD_OK;
+}
+
+extern "C" int mcd_vit_attention_cls(const float* q, int64_t q_img, const float* k, int64_t k_row, int64_t k_img,
+                                     const float* v, int64_t v_row, int64_t v_img, int64_t B, int64_t T, int64_t H,
+                                     float* out, mcd_stream_t stream) {
+    MCD_REQUIRE(q && k && v && out, MCD_E_ARG, "mcd_vit_attention_cls: NULL pointer");
+    MCD_REQUIRE(B >= 0 && T >= 1 && H >= 1, MCD_E_ARG, "mcd_vit_attention_cls: bad shape B=%lld T=%lld H=%lld", (long long)B,
+                (long long)T, (long long)H);
+    MCD_REQUIRE(T <= AC_MAX_T, MCD_E_UNSUPPORTED, "mcd_vit_attention_cls: T=%lld tokens, at most %d", (long long)T, AC_MAX_T);
+    MCD_REQUIRE(H <= 65535 && B <= INT32_MAX / 65535, MCD_E_UNSUPPORTED,
+                "mcd_vit_attention_cls: H must be <= 65535 and B * 65535 < 2^31");
+    const int64_t W = H * AT_D;
+    MCD_REQUIRE(q_img >= W && k_row >= W && v_row >= W && k_img >= W && v_img >= W, MCD_E_ARG,
+                "mcd_vit_attention_cls: a stride (q_img=%lld k_row=%lld k_img=%lld v_row=%lld v_img=%lld) is below H*64=%lld",
+                (long long)q_img, (long long)k_row, (long long)k_img, (long long)v_row, (long long)v_img, (long long)W);
+    MCD_REQUIRE(((uintptr_t)q) % 16 == 0 && ((uintptr_t)k) % 16 == 0 && ((uintptr_t)v) % 16 == 0 && ((uintptr_t)out) % 16 == 0 &&
+                    q_img % 4 == 0 && k_row % 4 == 0 && k_img % 4 == 0 && v_row % 4 == 0 && v_img % 4 == 0,
+                MCD_E_ARG, "mcd_vit_attention_cls: pointers must be 16-byte aligned and strides multiples of 4 floats");
+    if (B == 0) return MCD_OK;
+    const int S = T > AC_SPLIT_T ? AC_WAVES : 1;
+    const int64_t npairs = B * H;
+    const int64_t nwg = mcd_cdiv(npairs, (int64_t)(AC_WAVES / S));
+    hipLaunchKernelGGL(vit_attention_cls_kernel, dim3((unsigned)nwg), dim3(64 * AC_WAVES), 0, (hipStream_t)stream, q, q_img, k,
+                       k_row, k_img, v, v_row, v_img, (int)T, (int)H, npairs, S, out);
+    MCD_LAUNCH_CHECK("vit_attention_cls_kernel");
     return MCD_OK;
 }

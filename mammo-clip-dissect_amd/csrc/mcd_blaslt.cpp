@@ -200,16 +200,19 @@ int linear_residual(const float* h, int64_t ldh, const float* W, int64_t ldw, co
         if (n <= 0) return fail(MCD_E_UNSUPPORTED, "mcd_linear_residual: hipBLASLt offers no algorithm for %lld x %lld x %lld",
                                 (long long)M, (long long)N, (long long)K);
         // a forced pick (mcd_linear_residual_set_pick) or MCD_BLASLT_PICK=heuristic: nothing is timed
+        // A pick is recorded per (M, N, K, has_res), the heuristic's list also depends on the leading dimensions: the same
+        // shape called on packed rows and on rows strided out of a larger tensor may get two lists.  An index forced for
+        // one that is past the other's list, or names a candidate it cannot run, falls back to the first usable one.
         int forced = -1;
         {
+            auto usable = [&](int i) { return cand[i].state == HIPBLAS_STATUS_SUCCESS && cand[i].workspaceSize <= max_ws; };
+            int first = 0;
+            for (int i = 0; i < n; ++i)
+                if (usable(i)) { first = i; break; }
             auto f = g_forced.find(ShapeKey{M, N, K, flags});
-            if (f != g_forced.end()) forced = f->second < n ? f->second : 0;
+            if (f != g_forced.end()) forced = (f->second < n && usable(f->second)) ? f->second : first;
             else if (const char* e = getenv("MCD_BLASLT_PICK")) {
-                if (e[0] == 'h') {
-                    forced = 0;
-                    for (int i = 0; i < n; ++i)
-                        if (cand[i].state == HIPBLAS_STATUS_SUCCESS && cand[i].workspaceSize <= max_ws) { forced = i; break; }
-                }
+                if (e[0] == 'h') forced = first;
             }
         }
         // time the candidates into a scratch D (the caller's out must be written exactly once)

@@ -216,6 +216,8 @@ class Dissector:
             n = self.ops.hook_pool(output.detach(), self.pool_mode, self.At, self.cursor, col0, True)
             if n != width:
                 raise RuntimeError("layer %s produced %d neurons, expected %d" % (self.layer_names[layer_index], n, width))
+        # of a 3-D [B, T, D] output hook_pool takes token 0: a ViT tower may hand this hook [B, 1, D] (data_utils.cls_tail_route)
+        _hook.token0_only = True
         return _hook
 
     def add_image_features(self, feats):
