@@ -405,6 +405,23 @@ int mcd_bn_relu_maxpool_nhwc(const float* x, int64_t B, int64_t H, int64_t W, in
 int mcd_conv_igemm_nhwc(const float* x, int64_t B, int64_t H, int64_t W, int64_t Cin, const float* w, const float* bias,
                         int64_t Cout, int k, int stride, int relu_in, int relu_out, float* y, mcd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * K18 with a residual operand in its epilogue: everything of mcd_conv_igemm_nhwc (shapes, layouts, alignment, size limits
+ *      and return codes), and res NHWC [B, Ho, Wo, Cout], contiguous and 16-byte aligned:
+ *        y = act_out( (bias + sum over (tap, cin) of w * act_in(x)) + res )
+ *      The order per output element is fixed: (1) K18's chunked sum as above, (2) + bias, (3) + res, (4) the ReLU when
+ *      relu_out is set.  The ReLU acts on the whole sum: a residual that drives it negative gives 0.  res must not
+ *      overlap y (MCD_E_ARG).  res == NULL means no residual: the call is mcd_conv_igemm_nhwc, bit for bit; and
+ *      mcd_conv_igemm_nhwc returns the bits it returned before this entry existed.  The residual is the 16-byte NHWC
+ *      piece a lane stores, one float4 load per store under the store's guards; nothing else of the kernel changes, so
+ *      an image's bits still depend neither on its batch nor on its place in it.
+ * replaces  BasicBlock.conv2 + bn2 + (+= identity) + relu of the torchvision ResNet-18 / -34 (and resnet18_places)
+ *                                                                 concept_vit/data_utils.py:70-89
+ * ------------------------------------------------------------------------------------------- */
+int mcd_conv_igemm_res_nhwc(const float* x, int64_t B, int64_t H, int64_t W, int64_t Cin, const float* w,
+                            const float* bias, const float* res, int64_t Cout, int k, int stride, int relu_in,
+                            int relu_out, float* y, mcd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

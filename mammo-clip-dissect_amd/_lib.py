@@ -50,6 +50,7 @@ SIGNATURES = {
     "mcd_conv7x7s2_nhwc": (_int, [_p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p]),
     "mcd_bn_relu_maxpool_nhwc": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
     "mcd_conv_igemm_nhwc": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _i64, _int, _int, _int, _int, _p, _p]),
+    "mcd_conv_igemm_res_nhwc": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _int, _int, _int, _int, _p, _p]),
 }
 
 MCD_E_ARG = -1

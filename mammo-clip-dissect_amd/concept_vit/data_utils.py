@@ -13,7 +13,9 @@ dissection core they feed is the HIP library.
     breastclip_vit         image_encoder.encoder.layer[0..11]          ViT-B/16: 12 x 768
     breastclip_classifier  image_encoder._blocks[0..38]                + linear head (n_class)
     clip                   vision_model.encoder.layers[0..11]          CLIP ViT-B/16: 12 x 768
-    resnet50               conv1, layer1..layer4                       64/256/512/1024/2048
+    resnet50 / 101 / 152   conv1, layer1..layer4                       64/256/512/1024/2048
+    resnet18 / 34          conv1, layer1..layer4                       64/64/128/256/512
+    resnet18_places        as resnet18, 365 classes (reference :70-79)
 """
 import math
 import os
@@ -53,9 +55,11 @@ HIP_LAYER_NORM = os.environ.get("MCD_NO_HIP_LAYER_NORM", "0") != "1"
 # rest.  MCD_NO_HIP_MBCONV=1 (or setting this to False) keeps the ATen route: MIOpen convolutions, ATen batch norm,
 # SiLU, mean, sigmoid-multiply and add -- the tests' reference and the other side of the timing A/B.
 HIP_MBCONV = os.environ.get("MCD_NO_HIP_MBCONV", "0") != "1"
-# The ResNet-50 target's inference route on channels-last activations with folded batch norm (core.conv7x7s2_nhwc,
-# bn_relu_maxpool_nhwc, conv_igemm_nhwc: K16-K18, and the 1x1 convolutions as hipBLASLt GEMMs with the skip add and the
-# ReLU in their epilogue).  MCD_NO_HIP_RESNET=1 restores the ATen NCHW route everywhere.
+# The ResNet targets' inference route on channels-last activations with folded batch norm (core.conv7x7s2_nhwc,
+# bn_relu_maxpool_nhwc, conv_igemm_nhwc: K16-K18).  Bottleneck networks (50 / 101 / 152): the 1x1 convolutions are
+# hipBLASLt GEMMs with the skip add and the ReLU in their epilogue.  BasicBlock networks (18 / 34 / resnet18_places):
+# every convolution is K18, the skip add and the ReLU in its epilogue -- no library GEMM in front of a hooked output.
+# MCD_NO_HIP_RESNET=1 restores the ATen NCHW route everywhere.
 HIP_RESNET = os.environ.get("MCD_NO_HIP_RESNET", "0") != "1"
 MAX_BATCH = 65535      # the images of one call that the K12-K18 entries accept
 
@@ -662,20 +666,24 @@ class ClipViT(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------------
-# ResNet-50 (torchvision layout: conv1, bn1, layer1..4, fc)
+# ResNet-18 / 34 / 50 / 101 / 152 (torchvision layout: conv1, bn1, layer1..4, fc)
 # ------------------------------------------------------------------------------------------------------
 _BOTTLENECK_SKIPPED = ("conv1", "bn1", "conv2", "bn2", "conv3", "bn3", "downsample")
+_BASICBLOCK_SKIPPED = ("conv1", "bn1", "conv2", "bn2", "downsample")
 _RESNET_SKIPPED = ("bn1",)
 
 
 def resnet_route(module, x):
-    """'hip' when the ResNet-50 target (a ResNet50 or its stem convolution, with the NCHW-contiguous input image) or one
-    of its blocks (a _Bottleneck with a channels_last-contiguous input) can take the HIP route: HIP_RESNET on, a CUDA fp32
-    tensor, inference (no autograd, eval mode), libmcd_blaslt.so loaded, widths K16-K18 take (stem: Cin <= 4, Cout a
-    multiple of 4, 7x7 / 2 / pad 3; block: every width a multiple of 32, stride 1 or 2), one image's tensors under 2^31
-    bytes, at most 65535 images, and no hook on a submodule the route does not call (a hook on layer2[0].conv2 must fire,
-    so that block takes ATen; the hook points of the tower itself -- conv1 and layer1..4 -- are called as modules on
-    either route).  'aten' otherwise."""
+    """'hip' when a ResNet target (a ResNet or its stem convolution, with the NCHW-contiguous input image) or one of its
+    blocks (a _Bottleneck or a _BasicBlock with a channels_last-contiguous input) can take the HIP route: HIP_RESNET on,
+    a CUDA fp32 tensor, inference (no autograd, eval mode), libmcd_blaslt.so loaded, widths K16-K18 take (stem: Cin <= 4,
+    Cout a multiple of 4, 7x7 / 2 / pad 3; block: every width a multiple of 32, stride 1 or 2), one image's tensors under
+    2^31 bytes, at most 65535 images, and no hook on a submodule the route does not call (a hook on layer2[0].conv2 must
+    fire, so that block takes ATen; the hook points of the tower itself -- conv1 and layer1..4 -- are called as modules
+    on either route).  'aten' otherwise.
+    A _BasicBlock calls no library GEMM, but it asks for libmcd_blaslt.so like everything else (_tower_gate): one gate
+    for the whole family, so a tower never runs half of its stages on each route for want of a library.  Its stride-1
+    block with cin != width (a 1x1 / 1 downsample, which K18 does not do and torchvision does not build) takes ATen."""
     if not _tower_gate(HIP_RESNET, module, x):
         return "aten"
     B, C, H, W = x.shape
@@ -688,8 +696,15 @@ def resnet_route(module, x):
               and _under_2g(max(cin, width) * H * W, cout * core.conv_out(H, 3, s, 1) * core.conv_out(W, 3, s, 1),
                             9 * width * width))
         names = _BOTTLENECK_SKIPPED                     # "downsample" covers the convolution and the batch norm in it
-    elif isinstance(module, (ResNet50, _StemConv)):
-        stem = module.conv1 if isinstance(module, ResNet50) else module
+    elif isinstance(module, _BasicBlock):
+        cin, width, s = module.conv1.in_channels, module.conv2.out_channels, module.stride
+        ok = (C == cin and not (cin % 32 or width % 32) and s in (1, 2) and (s == 2 or cin == width)
+              and core.channels_last(x) and not x.data_ptr() % 16
+              and _under_2g(cin * H * W, width * core.conv_out(H, 3, s, 1) * core.conv_out(W, 3, s, 1),
+                            9 * max(cin, width) * width))
+        names = _BASICBLOCK_SKIPPED
+    elif isinstance(module, (ResNet, _StemConv)):
+        stem = module.conv1 if isinstance(module, ResNet) else module
         ho, wo = core.conv_out(H, 7, 2, 3), core.conv_out(W, 7, 2, 3)
         ok = (C == stem.in_channels and C <= 4 and not stem.out_channels % 4 and stem.kernel_size == (7, 7)
               and stem.stride == (2, 2) and stem.padding == (3, 3) and stem.dilation == (1, 1) and stem.groups == 1
@@ -705,7 +720,7 @@ def resnet_route(module, x):
 
 
 class _StemConv(nn.Conv2d):
-    """ResNet-50's conv1.  On the HIP route K16 computes it and the result comes back as a [B, Cout, Ho, Wo] view of
+    """A ResNet's conv1.  On the HIP route K16 computes it and the result comes back as a [B, Cout, Ho, Wo] view of
     channels-last memory; it is still called as a module, so a hook on conv1 sees the raw convolution output."""
 
     def forward(self, x):
@@ -716,6 +731,8 @@ class _StemConv(nn.Conv2d):
 
 
 class _Bottleneck(nn.Module):
+    expansion = 4                                    # output channels / width
+
     def __init__(self, cin, width, stride):
         super().__init__()
         cout = width * 4
@@ -769,6 +786,52 @@ class _Bottleneck(nn.Module):
         return f
 
 
+class _BasicBlock(nn.Module):
+    """torchvision's BasicBlock (ResNet-18 / -34): conv3x3 -> bn -> relu -> conv3x3 -> bn -> (+ skip) -> relu; the output
+    has `width` channels."""
+    expansion = 1                                    # output channels / width
+
+    def __init__(self, cin, width, stride):
+        super().__init__()
+        self.stride = stride
+        self.conv1 = nn.Conv2d(cin, width, 3, stride, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(width)
+        self.conv2 = nn.Conv2d(width, width, 3, 1, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(width)
+        self.downsample = None
+        if stride != 1 or cin != width:
+            self.downsample = nn.Sequential(nn.Conv2d(cin, width, 1, stride, bias=False), nn.BatchNorm2d(width))
+
+    def forward(self, x):
+        if resnet_route(self, x) == "hip":
+            return self._forward_hip(x)
+        y = F.relu(self.bn1(self.conv1(x)))
+        y = self.bn2(self.conv2(y))
+        return F.relu(y + (x if self.downsample is None else self.downsample(x)))
+
+    def _forward_hip(self, x):
+        """The block on channels-last activations, two K18 launches (three with a downsample) and nothing else: conv1
+        (3x3 / stride, folded bn1, ReLU on the way out), the skip (x itself, or K18 1x1 / 2 with the folded downsample
+        batch norm), conv2 (3x3 / 1, folded bn2) with the skip as K18's residual operand and the ReLU behind the add.  x
+        is left alone.  Returns [B, C, H, W] in channels_last memory."""
+        f = _folded(self, _BASICBLOCK_SKIPPED, _BasicBlock._fold)
+        xn = x.permute(0, 2, 3, 1)                                   # [B, H, W, cin], contiguous
+        h = core.conv_igemm_nhwc(xn, f["w1"], f["b1"], 3, self.stride, relu_out=True)
+        res = xn if self.downsample is None else core.conv_igemm_nhwc(xn, f["wd"], f["bd"], 1, 2)
+        return core.conv_igemm_nhwc(h, f["w2"], f["b2"], 3, 1, relu_out=True, res=res).permute(0, 3, 1, 2)
+
+    def _fold(self):
+        f = {}
+        w1, f["b1"] = fold_bn(self.conv1.weight, self.bn1)
+        f["w1"] = igemm_weight(w1)
+        w2, f["b2"] = fold_bn(self.conv2.weight, self.bn2)
+        f["w2"] = igemm_weight(w2)
+        if self.downsample is not None:
+            wd, f["bd"] = fold_bn(self.downsample[0].weight, self.downsample[1])
+            f["wd"] = igemm_weight(wd)
+        return f
+
+
 def igemm_weight(w):
     """K18's weight layout: [Cout, Cin, kh, kw] -> [Cout, kh*kw*Cin], tap-major then channel."""
     return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
@@ -788,17 +851,20 @@ class _Stage(nn.Sequential):
         return x
 
 
-class ResNet50(nn.Module):
-    def __init__(self, num_classes=1000):
+class ResNet(nn.Module):
+    """The torchvision ResNet of `block` (_BasicBlock or _Bottleneck) with layers[i] blocks of width 64 << i in
+    layer<i+1>; the stem, the stages, the pooling and fc are the same for every depth."""
+
+    def __init__(self, block, layers, num_classes=1000):
         super().__init__()
         self.conv1 = _StemConv(3, 64, 7, 2, 3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         cin = 64
-        for i, (w, n, s) in enumerate([(64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2)], 1):
+        for i, (w, n, s) in enumerate(zip((64, 128, 256, 512), layers, (1, 2, 2, 2)), 1):
             blocks = []
             for j in range(n):
-                blocks.append(_Bottleneck(cin, w, s if j == 0 else 1))
-                cin = w * 4
+                blocks.append(block(cin, w, s if j == 0 else 1))
+                cin = w * block.expansion
             setattr(self, "layer%d" % i, _Stage(*blocks))
         self.fc = nn.Linear(cin, num_classes)
 
@@ -824,6 +890,18 @@ class ResNet50(nn.Module):
     encode_image = forward  # describe_og_neurons.py calls encode_image on every target
 
 
+class ResNet50(ResNet):
+    def __init__(self, num_classes=1000):
+        super().__init__(_Bottleneck, [3, 4, 6, 3], num_classes)
+
+
+# name -> (block, layers, classes): the reference's torchvision targets and its Places365 ResNet-18 (data_utils.py:70-89)
+RESNETS = {"resnet18": (_BasicBlock, [2, 2, 2, 2], 1000), "resnet34": (_BasicBlock, [3, 4, 6, 3], 1000),
+           "resnet101": (_Bottleneck, [3, 4, 23, 3], 1000), "resnet152": (_Bottleneck, [3, 8, 36, 3], 1000),
+           "resnet18_places": (_BasicBlock, [2, 2, 2, 2], 365)}
+PLACES_CKPT = "data/resnet18_places365.pth.tar"      # where the reference keeps it, relative to the working directory
+
+
 # ------------------------------------------------------------------------------------------------------
 # factories
 # ------------------------------------------------------------------------------------------------------
@@ -836,6 +914,27 @@ def _load_local(model, ckpt):
         ckpt = torch.load(ckpt, map_location="cpu", weights_only=True)
     sd = ckpt["model"] if isinstance(ckpt, dict) and "model" in ckpt else ckpt
     model.load_state_dict(sd, strict=False)
+    return model
+
+
+def _load_places(model, ckpt):
+    """resnet18_places (reference data_utils.py:70-79): ckpt is None (the reference's relative PLACES_CKPT if that file
+    exists, else the seeded weights stay), a state dict, the reference's {'state_dict': {...}} container, or a LOCAL
+    path to either.  A leading 'module.' (DataParallel) is stripped from the keys and the load is strict, as the
+    reference's is.  Files are read with weights_only=True; one that cannot be read that way is an error, not a random
+    model."""
+    if ckpt is None:
+        if not os.path.isfile(PLACES_CKPT):
+            return model
+        ckpt = PLACES_CKPT
+    if isinstance(ckpt, str):
+        try:
+            ckpt = torch.load(ckpt, map_location="cpu", weights_only=True)
+        except Exception as e:
+            raise RuntimeError("resnet18_places: %r cannot be loaded with weights_only=True (%s: %s); re-save it as a "
+                               "plain {'state_dict': tensors} file" % (ckpt, type(e).__name__, e)) from e
+    sd = ckpt["state_dict"] if isinstance(ckpt, dict) and "state_dict" in ckpt else ckpt
+    model.load_state_dict({(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()})
     return model
 
 
@@ -865,10 +964,17 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
             model = ClipViT(image_size=image_size)
         elif target_name == "resnet50":
             model = ResNet50()
+        elif target_name in RESNETS:
+            block, layers, classes = RESNETS[target_name]
+            model = ResNet(block, layers, classes)
         else:
             raise ValueError("unknown target model %r (offline build: breastclip, breastclip_vit, "
-                             "breastclip_classifier, clip, resnet50)" % (target_name,))
-    _load_local(model, ckpt)
+                             "breastclip_classifier, clip, resnet18, resnet18_places, resnet34, resnet50, resnet101, "
+                             "resnet152)" % (target_name,))
+    if target_name == "resnet18_places":
+        _load_places(model, ckpt)
+    else:
+        _load_local(model, ckpt)
     _load_local(model, finetuned_ckpt)
     return model.to(device).eval(), None
 

@@ -614,7 +614,7 @@ def silu_avg_pool_nhwc(x):
     return out
 
 
-# ---- K16 - K18: the ResNet-50 target on channels-last activations (csrc/k_resnet.hip) ---------------------------
+# ---- K16 - K18: the ResNet targets on channels-last activations (csrc/k_resnet.hip) ---------------------------
 def conv_out(n, k, s, p):
     """Output size of one axis under ResNet's symmetric padding: (n + 2p - k) // s + 1."""
     return (n + 2 * p - k) // s + 1
@@ -657,10 +657,13 @@ def bn_relu_maxpool_nhwc(x, scale, shift):
 
 
 @_on_device
-def conv_igemm_nhwc(x, w_tap, bias, k, stride, relu_in=False, relu_out=False):
+def conv_igemm_nhwc(x, w_tap, bias, k, stride, relu_in=False, relu_out=False, res=None, out=None):
     """K18: implicit-GEMM convolution on the exact-fp32 MFMA: x NHWC [B, H, W, Cin], w_tap [Cout, k*k*Cin] (tap-major,
-    then channel), bias [Cout] -> NHWC [B, Ho, Wo, Cout] = act_out(bias + conv(act_in(x))), act = ReLU where the flag is
-    set.  k = 3 with stride 1 or 2 (pad 1), or k = 1 with stride 2 (pad 0); Cin and Cout multiples of 32."""
+    then channel), bias [Cout] -> NHWC [B, Ho, Wo, Cout] = act_out(bias + conv(act_in(x)) + res), act = ReLU where the
+    flag is set.  k = 3 with stride 1 or 2 (pad 1), or k = 1 with stride 2 (pad 0); Cin and Cout multiples of 32.
+    res: None, or a residual NHWC [B, Ho, Wo, Cout] added after the bias and before the ReLU (mcd_conv_igemm_res_nhwc;
+    None calls mcd_conv_igemm_nhwc, the same bits as before the keyword existed).  out: None (a new tensor), or the
+    tensor to write, of the output's shape; it must not share memory with res."""
     x = _nhwc(x, "x")
     B, H, W, Cin = x.shape
     if (k, stride) not in ((3, 1), (3, 2), (1, 2)):
@@ -675,11 +678,26 @@ def conv_igemm_nhwc(x, w_tap, bias, k, stride, relu_in=False, relu_out=False):
     _vec(bias, Cout, "bias")
     _aligned16("conv_igemm_nhwc: tensors must be 16-byte aligned", x, w_tap, bias)
     pad = 1 if k == 3 else 0
-    y = torch.empty((B, conv_out(H, k, stride, pad), conv_out(W, k, stride, pad), Cout), dtype=torch.float32,
-                    device=x.device)
+    shape = (B, conv_out(H, k, stride, pad), conv_out(W, k, stride, pad), Cout)
+    for t, name in ((res, "res"), (out, "out")):
+        if t is None:
+            continue
+        _nhwc(t, name)
+        if tuple(t.shape) != shape:
+            raise ValueError("conv_igemm_nhwc: %s must be %s, got %s" % (name, shape, tuple(t.shape)))
+        _aligned16("conv_igemm_nhwc: tensors must be 16-byte aligned", t)
+    y = torch.empty(shape, dtype=torch.float32, device=x.device) if out is None else out
     L = _lib.load()
-    check(L.mcd_conv_igemm_nhwc(x.data_ptr(), B, H, W, Cin, w_tap.data_ptr(), bias.data_ptr(), Cout, int(k), int(stride),
-                                1 if relu_in else 0, 1 if relu_out else 0, y.data_ptr(), _stream()))
+    if res is None:
+        check(L.mcd_conv_igemm_nhwc(x.data_ptr(), B, H, W, Cin, w_tap.data_ptr(), bias.data_ptr(), Cout, int(k),
+                                    int(stride), 1 if relu_in else 0, 1 if relu_out else 0, y.data_ptr(), _stream()))
+        return y
+    nbytes = y.numel() * 4
+    if res.data_ptr() < y.data_ptr() + nbytes and y.data_ptr() < res.data_ptr() + nbytes:
+        raise ValueError("conv_igemm_nhwc: res must not share memory with the output")
+    check(L.mcd_conv_igemm_res_nhwc(x.data_ptr(), B, H, W, Cin, w_tap.data_ptr(), bias.data_ptr(), res.data_ptr(), Cout,
+                                    int(k), int(stride), 1 if relu_in else 0, 1 if relu_out else 0, y.data_ptr(),
+                                    _stream()))
     return y
 
 

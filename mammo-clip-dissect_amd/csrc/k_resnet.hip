@@ -119,6 +119,11 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(const float* __res
 // sums are added to the total in ascending order, the bias last.  One chain over all of k = 4 608 (layer4) measured
 // 2.0e-6 of the output's maximum against float64, eight times ATen's error; the two-level sum keeps the rounding
 // error near sqrt(256) + sqrt(18) ulps instead of sqrt(4 608) and costs 64 additions per wave and chunk.
+// RES (mcd_conv_igemm_res_nhwc, a BasicBlock's conv2 + bn2 + skip + ReLU): a residual operand res [B, Ho, Wo, Cout] in the
+// epilogue, y = act_out((total + bias) + res).  It is the same 16-byte NHWC piece the store writes, so a lane loads one
+// float4 per store; a pixel tile's loads (4 * TC of them, under the stores' two guards) are issued together ahead of
+// the adds.  Without RES the kernel is the code it was: the main loop is shared and the epilogue's extra lines are
+// compiled out.
 constexpr int IG_BP = 128;
 constexpr int IG_BK = 32;
 constexpr int IG_LDP = IG_BP + 4;
@@ -126,11 +131,12 @@ constexpr int IG_CHUNK = 8;                        // k-steps (of 32) per partia
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-template <int BC, int KS>
+template <int BC, int KS, bool RES>
 __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const float* __restrict__ x, int H, int W, int Cin,
                                                           const float* __restrict__ wt, const float* __restrict__ bias,
-                                                          int Cout, int stride, int pad, int Ho, int Wo, int64_t Mtot,
-                                                          int nct, int relu_in, int relu_out, float* __restrict__ y) {
+                                                          const float* __restrict__ res, int Cout, int stride, int pad,
+                                                          int Ho, int Wo, int64_t Mtot, int nct, int relu_in,
+                                                          int relu_out, float* __restrict__ y) {
     constexpr int LDC = BC + 4;
     constexpr int TC = BC / 64;                     // accumulator tiles per wave along the channels
     constexpr int NW = BC / 64;                     // weight rows per thread and step
@@ -277,7 +283,19 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const float* __restr
         const int64_t m = m_base + wp * 64 + p * 32 + l31;
         if (m >= Mtot) continue;
         const int64_t b = m / HoWo;
-        float* yp = y + b * HoWo * Cout + (int)(m - b * HoWo) * Cout;
+        const int64_t poff = b * HoWo * Cout + (int)(m - b * HoWo) * Cout;     // the pixel's place in y, and in res
+        float* yp = y + poff;
+        float4 rq[RES ? TC : 1][4];
+        if constexpr (RES) {                        // the pixel tile's residual pieces, all in flight before the first add
+#pragma unroll
+            for (int a = 0; a < TC; ++a)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int n = c_base + wc * (BC / 2) + a * 32 + 8 * g + 4 * lh;
+                    rq[a][g] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (n < Cout) rq[a][g] = *reinterpret_cast<const float4*>(res + poff + n);
+                }
+        }
 #pragma unroll
         for (int a = 0; a < TC; ++a)
 #pragma unroll
@@ -287,6 +305,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const float* __restr
                 const float4 bq = *reinterpret_cast<const float4*>(bias + n);
                 float4 o = make_float4(tot[a][p][4 * g] + bq.x, tot[a][p][4 * g + 1] + bq.y, tot[a][p][4 * g + 2] + bq.z,
                                        tot[a][p][4 * g + 3] + bq.w);
+                if constexpr (RES) o = make_float4(o.x + rq[a][g].x, o.y + rq[a][g].y, o.z + rq[a][g].z, o.w + rq[a][g].w);
                 if (relu_out) o = relu4(o);
                 *reinterpret_cast<float4*>(yp + n) = o;
             }
@@ -298,15 +317,15 @@ inline unsigned grid_for(int64_t n, int64_t per_block, int64_t cap) {
     return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
-template <int BC, int KS>
+template <int BC, int KS, bool RES>
 int launch_igemm(const float* x, int64_t B, int64_t H, int64_t W, int64_t Cin, const float* wt, const float* bias,
-                 int64_t Cout, int stride, int pad, int64_t Ho, int64_t Wo, int relu_in, int relu_out, float* y,
-                 hipStream_t st) {
+                 const float* res, int64_t Cout, int stride, int pad, int64_t Ho, int64_t Wo, int relu_in, int relu_out,
+                 float* y, hipStream_t st) {
     static bool attr_done[MCD_MAX_DEVICES] = {};
     constexpr size_t lds = (size_t)2 * IG_BK * (IG_LDP + BC + 4) * sizeof(float);
     const int dev = mcd_cur_device();
     if (!attr_done[dev]) {
-        if (hipFuncSetAttribute((const void*)conv_igemm_kernel<BC, KS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute((const void*)conv_igemm_kernel<BC, KS, RES>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds) != hipSuccess)
             return mcd_fail(MCD_E_LAUNCH, "mcd_conv_igemm_nhwc: cannot reserve %zu bytes of LDS", lds);
         attr_done[dev] = true;
@@ -315,8 +334,8 @@ int launch_igemm(const float* x, int64_t B, int64_t H, int64_t W, int64_t Cin, c
     const int64_t nct = mcd_cdiv(Cout, BC), npt = mcd_cdiv(Mtot, IG_BP);
     MCD_REQUIRE(nct * npt < ((int64_t)1 << 31), MCD_E_UNSUPPORTED, "mcd_conv_igemm_nhwc: %lld tiles exceed the grid",
                 (long long)(nct * npt));
-    hipLaunchKernelGGL((conv_igemm_kernel<BC, KS>), dim3((unsigned)(nct * npt)), dim3(256), lds, st, x, (int)H, (int)W,
-                       (int)Cin, wt, bias, (int)Cout, stride, pad, (int)Ho, (int)Wo, Mtot, (int)nct, relu_in ? 1 : 0,
+    hipLaunchKernelGGL((conv_igemm_kernel<BC, KS, RES>), dim3((unsigned)(nct * npt)), dim3(256), lds, st, x, (int)H, (int)W,
+                       (int)Cin, wt, bias, res, (int)Cout, stride, pad, (int)Ho, (int)Wo, Mtot, (int)nct, relu_in ? 1 : 0,
                        relu_out ? 1 : 0, y);
     MCD_LAUNCH_CHECK("conv_igemm_kernel");
     return MCD_OK;
@@ -367,30 +386,58 @@ extern "C" int mcd_bn_relu_maxpool_nhwc(const float* x, int64_t B, int64_t H, in
     return MCD_OK;
 }
 
-extern "C" int mcd_conv_igemm_nhwc(const float* x, int64_t B, int64_t H, int64_t W, int64_t Cin, const float* w,
-                                   const float* bias, int64_t Cout, int k, int stride, int relu_in, int relu_out, float* y,
-                                   mcd_stream_t stream) {
-    MCD_REQUIRE(x && w && bias && y, MCD_E_ARG, "mcd_conv_igemm_nhwc: NULL pointer");
+namespace {
+
+// The checks and the dispatch of both K18 entries (`name` is the entry's, for the messages).  res == NULL: the
+// instantiations without a residual, whichever entry was called.
+int conv_igemm_entry(const char* name, const float* x, int64_t B, int64_t H, int64_t W, int64_t Cin, const float* w,
+                     const float* bias, const float* res, int64_t Cout, int k, int stride, int relu_in, int relu_out,
+                     float* y, mcd_stream_t stream) {
+    MCD_REQUIRE(x && w && bias && y, MCD_E_ARG, "%s: NULL pointer", name);
     MCD_REQUIRE(B >= 0 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1, MCD_E_ARG,
-                "mcd_conv_igemm_nhwc: bad shape B=%lld H=%lld W=%lld Cin=%lld Cout=%lld", (long long)B, (long long)H,
-                (long long)W, (long long)Cin, (long long)Cout);
+                "%s: bad shape B=%lld H=%lld W=%lld Cin=%lld Cout=%lld", name, (long long)B, (long long)H, (long long)W,
+                (long long)Cin, (long long)Cout);
     MCD_REQUIRE(((k == 3 && (stride == 1 || stride == 2)) || (k == 1 && stride == 2)) && Cin % 32 == 0 && Cout % 32 == 0,
-                MCD_E_UNSUPPORTED,
-                "mcd_conv_igemm_nhwc: k=%d stride=%d Cin=%lld Cout=%lld (3x3 / 1 or 2, 1x1 / 2; Cin, Cout %% 32 == 0)", k,
-                stride, (long long)Cin, (long long)Cout);
+                MCD_E_UNSUPPORTED, "%s: k=%d stride=%d Cin=%lld Cout=%lld (3x3 / 1 or 2, 1x1 / 2; Cin, Cout %% 32 == 0)",
+                name, k, stride, (long long)Cin, (long long)Cout);
     MCD_REQUIRE(((uintptr_t)x) % 16 == 0 && ((uintptr_t)w) % 16 == 0 && ((uintptr_t)bias) % 16 == 0 &&
-                    ((uintptr_t)y) % 16 == 0, MCD_E_ARG, "mcd_conv_igemm_nhwc: pointers must be 16-byte aligned");
+                    ((uintptr_t)y) % 16 == 0 && ((uintptr_t)res) % 16 == 0, MCD_E_ARG,
+                "%s: pointers must be 16-byte aligned", name);
     const int pad = k == 3 ? 1 : 0;
     const int64_t Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
     MCD_REQUIRE(H * W * Cin * 4 < kImageLimit && Ho * Wo * Cout * 4 < kImageLimit && (int64_t)k * k * Cin * Cout * 4 < kImageLimit &&
                     B <= 65535, MCD_E_UNSUPPORTED,
-                "mcd_conv_igemm_nhwc: one image's tensor (or the weight) reaches 2^31 bytes, or B > 65535");
+                "%s: one image's tensor (or the weight) reaches 2^31 bytes, or B > 65535", name);
+    if (res) {      // every workgroup reads its residual pieces before it stores, but another may have stored there already
+        const uintptr_t r0 = (uintptr_t)res, y0 = (uintptr_t)y, bytes = (uintptr_t)(B * Ho * Wo * Cout * 4);
+        MCD_REQUIRE(r0 != y0 && (r0 + bytes <= y0 || y0 + bytes <= r0), MCD_E_ARG, "%s: res overlaps y", name);
+    }
     if (B == 0) return MCD_OK;
     hipStream_t st = (hipStream_t)stream;
     const bool wide = Cout % 128 == 0;
-    if (k == 3)
-        return wide ? launch_igemm<128, 3>(x, B, H, W, Cin, w, bias, Cout, stride, pad, Ho, Wo, relu_in, relu_out, y, st)
-                    : launch_igemm<64, 3>(x, B, H, W, Cin, w, bias, Cout, stride, pad, Ho, Wo, relu_in, relu_out, y, st);
-    return wide ? launch_igemm<128, 1>(x, B, H, W, Cin, w, bias, Cout, stride, pad, Ho, Wo, relu_in, relu_out, y, st)
-                : launch_igemm<64, 1>(x, B, H, W, Cin, w, bias, Cout, stride, pad, Ho, Wo, relu_in, relu_out, y, st);
+#define MCD_IGEMM(BC, KS, RES) \
+    launch_igemm<BC, KS, RES>(x, B, H, W, Cin, w, bias, res, Cout, stride, pad, Ho, Wo, relu_in, relu_out, y, st)
+    if (res) {
+        if (k == 3) return wide ? MCD_IGEMM(128, 3, true) : MCD_IGEMM(64, 3, true);
+        return wide ? MCD_IGEMM(128, 1, true) : MCD_IGEMM(64, 1, true);
+    }
+    if (k == 3) return wide ? MCD_IGEMM(128, 3, false) : MCD_IGEMM(64, 3, false);
+    return wide ? MCD_IGEMM(128, 1, false) : MCD_IGEMM(64, 1, false);
+#undef MCD_IGEMM
+}
+
+}  // namespace
+
+extern "C" int mcd_conv_igemm_nhwc(const float* x, int64_t B, int64_t H, int64_t W, int64_t Cin, const float* w,
+                                   const float* bias, int64_t Cout, int k, int stride, int relu_in, int relu_out, float* y,
+                                   mcd_stream_t stream) {
+    return conv_igemm_entry("mcd_conv_igemm_nhwc", x, B, H, W, Cin, w, bias, nullptr, Cout, k, stride, relu_in, relu_out,
+                            y, stream);
+}
+
+extern "C" int mcd_conv_igemm_res_nhwc(const float* x, int64_t B, int64_t H, int64_t W, int64_t Cin, const float* w,
+                                       const float* bias, const float* res, int64_t Cout, int k, int stride, int relu_in,
+                                       int relu_out, float* y, mcd_stream_t stream) {
+    return conv_igemm_entry("mcd_conv_igemm_res_nhwc", x, B, H, W, Cin, w, bias, res, Cout, k, stride, relu_in, relu_out,
+                            y, stream);
 }

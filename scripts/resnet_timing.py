@@ -1,9 +1,13 @@
-"""The ResNet-50 target's HIP route (K16-K18, csrc/k_resnet.hip) measured.  Dev tool.
+"""The ResNet targets' HIP route (K16-K18, csrc/k_resnet.hip) measured.  Dev tool.
 
-  --kernels [B]   K16, K17 and K18 at every ResNet-50 shape of a 224 x 224 input (batch B, default 250): device events
-                  after a warm-up; flop, ms, TFLOP/s and the fraction of the fp32 peak (157.3 TFLOP/s, the MFMA's and the
-                  packed VALU's alike), and beside each convolution ATen's F.conv2d on the NCHW tensor (MIOpen, the route
-                  the kernel replaces) on the same device.
+  --target NAME   the network: resnet50 (default), resnet101, resnet152 (the same convolution shapes, other counts), or
+                  a BasicBlock one, resnet18 / resnet34 / resnet18_places (K18 alone, conv2 with the skip as its residual
+                  operand).  Applies to --kernels, --driver and --forwards.
+  --kernels [B]   K16, K17 and K18 at every shape the network has at a 224 x 224 input (batch B, default 250): device
+                  events after a warm-up; flop, ms, TFLOP/s and the fraction of the fp32 peak (157.3 TFLOP/s, the MFMA's
+                  and the packed VALU's alike), and beside each convolution ATen's F.conv2d alone on the NCHW tensor
+                  (MIOpen, the route the kernel replaces; its batch norm, ReLU and skip add are further kernels) on the
+                  same device.
   --driver [N]    describe_clip_neurons.main() on synthetic_<N>_224 (default 10000), batch --batch (default 250), conv1 +
                   layer1..4, after a warm-up run on 2 batches: prints one JSON line with images/s.  --keep DIR copies the
                   CSV there (for --compare).
@@ -30,6 +34,29 @@ CONVS = [("layer1 3x3", 64, 64, 56, 56, 3, 1, 3), ("layer2 3x3/2", 128, 128, 56,
          ("layer3 3x3", 256, 256, 14, 14, 3, 1, 5), ("layer4 3x3/2", 512, 512, 14, 14, 3, 2, 1),
          ("layer4 3x3", 512, 512, 7, 7, 3, 1, 2), ("layer2 ds 1x1/2", 256, 512, 56, 56, 1, 2, 1),
          ("layer3 ds 1x1/2", 512, 1024, 28, 28, 1, 2, 1), ("layer4 ds 1x1/2", 1024, 2048, 14, 14, 1, 2, 1)]
+DEPTHS = {"resnet18": [2, 2, 2, 2], "resnet34": [3, 4, 6, 3], "resnet18_places": [2, 2, 2, 2], "resnet50": [3, 4, 6, 3],
+          "resnet101": [3, 4, 23, 3], "resnet152": [3, 8, 36, 3]}
+BASIC = ("resnet18", "resnet34", "resnet18_places")
+
+
+def convs_of(target):
+    """(name, Cin, Cout, H, W, k, stride, count, res) for every distinct K18 call of the network at 224 x 224; res: the
+    call carries the skip as its residual operand (a BasicBlock's conv2)."""
+    n = DEPTHS[target]
+    if target not in BASIC:
+        per = {"layer%d 3x3" % (i + 1): n[i] - (1 if i else 0) for i in range(4)}
+        return [(c[0],) + c[1:7] + (per.get(c[0], 1), False) for c in CONVS]
+    out, hw = [], 56
+    for i, w in enumerate((64, 128, 256, 512)):
+        name = "layer%d" % (i + 1)
+        if i:
+            out.append((name + " conv1 3x3/2", w // 2, w, hw, hw, 3, 2, 1, False))
+            out.append((name + " ds 1x1/2", w // 2, w, hw, hw, 1, 2, 1, False))
+            hw //= 2
+        if n[i] - (1 if i else 0):
+            out.append((name + " conv1 3x3", w, w, hw, hw, 3, 1, n[i] - (1 if i else 0), False))
+        out.append((name + " conv2 3x3+res", w, w, hw, hw, 3, 1, n[i], True))
+    return out
 
 
 def arg_n(flag, default):
@@ -62,7 +89,7 @@ def timeit(fn, n=10):
     return s.elapsed_time(e) / n
 
 
-def kernels_child(B, which):
+def kernels_child(B, which, target):
     sys.path.insert(0, ROOT)
     import torch
     import torch.nn.functional as F
@@ -91,7 +118,7 @@ def kernels_child(B, which):
         print("B=%d %-16s %8.2f GB     %8.3f ms  %6.2f TB/s                       ATen %8.3f ms  ATen / HIP %.2f"
               % (B, "K17 bn+relu+pool", gb, ms, gb / ms, ms_a, ms_a / ms), flush=True)
         return
-    name, Cin, Cout, H, W, k, s, count = CONVS[int(which)]
+    name, Cin, Cout, H, W, k, s, count, with_res = convs_of(target)[int(which)]
     pad = 1 if k == 3 else 0
     Ho, Wo = (H + 2 * pad - k) // s + 1, (W + 2 * pad - k) // s + 1
     x = torch.randn(B, H, W, Cin, device=dev, generator=g)
@@ -99,13 +126,17 @@ def kernels_child(B, which):
     b = torch.randn(Cout, device=dev, generator=g)
     wt = w.permute(0, 2, 3, 1).reshape(Cout, -1).contiguous()
     relu = k == 3
-    ms = timeit(lambda: core.conv_igemm_nhwc(x, wt, b, k, s, relu_in=relu, relu_out=relu))
+    if target in BASIC:      # conv1: ReLU on the way out; conv2: the skip, then the ReLU; the downsample bare
+        res = torch.randn(B, Ho, Wo, Cout, device=dev, generator=g) if with_res else None
+        ms = timeit(lambda: core.conv_igemm_nhwc(x, wt, b, k, s, relu_out=relu, res=res))
+    else:
+        ms = timeit(lambda: core.conv_igemm_nhwc(x, wt, b, k, s, relu_in=relu, relu_out=relu))
     xn = x.permute(0, 3, 1, 2).contiguous()
     ms_a = timeit(lambda: F.conv2d(xn, w, None, s, pad))             # the convolution alone: bn and relu are extra kernels
     line("K18 %s (x%d)" % (name, count), 2.0 * B * Ho * Wo * Cout * k * k * Cin, ms, ms_a)
 
 
-def driver_child(n, batch, keep):
+def driver_child(n, batch, keep, target):
     sys.path.insert(0, ROOT)
     import torch
     import mammo_clip_dissect_amd as m
@@ -117,7 +148,7 @@ def driver_child(n, batch, keep):
         try:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            out = drv.main(["--target_model", "resnet50", "--target_layers", LAYERS, "--d_probe",
+            out = drv.main(["--target_model", target, "--target_layers", LAYERS, "--d_probe",
                             "synthetic_%d_224" % count, "--concept_set", concepts, "--batch_size", str(batch), "--device",
                             "cuda:0", "--activation_dir", tmp + "/acts", "--result_dir", tmp + "/results"])
             torch.cuda.synchronize()
@@ -127,17 +158,17 @@ def driver_child(n, batch, keep):
                 shutil.copy(os.path.join(out, "descriptions.csv"), os.path.join(keep, "descriptions_%s.csv" % route))
         finally:
             shutil.rmtree(tmp, ignore_errors=True)
-    print(json.dumps({"tool": "scripts/resnet_timing.py --driver", "route": route, "images": n, "batch": batch,
+    print(json.dumps({"tool": "scripts/resnet_timing.py --driver", "target": target, "route": route, "images": n, "batch": batch,
                       "layers": LAYERS, "seconds": round(dt, 3), "images_per_s": round(n / dt, 1)}), flush=True)
 
 
-def forwards_child(n):
+def forwards_child(n, target):
     sys.path.insert(0, ROOT)
     import torch
     import mammo_clip_dissect_amd  # noqa: F401
     from mammo_clip_dissect_amd.concept_vit import data_utils
     dev = torch.device("cuda:0")
-    net, _ = data_utils.get_target_model("resnet50", dev)
+    net, _ = data_utils.get_target_model(target, dev)
     x = torch.randn(250, 3, 224, 224, device=dev)
     with torch.no_grad():
         for _ in range(n):
@@ -159,19 +190,23 @@ def compare(a, b):
 
 
 if __name__ == "__main__":
+    target = opt("--target", "resnet50")
+    if target not in DEPTHS:
+        sys.exit("--target: one of %s" % ", ".join(sorted(DEPTHS)))
     if "--child-kernels" in sys.argv:
-        kernels_child(int(sys.argv[2]), sys.argv[3])
+        kernels_child(int(sys.argv[2]), sys.argv[3], target)
     elif "--child-driver" in sys.argv:
-        driver_child(int(sys.argv[2]), int(sys.argv[3]), sys.argv[4] if len(sys.argv) > 4 else None)
+        driver_child(int(sys.argv[2]), int(sys.argv[3]), opt("--keep", None), target)
     elif "--kernels" in sys.argv:
         B = arg_n("--kernels", 250)
-        for which in ["stem"] + [str(i) for i in range(len(CONVS))]:
-            child(["--child-kernels", str(B), which], 300)
+        for which in ["stem"] + [str(i) for i in range(len(convs_of(target)))]:
+            child(["--child-kernels", str(B), which, "--target", target], 300)
     elif "--driver" in sys.argv:
         keep = opt("--keep", None)
-        child(["--child-driver", str(arg_n("--driver", 10000)), opt("--batch", "250")] + ([keep] if keep else []), 900)
+        child(["--child-driver", str(arg_n("--driver", 10000)), opt("--batch", "250"), "--target", target]
+              + (["--keep", keep] if keep else []), 900)
     elif "--forwards" in sys.argv:
-        forwards_child(arg_n("--forwards", 4))
+        forwards_child(arg_n("--forwards", 4), target)
     elif "--compare" in sys.argv:
         i = sys.argv.index("--compare")
         compare(sys.argv[i + 1], sys.argv[i + 2])
