@@ -422,6 +422,43 @@ int mcd_conv_igemm_res_nhwc(const float* x, int64_t B, int64_t H, int64_t W, int
                             const float* bias, const float* res, int64_t Cout, int k, int stride, int relu_in,
                             int relu_out, float* y, mcd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * OpenAI-CLIP's anti-aliased ResNet (the RN50 / RN101 dissectors), inference route (K19-K21, with K18, K9C, K0n and the
+ * GEMMs of libmcd_blaslt.so): the rules of K16-K18 -- fp32, channels-last activations, folded batch norm, no atomics, no
+ * split reduction, one fixed order per output element (an image's bits depend neither on its batch nor on its place in
+ * it), one image's tensor of 2^31 bytes or more or B > 65535 is MCD_E_UNSUPPORTED; NULL, misaligned (16 bytes; K19's x:
+ * 4) or overlapping input / output pointers, C % 4 != 0 and Cin > 4 are MCD_E_ARG.  No entry reads the environment.
+ *
+ * K19  stem: x NCHW [B, Cin, H, W] (Cin <= 4) -> y NHWC [B, Ho, Wo, Cout] = act(conv3x3/2, pad 1 (x, w) + bias),
+ *      Ho = (H + 2 - 3) / 2 + 1; w tap-major [Cin, 3, 3, Cout] with the batch norm folded in, Cout % 4 == 0; act = ReLU
+ *      when relu != 0 (it keeps a NaN).  K16's design: a 16 x 16 output tile per workgroup, its 33 x 33 x Cin window in
+ *      LDS, weights through the scalar cache, 32 output channels per pass (4 when Cout % 32).  Per output element: one
+ *      fmaf chain from 0 over (channel, row, column), then + bias, then the ReLU.
+ * replaces  visual.conv1 + bn1 + relu of ModifiedResNet           concept_vit/clip/model.py:107-108, :136-138
+ * ------------------------------------------------------------------------------------------- */
+int mcd_conv3x3s2_nhwc(const float* x, int64_t B, int64_t Cin, int64_t H, int64_t W, const float* w, const float* bias,
+                       int64_t Cout, int relu, float* y, mcd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * K20  nn.AvgPool2d(2) on NHWC x [B, H, W, C] (C % 4 == 0) -> y [B, H/2, W/2, C] (floor: an odd trailing row or column
+ *      is dropped; H == 1 or W == 1 is an empty output: MCD_OK, nothing is written).  One thread per (output pixel,
+ *      channel quad).  y = (((x00 + x01) + x10) + x11) * 0.25f: bit-equal to F.avg_pool2d(x, 2) in either memory format.
+ * replaces  the stem's avgpool, a stride-2 Bottleneck's avgpool     concept_vit/clip/model.py:113, :139, :23, :45,
+ *           and downsample."-1"                                     :35
+ * ------------------------------------------------------------------------------------------- */
+int mcd_avgpool2_nhwc(const float* x, int64_t B, int64_t H, int64_t W, int64_t C, float* y, mcd_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * K21  the attention pool's token sequence: x NHWC [B, HW, C], pos [HW + 1, C] -> tok [B, HW + 1, C] (C % 4 == 0),
+ *        tok[b, 0, :] = mean_p x[b, p, :] + pos[0],    tok[b, 1 + p, :] = x[b, p, :] + pos[1 + p]
+ *      A thread owns a channel quad of one image.  The mean is one ascending sum over p, times 1/HW (computed once, in
+ *      fp32), the position row added last; rows 1.. are a single fp32 add (torch's bits).
+ * replaces  reshape / permute, cat(mean, x), + positional_embedding  concept_vit/clip/model.py:67-69
+ *           of AttentionPool2d.forward
+ * ------------------------------------------------------------------------------------------- */
+int mcd_attnpool_tokens(const float* x, int64_t B, int64_t HW, int64_t C, const float* pos, float* tok,
+                        mcd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

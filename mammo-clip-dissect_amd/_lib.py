@@ -51,6 +51,9 @@ SIGNATURES = {
     "mcd_bn_relu_maxpool_nhwc": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
     "mcd_conv_igemm_nhwc": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _i64, _int, _int, _int, _int, _p, _p]),
     "mcd_conv_igemm_res_nhwc": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _int, _int, _int, _int, _p, _p]),
+    "mcd_conv3x3s2_nhwc": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _i64, _int, _p, _p]),
+    "mcd_avgpool2_nhwc": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p]),
+    "mcd_attnpool_tokens": (_int, [_p, _i64, _i64, _i64, _p, _p, _p]),
 }
 
 MCD_E_ARG = -1

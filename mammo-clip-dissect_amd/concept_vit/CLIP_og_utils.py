@@ -16,7 +16,7 @@ PM_SUFFIX = _u.PM_SUFFIX
 
 def save_activations(clip_name, target_name, target_layers, d_probe,
                      concept_set, batch_size, device, pool_mode, save_dir):
-    clip_model, tokenize = _clip_dissector(device)
+    clip_model, tokenize = _clip_dissector(device, clip_name)
     target_model = clip_model if target_name == "clip" else data_utils.get_target_model(target_name, device)[0]
     data = _u._probe_data(d_probe, device)
     words = _u._read_concepts(concept_set)

@@ -16,6 +16,7 @@ dissection core they feed is the HIP library.
     resnet50 / 101 / 152   conv1, layer1..layer4                       64/256/512/1024/2048
     resnet18 / 34          conv1, layer1..layer4                       64/64/128/256/512
     resnet18_places        as resnet18, 365 classes (reference :70-79)
+    clip_rn50 / clip_rn101 visual.layer1..layer4, visual.attnpool      CLIP RN50 / RN101: 256/512/1024/2048, 1024 | 512
 """
 import math
 import os
@@ -61,6 +62,10 @@ HIP_MBCONV = os.environ.get("MCD_NO_HIP_MBCONV", "0") != "1"
 # every convolution is K18, the skip add and the ReLU in its epilogue -- no library GEMM in front of a hooked output.
 # MCD_NO_HIP_RESNET=1 restores the ATen NCHW route everywhere.
 HIP_RESNET = os.environ.get("MCD_NO_HIP_RESNET", "0") != "1"
+# The OpenAI-CLIP RN50 / RN101 dissectors' inference route (clip_rn_route): the anti-aliased stem on K19 + K18 + K20, the
+# blocks on GEMMs + K18 + K20 (the 2x2 average pooling that stands in for every stride), the attention pool on K21, two
+# GEMMs, K9C and c_proj.  MCD_NO_HIP_CLIP_RN=1 (or setting this to False) keeps the ATen route of the same modules.
+HIP_CLIP_RN = os.environ.get("MCD_NO_HIP_CLIP_RN", "0") != "1"
 MAX_BATCH = 65535      # the images of one call that the K12-K18 entries accept
 
 
@@ -903,6 +908,256 @@ PLACES_CKPT = "data/resnet18_places365.pth.tar"      # where the reference keeps
 
 
 # ------------------------------------------------------------------------------------------------------
+# OpenAI-CLIP RN50 / RN101 (the anti-aliased "ModifiedResNet" with an attention-pooling head; parameter names under
+# `visual.` follow OpenAI's layout so that a local CLIP state dict's visual.* keys load strictly)
+# ------------------------------------------------------------------------------------------------------
+_CLIP_BOTTLENECK_SKIPPED = ("conv1", "bn1", "conv2", "bn2", "avgpool", "conv3", "bn3", "downsample")
+_CLIP_STEM_SKIPPED = ("conv1", "bn1", "conv2", "bn2", "conv3", "bn3", "avgpool")
+_ATTNPOOL_SKIPPED = ("q_proj", "k_proj", "v_proj", "c_proj")
+
+
+def _plain_conv(conv, k, s, p):
+    """conv is the bias-free, ungrouped k x k / s convolution with pad p."""
+    return (conv.kernel_size == (k, k) and conv.stride == (s, s) and conv.padding == (p, p) and conv.dilation == (1, 1)
+            and conv.groups == 1 and conv.bias is None)
+
+
+def clip_rn_route(module, x):
+    """'hip' when a piece of the CLIP ResNet can take the HIP route: HIP_CLIP_RN on, a CUDA fp32 4-D tensor, inference (no
+    autograd, eval mode), libmcd_blaslt.so loaded, at most 65535 images, one image's tensors under 2^31 bytes, and no hook
+    on a submodule the route does not call (a hook on visual.layer2[0].conv2 must fire, so that block takes ATen; the hook
+    points visual.layer1..4 and visual.attnpool are called as modules on either route).  'aten' otherwise.
+      ModifiedResNet   its stem, on the NCHW-contiguous image: Cin <= 4, width a multiple of 64 (K18 takes multiples of
+                       32 and the stem's first two convolutions have width / 2 channels: the RN50x4 / x16 / x64 widths
+                       80, 96, 128 are out of scope and take ATen, 128 included, for one rule), at least 2 x 2 pixels
+                       in front of the pooling;
+      _ClipBottleneck  a channels_last-contiguous input, every width a multiple of 32, stride 1 or 2 (2: at least 2 x 2
+                       pixels);
+      AttentionPool2d  a channels_last-contiguous input of embed_dim = 64 * heads channels whose pixels + 1 are the rows
+                       of positional_embedding, within K9C's token limit, all four projections with a bias."""
+    if not _tower_gate(HIP_CLIP_RN, module, x):
+        return "aten"
+    B, C, H, W = x.shape
+    if H < 1 or W < 1:
+        return "aten"
+    if isinstance(module, _ClipBottleneck):
+        cin, width, cout, s = module.conv1.in_channels, module.conv2.in_channels, module.conv3.out_channels, module.stride
+        ok = (C == cin and not (cin % 32 or width % 32 or cout % 32) and s in (1, 2) and (s == 1 or (H >= 2 and W >= 2))
+              and core.channels_last(x) and not x.data_ptr() % 16
+              and _under_2g(max(cin, width) * H * W, cout * (H // s) * (W // s), 9 * width * width))
+        names = _CLIP_BOTTLENECK_SKIPPED               # "downsample" covers the pooling, the convolution and the batch norm
+    elif isinstance(module, AttentionPool2d):
+        E, T = module.embed_dim, H * W + 1
+        ok = (C == E and E == 64 * module.num_heads and T == module.positional_embedding.shape[0]
+              and T <= core.VIT_ATTENTION_CLS_MAX_T and core.channels_last(x) and not x.data_ptr() % 16
+              and all(getattr(module, n).bias is not None for n in _ATTNPOOL_SKIPPED) and _under_2g(T * 2 * E))
+        names = _ATTNPOOL_SKIPPED
+    elif isinstance(module, ModifiedResNet):
+        c1, c3 = module.conv1.out_channels, module.conv3.out_channels
+        ho, wo = core.conv_out(H, 3, 2, 1), core.conv_out(W, 3, 2, 1)
+        ok = (C == module.conv1.in_channels and C <= 4 and c3 % 64 == 0 and 2 * c1 == c3
+              and module.conv2.in_channels == c1 and module.conv2.out_channels == c1 and module.conv3.in_channels == c1
+              and _plain_conv(module.conv1, 3, 2, 1) and _plain_conv(module.conv2, 3, 1, 1)
+              and _plain_conv(module.conv3, 3, 1, 1) and ho >= 2 and wo >= 2 and x.is_contiguous()
+              and not x.data_ptr() % 16 and _under_2g(C * H * W, c3 * ho * wo))
+        names = _CLIP_STEM_SKIPPED
+    else:
+        return "aten"
+    return "hip" if ok and not _hooks_on(module, names) else "aten"
+
+
+class _ClipBottleneck(nn.Module):
+    """CLIP's anti-aliased Bottleneck: every convolution has stride 1; a block of stride s > 1 average-pools s x s behind
+    conv2 and, on the skip, in front of the 1x1 downsample convolution (downsample."-1")."""
+    expansion = 4
+
+    def __init__(self, cin, width, stride=1):
+        super().__init__()
+        cout = width * self.expansion
+        self.stride = stride
+        self.conv1 = nn.Conv2d(cin, width, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(width)
+        self.conv2 = nn.Conv2d(width, width, 3, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(width)
+        self.avgpool = nn.Identity() if stride == 1 else nn.AvgPool2d(stride, stride)     # no parameters: no keys
+        self.conv3 = nn.Conv2d(width, cout, 1, bias=False)
+        self.bn3 = nn.BatchNorm2d(cout)
+        self.downsample = None
+        if stride > 1 or cin != cout:
+            self.downsample = nn.Sequential()
+            self.downsample.add_module("-1", nn.AvgPool2d(stride))
+            self.downsample.add_module("0", nn.Conv2d(cin, cout, 1, bias=False))
+            self.downsample.add_module("1", nn.BatchNorm2d(cout))
+
+    def forward(self, x):
+        if clip_rn_route(self, x) == "hip":
+            return self._forward_hip(x)
+        y = F.relu(self.bn1(self.conv1(x)))
+        y = self.avgpool(F.relu(self.bn2(self.conv2(y))))
+        y = self.bn3(self.conv3(y))
+        return F.relu(y + (x if self.downsample is None else self.downsample(x)))
+
+    def _forward_hip(self, x):
+        """The block on channels-last activations: conv1 as a GEMM (raw, folded bn1 as its bias; its ReLU is K18's
+        relu_in), conv2 by K18 (3x3 / 1, folded bn2, ReLU on the way in and out); at stride 2, K20 on conv2's output and
+        on the block's input for the skip; the downsample as a GEMM on the (pooled) input with folded BN; conv3 as one
+        GEMM with folded bn3 as its bias, the skip as its residual operand and the ReLU as its epilogue.  x is left alone.
+        Returns [B, C, H, W] in channels_last memory."""
+        f = _folded(self, _CLIP_BOTTLENECK_SKIPPED, _ClipBottleneck._fold)
+        xn = x.permute(0, 2, 3, 1)                                   # [B, H, W, cin], contiguous
+        h = core.linear_residual(None, xn, f["w1"], f["b1"])
+        h = core.conv_igemm_nhwc(h, f["w2"], f["b2"], 3, 1, relu_in=True, relu_out=True)
+        if self.stride == 2:
+            h, xn = core.avgpool2_nhwc(h), core.avgpool2_nhwc(xn)
+        res = xn if self.downsample is None else core.linear_residual(None, xn, f["wd"], f["bd"])
+        return core.linear_residual(res, h, f["w3"], f["b3"], relu=True).permute(0, 3, 1, 2)
+
+    def _fold(self):
+        f = {}
+        w1, f["b1"] = fold_bn(self.conv1.weight, self.bn1)
+        f["w1"] = w1.flatten(1).contiguous()
+        w2, f["b2"] = fold_bn(self.conv2.weight, self.bn2)
+        f["w2"] = igemm_weight(w2)
+        w3, f["b3"] = fold_bn(self.conv3.weight, self.bn3)
+        f["w3"] = w3.flatten(1).contiguous()
+        if self.downsample is not None:
+            wd, f["bd"] = fold_bn(self.downsample[1].weight, self.downsample[2])      # children: "-1", "0", "1"
+            f["wd"] = wd.flatten(1).contiguous()
+        return f
+
+
+class AttentionPool2d(nn.Module):
+    """CLIP's pooling head: the pixels of [B, C, H, W] become H*W tokens, their mean is put in front as the query token,
+    a position embedding is added, and one multi-head attention (separate q / k / v projections, output projection
+    c_proj) is read at the query token: [B, output_dim]."""
+
+    def __init__(self, side, embed_dim, num_heads, output_dim=None):
+        """side: pixels along one edge of the pooled map (side * side + 1 position rows).  The parameters are registered
+        in the order of OpenAI's state dict: positional_embedding, k_proj, q_proj, v_proj, c_proj."""
+        super().__init__()
+        tokens = side * side + 1
+        self.positional_embedding = nn.Parameter(torch.empty(tokens, embed_dim).normal_(std=embed_dim ** -0.5))
+        for name in ("k_proj", "q_proj", "v_proj"):
+            setattr(self, name, nn.Linear(embed_dim, embed_dim))
+        self.c_proj = nn.Linear(embed_dim, embed_dim if output_dim is None else output_dim)
+        self.embed_dim, self.num_heads = embed_dim, num_heads
+
+    def forward(self, x):
+        if clip_rn_route(self, x) == "hip":
+            return self._forward_hip(x)
+        B, C = x.shape[:2]
+        t = x.flatten(2).transpose(1, 2)                             # [B, HW, C]
+        t = torch.cat([t.mean(dim=1, keepdim=True), t], dim=1) + self.positional_embedding.to(t.dtype)
+        T, hd = t.shape[1], C // self.num_heads
+        # only the query token's output is read: its row of the attention is all that is computed
+        q = self.q_proj(t[:, :1]).view(B, 1, self.num_heads, hd).transpose(1, 2)
+        k = self.k_proj(t).view(B, T, self.num_heads, hd).transpose(1, 2)
+        v = self.v_proj(t).view(B, T, self.num_heads, hd).transpose(1, 2)
+        o = F.scaled_dot_product_attention(q, k, v)                  # softmax(q k^T / sqrt(hd)) v
+        return self.c_proj(o.transpose(1, 2).reshape(B, C))
+
+    def _forward_hip(self, x):
+        """K21 builds the tokens from the channels-last pixels; one GEMM of all B*T tokens against cat(k_proj, v_proj)
+        gives [B, T, 2, heads, 64]; q_proj runs on the query rows alone (a row-strided GEMM operand); K9C (its / 8 is the
+        q scaling at head width 64); c_proj."""
+        wkv, bkv = _folded(self, _ATTNPOOL_SKIPPED, AttentionPool2d._fold)
+        B = x.shape[0]
+        tok = core.attnpool_tokens(x.permute(0, 2, 3, 1), self.positional_embedding.detach())      # [B, T, C]
+        kv = core.linear_residual(None, tok, wkv, bkv).view(B, tok.shape[1], 2, self.num_heads, 64)
+        q = core.linear_residual(None, tok[:, 0], self.q_proj.weight, self.q_proj.bias)
+        o = core.vit_attention_cls(q, kv[:, :, 0], kv[:, :, 1])                                     # K9C
+        return core.linear_residual(None, o, self.c_proj.weight, self.c_proj.bias)
+
+    def _fold(self):
+        return (torch.cat([self.k_proj.weight.detach(), self.v_proj.weight.detach()]).contiguous(),
+                torch.cat([self.k_proj.bias.detach(), self.v_proj.bias.detach()]).contiguous())
+
+
+class ModifiedResNet(nn.Module):
+    """CLIP's ResNet: a stem of three 3x3 convolutions (the first of stride 2) and a 2x2 average pooling instead of
+    7x7 / 2 + max pooling, anti-aliased stride-2 blocks (_ClipBottleneck), and an attention pool instead of the mean.
+    Hook points: layer1..4 (4-D) and attnpool ([B, output_dim])."""
+
+    def __init__(self, layers, output_dim, heads, input_resolution=224, width=64):
+        super().__init__()
+        self.output_dim, self.input_resolution = output_dim, input_resolution
+        self.conv1 = nn.Conv2d(3, width // 2, 3, 2, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(width // 2)
+        self.conv2 = nn.Conv2d(width // 2, width // 2, 3, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(width // 2)
+        self.conv3 = nn.Conv2d(width // 2, width, 3, padding=1, bias=False)
+        self.bn3 = nn.BatchNorm2d(width)
+        self.avgpool = nn.AvgPool2d(2)
+        cin = width
+        for i, (n, s) in enumerate(zip(layers, (1, 2, 2, 2)), 1):
+            blocks = []
+            for j in range(n):
+                blocks.append(_ClipBottleneck(cin, width << (i - 1), s if j == 0 else 1))
+                cin = (width << (i - 1)) * _ClipBottleneck.expansion
+            setattr(self, "layer%d" % i, _Stage(*blocks))
+        self.attnpool = AttentionPool2d(input_resolution // 32, cin, heads, output_dim)
+
+    def forward(self, x):
+        x = x.to(self.conv1.weight.dtype)
+        if clip_rn_route(self, x) == "hip":
+            x = self._stem_hip(x)
+        else:
+            x = self.stem(x)
+            if _tower_gate(HIP_CLIP_RN, self, x):                    # a hooked stem took ATen: the blocks need not
+                x = x.contiguous(memory_format=torch.channels_last)
+        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))     # _Stage keeps the memory channels-last
+        return self.attnpool(x)
+
+    def stem(self, x):
+        x = F.relu(self.bn1(self.conv1(x)))
+        x = F.relu(self.bn2(self.conv2(x)))
+        return self.avgpool(F.relu(self.bn3(self.conv3(x))))
+
+    def _stem_hip(self, x):
+        """K19 (conv1 + folded bn1 + ReLU, NCHW image -> channels-last), K18 twice (conv2, conv3: 3x3 / 1, folded BN,
+        ReLU on the way out), K20.  Returns [B, width, H/4, W/4] in channels_last memory."""
+        f = _folded(self, _CLIP_STEM_SKIPPED, ModifiedResNet._fold_stem)
+        h = core.conv3x3s2_nhwc(x, f["w1"], f["b1"], relu=True)
+        h = core.conv_igemm_nhwc(h, f["w2"], f["b2"], 3, 1, relu_out=True)
+        h = core.conv_igemm_nhwc(h, f["w3"], f["b3"], 3, 1, relu_out=True)
+        return core.avgpool2_nhwc(h).permute(0, 3, 1, 2)
+
+    def _fold_stem(self):
+        w1, b1 = fold_bn(self.conv1.weight, self.bn1)
+        w2, b2 = fold_bn(self.conv2.weight, self.bn2)
+        w3, b3 = fold_bn(self.conv3.weight, self.bn3)
+        return {"w1": w1.permute(1, 2, 3, 0).contiguous(), "b1": b1.contiguous(),      # tap-major [Cin, 3, 3, Cout]
+                "w2": igemm_weight(w2), "b2": b2.contiguous(), "w3": igemm_weight(w3), "b3": b3.contiguous()}
+
+
+class ClipResNet(nn.Module):
+    """OpenAI-CLIP RN50 / RN101 shaped dissector/target: hook points visual.layer1..4 and visual.attnpool; the text side
+    as ClipViT's (width 512, 8 heads), projected to the image tower's embed_dim."""
+
+    def __init__(self, layers, embed_dim, image_size=224, width=64, text_depth=12):
+        super().__init__()
+        self.embed_dim = embed_dim
+        self.visual = ModifiedResNet(layers, embed_dim, width * 32 // 64, image_size, width)
+        self.text_model = TextTower(vocab=49408, dim=512, heads=8, mlp=2048, depth=text_depth, max_pos=77)
+        self.text_projection = nn.Linear(512, embed_dim, bias=False)
+
+    def encode_image(self, image):
+        return self.visual(image)
+
+    def encode_text(self, tokens):
+        f = self.text_model(tokens)
+        eos = tokens["attention_mask"].sum(dim=-1) - 1
+        return self.text_projection(f[torch.arange(f.shape[0], device=f.device), eos])
+
+    def forward(self, image):
+        return self.encode_image(image)
+
+
+# name -> (layers, embed_dim): reference concept_vit/clip/model.py:258-266 with OpenAI's RN50 / RN101 configurations
+CLIP_RESNETS = {"clip_rn50": ((3, 4, 6, 3), 1024), "clip_rn101": ((3, 4, 23, 3), 512)}
+
+
+# ------------------------------------------------------------------------------------------------------
 # factories
 # ------------------------------------------------------------------------------------------------------
 def _load_local(model, ckpt):
@@ -967,10 +1222,16 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
         elif target_name in RESNETS:
             block, layers, classes = RESNETS[target_name]
             model = ResNet(block, layers, classes)
+        elif target_name in CLIP_RESNETS:
+            if not isinstance(image_size, int):
+                raise ValueError("%s: image_size must be an int (the attention pool is square), got %r"
+                                 % (target_name, image_size))
+            layers, embed = CLIP_RESNETS[target_name]
+            model = ClipResNet(layers, embed, image_size=image_size)
         else:
             raise ValueError("unknown target model %r (offline build: breastclip, breastclip_vit, "
-                             "breastclip_classifier, clip, resnet18, resnet18_places, resnet34, resnet50, resnet101, "
-                             "resnet152)" % (target_name,))
+                             "breastclip_classifier, clip, clip_rn50, clip_rn101, resnet18, resnet18_places, resnet34, "
+                             "resnet50, resnet101, resnet152)" % (target_name,))
     if target_name == "resnet18_places":
         _load_places(model, ckpt)
     else:

@@ -3,7 +3,8 @@
 Kept contracts (reference og_utils.py): get_activation :31-56, get_save_names :58-66,
 save_activations :374-471, get_similarity_from_activations :474-518 (no `top_k` argument: the similarity
 function runs with its own default, as in the reference).  The CLIP dissector is the offline ClipViT of
-data_utils (reference: clip.load(clip_name), a URL download); text goes through the same offline tokenizer.
+data_utils, or its ClipResNet for --clip_model RN50 / RN101 (reference: clip.load(clip_name), a URL download); text
+goes through the same offline tokenizer.
 """
 import torch
 
@@ -23,8 +24,14 @@ def save_prefix(target_name, d_probe, breast_clip_ckh=None, fine_tuned_ckh=None)
     return "/clip_dissector_{}_target_{}_small_not_mammo_pretrained_".format(target_name, d_probe)
 
 
-def _clip_dissector(device):
-    model, _ = data_utils.get_target_model("clip", device)
+# --clip_model names that have a dissector of their own; every other name keeps the ViT-B/16-shaped ClipViT
+CLIP_DISSECTORS = {"RN50": "clip_rn50", "RN101": "clip_rn101"}
+
+
+def _clip_dissector(device, clip_name="ViT-B/16"):
+    """(dissector, tokenize) for --clip_model `clip_name` (reference: clip.load(clip_name)): ClipResNet for RN50 /
+    RN101, ClipViT otherwise."""
+    model, _ = data_utils.get_target_model(CLIP_DISSECTORS.get(clip_name, "clip"), device)
     tok = data_utils.HashTokenizer()
     return model, (lambda texts: tok(texts, max_length=77))
 
@@ -33,7 +40,7 @@ def save_activations(clip_name, target_name, target_layers, d_probe,
                      concept_set, batch_size, device, pool_mode, save_dir, breast_clip_ckh=None, fine_tuned_ckh=None,
                      args=None):
     """reference og_utils.py:374-471.  Returns the Extraction left on the device (None when every cache file existed)."""
-    clip_model, tokenize = _clip_dissector(device)
+    clip_model, tokenize = _clip_dissector(device, clip_name)
     if target_name == "clip":
         target_model = clip_model
         encode_target = target_model                      # reference :464-469 -> target_model(images), :127

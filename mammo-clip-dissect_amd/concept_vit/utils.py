@@ -260,7 +260,8 @@ def extract_and_save(clip_model, target_model, encode_target, target_layers, dat
         layers = [resolve_layer(target_model, l) for l in target_layers]
         widths = _layer_widths(target_model, layers, first, encode_target)
         same = target_model is clip_model
-        dis = Dissector(N, list(target_layers), widths, len(words), data_utils.PROJ_DIM, device,
+        # the embedding width is the text features' (512 for the ViT-shaped dissectors, 1024 for CLIP RN50)
+        dis = Dissector(N, list(target_layers), widths, len(words), E_txt.shape[1], device,
                         pool_mode=pool_mode, gather=gather)
         handles = [m.register_forward_hook(dis.hook(i)) for i, m in enumerate(layers)] if need_target else []
         try:

@@ -701,6 +701,66 @@ def conv_igemm_nhwc(x, w_tap, bias, k, stride, relu_in=False, relu_out=False, re
     return y
 
 
+# ---- K19 - K21: OpenAI-CLIP's anti-aliased ResNet (csrc/k_clip_rn.hip) -------------------------------------------
+@_on_device
+def conv3x3s2_nhwc(x, w_tap, bias, relu=False):
+    """K19: the anti-aliased stem's first convolution, conv3x3/2, pad 1, + bias (+ ReLU): x NCHW [B, Cin, H, W]
+    (Cin <= 4), w_tap [Cin, 3, 3, Cout] (the folded weight, tap-major, Cout % 4 == 0), bias [Cout] -> NHWC
+    [B, Ho, Wo, Cout]."""
+    B, Cin, H, W = _nchw_image(x, "conv3x3s2_nhwc: x must be a contiguous float32 [B, Cin, H, W] tensor").shape
+    if w_tap.dim() != 4 or tuple(w_tap.shape[:3]) != (Cin, 3, 3) or Cin > 4 or w_tap.shape[3] % 4:
+        raise ValueError("conv3x3s2_nhwc: w_tap must be [Cin, 3, 3, Cout] with Cin = %d <= 4 and Cout %% 4 == 0, got %s"
+                         % (Cin, tuple(w_tap.shape)))
+    if H < 1 or W < 1:
+        raise ValueError("conv3x3s2_nhwc: empty image")
+    Cout = w_tap.shape[3]
+    _vec(w_tap, Cin * 9 * Cout, "w_tap")
+    _vec(bias, Cout, "bias")
+    _aligned16("conv3x3s2_nhwc: w_tap and bias must be 16-byte aligned", w_tap, bias)
+    y = torch.empty((B, conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1), Cout), dtype=torch.float32, device=x.device)
+    L = _lib.load()
+    check(L.mcd_conv3x3s2_nhwc(x.data_ptr(), B, Cin, H, W, w_tap.data_ptr(), bias.data_ptr(), Cout, 1 if relu else 0,
+                               y.data_ptr(), _stream()))
+    return y
+
+
+@_on_device
+def avgpool2_nhwc(x):
+    """K20: nn.AvgPool2d(2) on NHWC [B, H, W, C] (C % 4 == 0) -> [B, H // 2, W // 2, C], the bits of F.avg_pool2d(x, 2).
+    An odd trailing row or column is dropped; H == 1 or W == 1 gives the empty output torch gives."""
+    x = _nhwc(x, "x")
+    B, H, W, C = x.shape
+    if C % 4 or H < 1 or W < 1:
+        raise ValueError("avgpool2_nhwc: C = %d must be a multiple of 4 and the image non-empty" % C)
+    _aligned16("avgpool2_nhwc: x must be 16-byte aligned", x)
+    y = torch.empty((B, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
+    if y.numel() == 0:          # nothing to write (and an empty tensor has no address to hand to the entry)
+        return y
+    L = _lib.load()
+    check(L.mcd_avgpool2_nhwc(x.data_ptr(), B, H, W, C, y.data_ptr(), _stream()))
+    return y
+
+
+@_on_device
+def attnpool_tokens(x, pos):
+    """K21: the attention pool's tokens: x NHWC [B, H, W, C] or [B, HW, C], pos [HW + 1, C] -> [B, HW + 1, C] with
+    row 0 = the mean over the pixels + pos[0] and row 1 + p = x[:, p] + pos[1 + p].  C % 4 == 0."""
+    _need_gpu(x, pos)
+    if x.dtype != torch.float32 or x.dim() not in (3, 4) or not x.is_contiguous():
+        raise TypeError("attnpool_tokens: x must be a contiguous float32 [B, H, W, C] or [B, HW, C] tensor")
+    B, C = x.shape[0], x.shape[-1]
+    HW = x.shape[1] if x.dim() == 3 else x.shape[1] * x.shape[2]
+    if C % 4 or HW < 1:
+        raise ValueError("attnpool_tokens: C = %d must be a multiple of 4 and the image non-empty" % C)
+    if pos.dtype != torch.float32 or tuple(pos.shape) != (HW + 1, C) or not pos.is_contiguous():
+        raise TypeError("attnpool_tokens: pos must be a contiguous float32 [%d, %d] tensor" % (HW + 1, C))
+    _aligned16("attnpool_tokens: x and pos must be 16-byte aligned", x, pos)
+    tok = torch.empty((B, HW + 1, C), dtype=torch.float32, device=x.device)
+    L = _lib.load()
+    check(L.mcd_attnpool_tokens(x.data_ptr(), B, HW, C, pos.data_ptr(), tok.data_ptr(), _stream()))
+    return tok
+
+
 # ---- encoder-side linear + bias + residual on hipBLASLt (libmcd_blaslt.so) ------------------------
 _blaslt_ws = {}
 # bench.py sets this to a list to time the library GEMMs inside the forwards: every call then appends
