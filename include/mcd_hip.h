@@ -374,7 +374,7 @@ int mcd_hook_pool_nhwc(const float* x, int64_t B, int64_t C, int64_t HW, int mod
  *
  * K16  stem, raw: x NCHW [B, Cin, H, W] (Cin <= 4) -> y NHWC [B, Ho, Wo, Cout] = conv7x7/2, pad 3 (x, w); no bias, no
  *      batch norm, no ReLU (conv1 is a hook point: the hook sees the convolution's own output).  w tap-major
- *      [Cin, 7, 7, Cout], Cout % 4 == 0.
+ *      [Cin, 7, 7, Cout], Cout % 4 == 0.  An x or a w that overlaps y is MCD_E_ARG.
  * replaces  conv1 of the torchvision ResNet-50                    concept_vit/data_utils.py:85-93
  * ------------------------------------------------------------------------------------------- */
 int mcd_conv7x7s2_nhwc(const float* x, int64_t B, int64_t Cin, int64_t H, int64_t W, const float* w, int64_t Cout,
@@ -431,7 +431,7 @@ int mcd_conv_igemm_res_nhwc(const float* x, int64_t B, int64_t H, int64_t W, int
  *
  * K19  stem: x NCHW [B, Cin, H, W] (Cin <= 4) -> y NHWC [B, Ho, Wo, Cout] = act(conv3x3/2, pad 1 (x, w) + bias),
  *      Ho = (H + 2 - 3) / 2 + 1; w tap-major [Cin, 3, 3, Cout] with the batch norm folded in, Cout % 4 == 0; act = ReLU
- *      when relu != 0 (it keeps a NaN).  K16's design: a 16 x 16 output tile per workgroup, its 33 x 33 x Cin window in
+ *      when relu != 0 (it keeps a NaN).  K16's kernel: a 16 x 16 output tile per workgroup, its 33 x 33 x Cin window in
  *      LDS, weights through the scalar cache, 32 output channels per pass (4 when Cout % 32).  Per output element: one
  *      fmaf chain from 0 over (channel, row, column), then + bias, then the ReLU.
  * replaces  visual.conv1 + bn1 + relu of ModifiedResNet           concept_vit/clip/model.py:107-108, :136-138

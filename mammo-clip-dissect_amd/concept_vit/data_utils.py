@@ -355,6 +355,23 @@ def fold_bn(weight, bn):
     return w.to(weight.dtype), shift.to(weight.dtype)
 
 
+def igemm_weight(w):
+    """K18's weight layout: [Cout, Cin, kh, kw] -> [Cout, kh*kw*Cin], tap-major then channel."""
+    return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
+
+
+_FOLD_LAYOUTS = {"gemm": lambda w: w.flatten(1),                     # [Cout, Cin] of a 1x1: a GEMM's weight
+                 "igemm": igemm_weight,                              # K18
+                 "tap": lambda w: w.permute(1, 2, 3, 0)}             # [Cin, kh, kw, Cout]: the image stems (K12, K19)
+
+
+def _fold_conv(conv, bn, layout):
+    """(w, b) of the bias-free convolution `conv` with the batch norm `bn` behind it folded in (fold_bn), the weight in
+    the layout its kernel reads ("gemm", "igemm" or "tap"), both contiguous."""
+    w, b = fold_bn(conv.weight, bn)
+    return _FOLD_LAYOUTS[layout](w).contiguous(), b.contiguous()
+
+
 def _folded(module, names, build, own=False, extra=()):
     """build(module) -> the tensors derived from the module's weights (folded, relaid), computed once and cached in the
     module's __dict__ (no parameter or buffer is registered: state_dict() and the module tree stay as they are).  The
@@ -470,8 +487,7 @@ class _MBConv(nn.Module):
     def _fold(self):
         f = {}
         if self.expand:
-            w0, f["b0"] = fold_bn(self._expand_conv.weight, self._bn0)
-            f["w0"] = w0.view(self.mid, self.cin).contiguous()
+            f["w0"], f["b0"] = _fold_conv(self._expand_conv, self._bn0, "gemm")
         wd, f["bd"] = fold_bn(self._depthwise_conv.weight, self._bn1)
         f["wd"] = wd.view(self.mid, self.k * self.k).t().contiguous()          # tap-major [k*k, mid]
         sq = self._se_reduce.out_channels
@@ -479,8 +495,7 @@ class _MBConv(nn.Module):
         f["br"] = self._se_reduce.bias.detach().contiguous()
         f["we"] = self._se_expand.weight.detach().reshape(self.mid, sq).t().contiguous()       # transposed: [sq, mid]
         f["be"] = self._se_expand.bias.detach().contiguous()
-        wp, f["bp"] = fold_bn(self._project_conv.weight, self._bn2)
-        f["wp"] = wp.view(self.cout, self.mid).contiguous()
+        f["wp"], f["bp"] = _fold_conv(self._project_conv, self._bn2, "gemm")
         return f
 
 
@@ -536,10 +551,10 @@ class EfficientNetB5Tower(nn.Module):
         return core.silu_avg_pool_nhwc(core.linear_residual(None, xn, f["wh"], f["bh"]))
 
     def _fold(self):
-        ws, bs = fold_bn(self._conv_stem.weight, self._bn0)
-        wh, bh = fold_bn(self._conv_head.weight, self._bn1)
-        return {"ws": ws.permute(1, 2, 3, 0).contiguous(), "bs": bs.contiguous(),      # tap-major [Cin, 3, 3, Cout]
-                "wh": wh.view(self.out_dim, -1).contiguous(), "bh": bh.contiguous()}
+        f = {}
+        f["ws"], f["bs"] = _fold_conv(self._conv_stem, self._bn0, "tap")
+        f["wh"], f["bh"] = _fold_conv(self._conv_head, self._bn1, "gemm")
+        return f
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -678,6 +693,16 @@ _BASICBLOCK_SKIPPED = ("conv1", "bn1", "conv2", "bn2", "downsample")
 _RESNET_SKIPPED = ("bn1",)
 
 
+def _bottleneck_ok(module, x, out_hw):
+    """What resnet_route and clip_rn_route both ask of a Bottleneck (conv1 1x1, conv2 3x3, conv3 1x1, .stride) and its
+    input: the block's input channels, every width a multiple of 32, stride 1 or 2, channels_last memory at a 16-byte
+    address, and one image's widest input, its output (out_hw(stride) pixels) and conv2's weight under 2^31 bytes."""
+    B, C, H, W = x.shape
+    cin, width, cout, s = module.conv1.in_channels, module.conv2.in_channels, module.conv3.out_channels, module.stride
+    return (C == cin and not (cin % 32 or width % 32 or cout % 32) and s in (1, 2) and core.channels_last(x)
+            and not x.data_ptr() % 16 and _under_2g(max(cin, width) * H * W, cout * out_hw(s), 9 * width * width))
+
+
 def resnet_route(module, x):
     """'hip' when a ResNet target (a ResNet or its stem convolution, with the NCHW-contiguous input image) or one of its
     blocks (a _Bottleneck or a _BasicBlock with a channels_last-contiguous input) can take the HIP route: HIP_RESNET on,
@@ -695,11 +720,7 @@ def resnet_route(module, x):
     if H < 1 or W < 1:
         return "aten"
     if isinstance(module, _Bottleneck):
-        cin, width, cout, s = module.conv1.in_channels, module.conv2.in_channels, module.conv3.out_channels, module.stride
-        ok = (C == cin and not (cin % 32 or width % 32 or cout % 32) and s in (1, 2) and core.channels_last(x)
-              and not x.data_ptr() % 16
-              and _under_2g(max(cin, width) * H * W, cout * core.conv_out(H, 3, s, 1) * core.conv_out(W, 3, s, 1),
-                            9 * width * width))
+        ok = _bottleneck_ok(module, x, lambda s: core.conv_out(H, 3, s, 1) * core.conv_out(W, 3, s, 1))
         names = _BOTTLENECK_SKIPPED                     # "downsample" covers the convolution and the batch norm in it
     elif isinstance(module, _BasicBlock):
         cin, width, s = module.conv1.in_channels, module.conv2.out_channels, module.stride
@@ -779,15 +800,11 @@ class _Bottleneck(nn.Module):
 
     def _fold(self):
         f = {}
-        w1, f["b1"] = fold_bn(self.conv1.weight, self.bn1)
-        f["w1"] = w1.flatten(1).contiguous()
-        w2, f["b2"] = fold_bn(self.conv2.weight, self.bn2)
-        f["w2"] = igemm_weight(w2)
-        w3, f["b3"] = fold_bn(self.conv3.weight, self.bn3)
-        f["w3"] = w3.flatten(1).contiguous()
+        f["w1"], f["b1"] = _fold_conv(self.conv1, self.bn1, "gemm")
+        f["w2"], f["b2"] = _fold_conv(self.conv2, self.bn2, "igemm")
+        f["w3"], f["b3"] = _fold_conv(self.conv3, self.bn3, "gemm")
         if self.downsample is not None:
-            wd, f["bd"] = fold_bn(self.downsample[0].weight, self.downsample[1])
-            f["wd"] = igemm_weight(wd)                               # 1x1: [Cout, Cin] either way
+            f["wd"], f["bd"] = _fold_conv(self.downsample[0], self.downsample[1], "igemm")   # 1x1: [Cout, Cin] either way
         return f
 
 
@@ -827,19 +844,11 @@ class _BasicBlock(nn.Module):
 
     def _fold(self):
         f = {}
-        w1, f["b1"] = fold_bn(self.conv1.weight, self.bn1)
-        f["w1"] = igemm_weight(w1)
-        w2, f["b2"] = fold_bn(self.conv2.weight, self.bn2)
-        f["w2"] = igemm_weight(w2)
+        f["w1"], f["b1"] = _fold_conv(self.conv1, self.bn1, "igemm")
+        f["w2"], f["b2"] = _fold_conv(self.conv2, self.bn2, "igemm")
         if self.downsample is not None:
-            wd, f["bd"] = fold_bn(self.downsample[0].weight, self.downsample[1])
-            f["wd"] = igemm_weight(wd)
+            f["wd"], f["bd"] = _fold_conv(self.downsample[0], self.downsample[1], "igemm")
         return f
-
-
-def igemm_weight(w):
-    """K18's weight layout: [Cout, Cin, kh, kw] -> [Cout, kh*kw*Cin], tap-major then channel."""
-    return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
 
 
 class _Stage(nn.Sequential):
@@ -941,10 +950,7 @@ def clip_rn_route(module, x):
     if H < 1 or W < 1:
         return "aten"
     if isinstance(module, _ClipBottleneck):
-        cin, width, cout, s = module.conv1.in_channels, module.conv2.in_channels, module.conv3.out_channels, module.stride
-        ok = (C == cin and not (cin % 32 or width % 32 or cout % 32) and s in (1, 2) and (s == 1 or (H >= 2 and W >= 2))
-              and core.channels_last(x) and not x.data_ptr() % 16
-              and _under_2g(max(cin, width) * H * W, cout * (H // s) * (W // s), 9 * width * width))
+        ok = _bottleneck_ok(module, x, lambda s: (H // s) * (W // s)) and (module.stride == 1 or (H >= 2 and W >= 2))
         names = _CLIP_BOTTLENECK_SKIPPED               # "downsample" covers the pooling, the convolution and the batch norm
     elif isinstance(module, AttentionPool2d):
         E, T = module.embed_dim, H * W + 1
@@ -1014,15 +1020,11 @@ class _ClipBottleneck(nn.Module):
 
     def _fold(self):
         f = {}
-        w1, f["b1"] = fold_bn(self.conv1.weight, self.bn1)
-        f["w1"] = w1.flatten(1).contiguous()
-        w2, f["b2"] = fold_bn(self.conv2.weight, self.bn2)
-        f["w2"] = igemm_weight(w2)
-        w3, f["b3"] = fold_bn(self.conv3.weight, self.bn3)
-        f["w3"] = w3.flatten(1).contiguous()
+        f["w1"], f["b1"] = _fold_conv(self.conv1, self.bn1, "gemm")
+        f["w2"], f["b2"] = _fold_conv(self.conv2, self.bn2, "igemm")
+        f["w3"], f["b3"] = _fold_conv(self.conv3, self.bn3, "gemm")
         if self.downsample is not None:
-            wd, f["bd"] = fold_bn(self.downsample[1].weight, self.downsample[2])      # children: "-1", "0", "1"
-            f["wd"] = wd.flatten(1).contiguous()
+            f["wd"], f["bd"] = _fold_conv(self.downsample[1], self.downsample[2], "gemm")    # children: "-1", "0", "1"
         return f
 
 
@@ -1123,11 +1125,11 @@ class ModifiedResNet(nn.Module):
         return core.avgpool2_nhwc(h).permute(0, 3, 1, 2)
 
     def _fold_stem(self):
-        w1, b1 = fold_bn(self.conv1.weight, self.bn1)
-        w2, b2 = fold_bn(self.conv2.weight, self.bn2)
-        w3, b3 = fold_bn(self.conv3.weight, self.bn3)
-        return {"w1": w1.permute(1, 2, 3, 0).contiguous(), "b1": b1.contiguous(),      # tap-major [Cin, 3, 3, Cout]
-                "w2": igemm_weight(w2), "b2": b2.contiguous(), "w3": igemm_weight(w3), "b3": b3.contiguous()}
+        f = {}
+        f["w1"], f["b1"] = _fold_conv(self.conv1, self.bn1, "tap")
+        f["w2"], f["b2"] = _fold_conv(self.conv2, self.bn2, "igemm")
+        f["w3"], f["b3"] = _fold_conv(self.conv3, self.bn3, "igemm")
+        return f
 
 
 class ClipResNet(nn.Module):

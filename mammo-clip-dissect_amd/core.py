@@ -537,14 +537,31 @@ def dwconv_tiles(Ho, Wo):
     return -(-Ho // DWCONV_TILE) * -(-Wo // DWCONV_TILE)
 
 
+def _stem_args(name, x, w_tap, k, bias=None, strict=True):
+    """The arguments of an image stem (K12, K16, K19): x NCHW [B, Cin, H, W], w_tap [Cin, k, k, Cout] tap-major, bias
+    [Cout] or None.  Returns (B, Cin, H, W, Cout).  strict: refuse here, with a ValueError, a weight of another shape,
+    Cin > 4, Cout % 4, an empty image and a pointer that is not 16-byte aligned; K12 leaves those to its entry."""
+    B, Cin, H, W = _nchw_image(x, "%s: x must be a contiguous float32 [B, Cin, H, W] tensor" % name).shape
+    if strict:
+        if w_tap.dim() != 4 or tuple(w_tap.shape[:3]) != (Cin, k, k) or Cin > 4 or w_tap.shape[3] % 4:
+            raise ValueError("%s: w_tap must be [Cin, %d, %d, Cout] with Cin = %d <= 4 and Cout %% 4 == 0, got %s"
+                             % (name, k, k, Cin, tuple(w_tap.shape)))
+        if H < 1 or W < 1:
+            raise ValueError("%s: empty image" % name)
+    Cout = w_tap.shape[-1]
+    _vec(w_tap, Cin * k * k * Cout, "w_tap")
+    if bias is not None:
+        _vec(bias, Cout, "bias")
+    if strict:
+        _aligned16("%s: w_tap and bias must be 16-byte aligned" % name, *(t for t in (w_tap, bias) if t is not None))
+    return B, Cin, H, W, Cout
+
+
 @_on_device
 def conv_stem_nhwc(x, w_tap, bias):
     """K12: SiLU(conv3x3/2(x) + bias) with TF-SAME padding: x NCHW [B, Cin, H, W] (Cin <= 4), w_tap [Cin, 3, 3, Cout]
     (the folded weight, tap-major) -> NHWC [B, ceil(H/2), ceil(W/2), Cout]."""
-    B, Cin, H, W = _nchw_image(x, "conv_stem_nhwc: x must be a contiguous float32 [B, Cin, H, W] tensor").shape
-    Cout = w_tap.shape[-1]
-    _vec(w_tap, Cin * 9 * Cout, "w_tap")
-    _vec(bias, Cout, "bias")
+    B, Cin, H, W, Cout = _stem_args("conv_stem_nhwc", x, w_tap, 3, bias, strict=False)
     y = torch.empty((B, same_pad(H, 3, 2)[0], same_pad(W, 3, 2)[0], Cout), dtype=torch.float32, device=x.device)
     L = _lib.load()
     check(L.mcd_conv_stem_nhwc(x.data_ptr(), B, Cin, H, W, w_tap.data_ptr(), bias.data_ptr(), Cout, y.data_ptr(), _stream()))
@@ -624,15 +641,7 @@ def conv_out(n, k, s, p):
 def conv7x7s2_nhwc(x, w_tap):
     """K16: the raw stem convolution conv7x7/2, pad 3 (no bias, no batch norm, no ReLU): x NCHW [B, Cin, H, W]
     (Cin <= 4), w_tap [Cin, 7, 7, Cout] (tap-major, Cout % 4 == 0) -> NHWC [B, Ho, Wo, Cout]."""
-    B, Cin, H, W = _nchw_image(x, "conv7x7s2_nhwc: x must be a contiguous float32 [B, Cin, H, W] tensor").shape
-    if w_tap.dim() != 4 or tuple(w_tap.shape[:3]) != (Cin, 7, 7) or Cin > 4 or w_tap.shape[3] % 4:
-        raise ValueError("conv7x7s2_nhwc: w_tap must be [Cin, 7, 7, Cout] with Cin = %d <= 4 and Cout %% 4 == 0, got %s"
-                         % (Cin, tuple(w_tap.shape)))
-    if H < 1 or W < 1:
-        raise ValueError("conv7x7s2_nhwc: empty image")
-    Cout = w_tap.shape[3]
-    _vec(w_tap, Cin * 49 * Cout, "w_tap")
-    _aligned16("conv7x7s2_nhwc: w_tap must be 16-byte aligned", w_tap)
+    B, Cin, H, W, Cout = _stem_args("conv7x7s2_nhwc", x, w_tap, 7)
     y = torch.empty((B, conv_out(H, 7, 2, 3), conv_out(W, 7, 2, 3), Cout), dtype=torch.float32, device=x.device)
     L = _lib.load()
     check(L.mcd_conv7x7s2_nhwc(x.data_ptr(), B, Cin, H, W, w_tap.data_ptr(), Cout, y.data_ptr(), _stream()))
@@ -701,22 +710,13 @@ def conv_igemm_nhwc(x, w_tap, bias, k, stride, relu_in=False, relu_out=False, re
     return y
 
 
-# ---- K19 - K21: OpenAI-CLIP's anti-aliased ResNet (csrc/k_clip_rn.hip) -------------------------------------------
+# ---- K19 - K21: OpenAI-CLIP's anti-aliased ResNet (K19: csrc/k_resnet.hip; K20, K21: csrc/k_clip_rn.hip) --------
 @_on_device
 def conv3x3s2_nhwc(x, w_tap, bias, relu=False):
     """K19: the anti-aliased stem's first convolution, conv3x3/2, pad 1, + bias (+ ReLU): x NCHW [B, Cin, H, W]
     (Cin <= 4), w_tap [Cin, 3, 3, Cout] (the folded weight, tap-major, Cout % 4 == 0), bias [Cout] -> NHWC
     [B, Ho, Wo, Cout]."""
-    B, Cin, H, W = _nchw_image(x, "conv3x3s2_nhwc: x must be a contiguous float32 [B, Cin, H, W] tensor").shape
-    if w_tap.dim() != 4 or tuple(w_tap.shape[:3]) != (Cin, 3, 3) or Cin > 4 or w_tap.shape[3] % 4:
-        raise ValueError("conv3x3s2_nhwc: w_tap must be [Cin, 3, 3, Cout] with Cin = %d <= 4 and Cout %% 4 == 0, got %s"
-                         % (Cin, tuple(w_tap.shape)))
-    if H < 1 or W < 1:
-        raise ValueError("conv3x3s2_nhwc: empty image")
-    Cout = w_tap.shape[3]
-    _vec(w_tap, Cin * 9 * Cout, "w_tap")
-    _vec(bias, Cout, "bias")
-    _aligned16("conv3x3s2_nhwc: w_tap and bias must be 16-byte aligned", w_tap, bias)
+    B, Cin, H, W, Cout = _stem_args("conv3x3s2_nhwc", x, w_tap, 3, bias)
     y = torch.empty((B, conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1), Cout), dtype=torch.float32, device=x.device)
     L = _lib.load()
     check(L.mcd_conv3x3s2_nhwc(x.data_ptr(), B, Cin, H, W, w_tap.data_ptr(), bias.data_ptr(), Cout, 1 if relu else 0,

@@ -1,88 +1,16 @@
-// k_clip_rn.hip -- K19 / K20 / K21: the pieces of OpenAI-CLIP's anti-aliased ResNet (RN50 / RN101 dissectors) that the
-// ResNet kernels of k_resnet.hip do not cover: its 3x3 / 2 image stem, the 2x2 average pooling it uses in place of every
-// strided convolution and of the max pooling, and the token sequence of its attention-pooling head.  The 3x3 / 1
-// convolutions are K18, the 1x1 convolutions and the projections GEMMs on libmcd_blaslt.so, the attention itself K9C.
-//   replaces  ModifiedResNet's conv1 + bn1 + relu, avgpool, Bottleneck.avgpool / downsample."-1" and the first three
-//             lines of AttentionPool2d.forward                       concept_vit/clip/model.py:107-108, :113, :23, :35, :67-69
-// The rules of K16-K18: fp32, no atomics, no split reduction, one fixed order per output element (an image's bits depend
+// k_clip_rn.hip -- K20 / K21: the pieces of OpenAI-CLIP's anti-aliased ResNet (RN50 / RN101 dissectors) that the ResNet
+// kernels of k_resnet.hip do not cover: the 2x2 average pooling it uses in place of every strided convolution and of the
+// max pooling, and the token sequence of its attention-pooling head.  Its 3x3 / 2 image stem is K19, an instantiation of
+// the stem kernel in k_resnet.hip; the 3x3 / 1 convolutions are K18, the 1x1 convolutions and the projections GEMMs on
+// libmcd_blaslt.so, the attention itself K9C.
+//   replaces  ModifiedResNet's avgpool, Bottleneck.avgpool / downsample."-1" and the first three lines of
+//             AttentionPool2d.forward                                concept_vit/clip/model.py:113, :23, :35, :67-69
+// The rules of K16-K19: fp32, no atomics, no split reduction, one fixed order per output element (an image's bits depend
 // neither on the batch it is in nor on its place in it), an image addressed from a 64-bit base with 32-bit offsets inside
 // it (the entries refuse an image of 2^31 bytes or more), no environment variable read.
-#include "mcd_common.h"
+#include "k_nhwc.h"
 
 namespace {
-
-constexpr int64_t kImageLimit = (int64_t)1 << 31;   // bytes of one image's tensor
-
-__device__ __forceinline__ float relu1(float v) { return v < 0.f ? 0.f : v; }      // keeps a NaN, like ATen's
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p) % 16 == 0; }
-inline bool overlaps(const void* a, int64_t abytes, const void* b, int64_t bbytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
-}
-
-inline unsigned grid_for(int64_t n, int64_t per_block, int64_t cap) {
-    const int64_t g = mcd_cdiv(n, per_block);
-    return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
-// ---- K19: 3x3 / 2 stem, pad 1, folded batch norm, optional ReLU ---------------------------------------------------------
-// K16's design at another kernel size: a workgroup owns a 16 x 16 tile of output pixels of one image and stages its
-// 33 x 33 x Cin input window in LDS (zeros outside the image = the padding).  A thread owns one pixel and CO output
-// channels at a time (32, or 4 for a width that is no multiple of 32): the weight and bias indices depend on loop
-// counters only, so they come through the scalar cache and every LDS read feeds CO FMAs.  One fmaf chain from 0 over
-// (channel, row, column), then + bias, then the ReLU.
-constexpr int S3_TILE = 16;
-constexpr int S3_WIN = (S3_TILE - 1) * 2 + 3;      // 33
-
-template <int CO>                                  // 32 when Cout % 32 == 0, else 4
-__global__ __launch_bounds__(256) void conv3x3s2_kernel(const float* __restrict__ x, int Cin, int H, int W,
-                                                         const float* __restrict__ w, const float* __restrict__ bias,
-                                                         int Cout, int Ho, int Wo, int ntx, int relu,
-                                                         float* __restrict__ y) {
-    __shared__ float win[4 * S3_WIN * S3_WIN];
-    const int64_t b = blockIdx.y;
-    const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
-    const int iy0 = ty * S3_TILE * 2 - 1, ix0 = tx * S3_TILE * 2 - 1;
-    const float* xb = x + b * Cin * H * W;
-    for (int i = threadIdx.x; i < Cin * S3_WIN * S3_WIN; i += 256) {
-        const int ci = i / (S3_WIN * S3_WIN), r = i - ci * (S3_WIN * S3_WIN);
-        const int ly = r / S3_WIN, lx = r - ly * S3_WIN;
-        const int iy = iy0 + ly, ix = ix0 + lx;
-        win[i] = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? xb[(ci * H + iy) * W + ix] : 0.f;
-    }
-    __syncthreads();
-    const int py = threadIdx.x >> 4, px = threadIdx.x & 15;
-    const int oy = ty * S3_TILE + py, ox = tx * S3_TILE + px;
-    const bool live = oy < Ho && ox < Wo;
-    float* yp = y + b * Ho * Wo * Cout + (live ? (oy * Wo + ox) * Cout : 0);
-    for (int c0 = 0; c0 < Cout; c0 += CO) {
-        float acc[CO];
-#pragma unroll
-        for (int j = 0; j < CO; ++j) acc[j] = 0.f;
-        for (int ci = 0; ci < Cin; ++ci)
-#pragma unroll
-            for (int dy = 0; dy < 3; ++dy) {
-                const float* wrow = win + (ci * S3_WIN + py * 2 + dy) * S3_WIN + px * 2;
-                const float* wt = w + (int64_t)((ci * 3 + dy) * 3) * Cout + c0;
-#pragma unroll
-                for (int dx = 0; dx < 3; ++dx) {
-                    const float v = wrow[dx];
-#pragma unroll
-                    for (int j = 0; j < CO; ++j) acc[j] = fmaf(wt[dx * Cout + j], v, acc[j]);
-                }
-            }
-        if (live) {
-#pragma unroll
-            for (int j = 0; j < CO; j += 4) {
-                float4 o = make_float4(acc[j] + bias[c0 + j], acc[j + 1] + bias[c0 + j + 1], acc[j + 2] + bias[c0 + j + 2],
-                                       acc[j + 3] + bias[c0 + j + 3]);
-                if (relu) o = make_float4(relu1(o.x), relu1(o.y), relu1(o.z), relu1(o.w));
-                *reinterpret_cast<float4*>(yp + c0 + j) = o;
-            }
-        }
-    }
-}
 
 // ---- K20: 2x2 average pooling, stride 2 ---------------------------------------------------------------------------------
 // One thread per (output pixel, channel quad): four 16-byte loads, one 16-byte store.  The order
@@ -134,35 +62,6 @@ __global__ __launch_bounds__(64) void attnpool_tokens_kernel(const float* __rest
 
 }  // namespace
 
-extern "C" int mcd_conv3x3s2_nhwc(const float* x, int64_t B, int64_t Cin, int64_t H, int64_t W, const float* w,
-                                  const float* bias, int64_t Cout, int relu, float* y, mcd_stream_t stream) {
-    MCD_REQUIRE(x && w && bias && y, MCD_E_ARG, "mcd_conv3x3s2_nhwc: NULL pointer");
-    MCD_REQUIRE(B >= 0 && Cin >= 1 && Cin <= 4 && H >= 1 && W >= 1 && Cout >= 4 && Cout % 4 == 0, MCD_E_ARG,
-                "mcd_conv3x3s2_nhwc: bad shape B=%lld Cin=%lld H=%lld W=%lld Cout=%lld (Cin <= 4, Cout %% 4 == 0)",
-                (long long)B, (long long)Cin, (long long)H, (long long)W, (long long)Cout);
-    MCD_REQUIRE(((uintptr_t)x) % 4 == 0 && aligned16(w) && aligned16(bias) && aligned16(y), MCD_E_ARG,
-                "mcd_conv3x3s2_nhwc: w, bias and y must be 16-byte aligned (x: 4-byte)");
-    const int64_t Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-    const int64_t ntx = mcd_cdiv(Wo, S3_TILE), nty = mcd_cdiv(Ho, S3_TILE);
-    MCD_REQUIRE(Cin * H * W * 4 < kImageLimit && Ho * Wo * Cout * 4 < kImageLimit && B <= 65535 &&
-                    ntx * nty < ((int64_t)1 << 31), MCD_E_UNSUPPORTED,
-                "mcd_conv3x3s2_nhwc: one image's tensor reaches 2^31 bytes, or B > 65535");
-    const int64_t ybytes = B * Ho * Wo * Cout * 4;
-    MCD_REQUIRE(B == 0 || !(overlaps(x, B * Cin * H * W * 4, y, ybytes) || overlaps(w, Cin * 9 * Cout * 4, y, ybytes) ||
-                            overlaps(bias, Cout * 4, y, ybytes)), MCD_E_ARG,
-                "mcd_conv3x3s2_nhwc: x, w or bias overlaps y");
-    if (B == 0) return MCD_OK;
-    const dim3 grid((unsigned)(ntx * nty), (unsigned)B);
-    if (Cout % 32 == 0)
-        hipLaunchKernelGGL(conv3x3s2_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, x, (int)Cin, (int)H, (int)W, w,
-                           bias, (int)Cout, (int)Ho, (int)Wo, (int)ntx, relu ? 1 : 0, y);
-    else
-        hipLaunchKernelGGL(conv3x3s2_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, (int)Cin, (int)H, (int)W, w,
-                           bias, (int)Cout, (int)Ho, (int)Wo, (int)ntx, relu ? 1 : 0, y);
-    MCD_LAUNCH_CHECK("conv3x3s2_kernel");
-    return MCD_OK;
-}
-
 extern "C" int mcd_avgpool2_nhwc(const float* x, int64_t B, int64_t H, int64_t W, int64_t C, float* y,
                                  mcd_stream_t stream) {
     MCD_REQUIRE(x && y, MCD_E_ARG, "mcd_avgpool2_nhwc: NULL pointer");
@@ -170,7 +69,7 @@ extern "C" int mcd_avgpool2_nhwc(const float* x, int64_t B, int64_t H, int64_t W
                 "mcd_avgpool2_nhwc: bad shape B=%lld H=%lld W=%lld C=%lld (C %% 4 == 0)", (long long)B, (long long)H,
                 (long long)W, (long long)C);
     MCD_REQUIRE(aligned16(x) && aligned16(y), MCD_E_ARG, "mcd_avgpool2_nhwc: pointers must be 16-byte aligned");
-    MCD_REQUIRE(H * W * C * 4 < kImageLimit && B <= 65535, MCD_E_UNSUPPORTED,
+    MCD_REQUIRE(H * W * C * 4 < kImageLimit && B <= kBatchLimit, MCD_E_UNSUPPORTED,
                 "mcd_avgpool2_nhwc: one image's tensor reaches 2^31 bytes, or B > 65535");
     const int64_t Ho = H / 2, Wo = W / 2;
     if (B == 0 || Ho == 0 || Wo == 0) return MCD_OK;      // a one-pixel-wide image pools to an empty output: nothing to write
@@ -189,7 +88,7 @@ extern "C" int mcd_attnpool_tokens(const float* x, int64_t B, int64_t HW, int64_
                 (long long)C);
     MCD_REQUIRE(aligned16(x) && aligned16(pos) && aligned16(tok), MCD_E_ARG,
                 "mcd_attnpool_tokens: pointers must be 16-byte aligned");
-    MCD_REQUIRE(HW < ((int64_t)1 << 31) && (HW + 1) * C * 4 < kImageLimit && B <= 65535, MCD_E_UNSUPPORTED,
+    MCD_REQUIRE(HW < ((int64_t)1 << 31) && (HW + 1) * C * 4 < kImageLimit && B <= kBatchLimit, MCD_E_UNSUPPORTED,
                 "mcd_attnpool_tokens: one image's tokens reach 2^31 bytes, or B > 65535");
     if (B == 0) return MCD_OK;
     const int64_t out_bytes = B * (HW + 1) * C * 4;

@@ -6,19 +6,13 @@
 //             :273, :301 -- and the forward hook's pooling of a channels-last block output (concept_vit/utils.py:37-47).
 // Every kernel addresses one image from a 64-bit base with 32-bit offsets inside it (the entries refuse an image of 2^31
 // bytes or more), uses no atomics and no data of other images: an image's bits do not depend on its batch.
-#include "mcd_common.h"
+#include "k_nhwc.h"
 
 namespace {
 
 // SiLU and sigmoid with the accurate expf (no fast-math exp), as ATen computes them: x / (1 + exp(-x)), 1 / (1 + exp(-x))
 __device__ __forceinline__ float silu(float v) { return v / (1.0f + expf(-v)); }
 __device__ __forceinline__ float4 silu4(float4 v) { return make_float4(silu(v.x), silu(v.y), silu(v.z), silu(v.w)); }
-__device__ __forceinline__ float4 fma4(float4 a, float4 b, float4 c) {
-    return make_float4(fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w));
-}
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-
-constexpr int64_t kImageLimit = (int64_t)1 << 31;   // bytes of one image's tensor
 
 // TF-SAME padding of _SameConv (concept_vit/data_utils.py): the total pad max((ceil(n/s)-1)*s + k - n, 0), its smaller
 // half in front (top / left), the rest behind
@@ -247,11 +241,6 @@ __global__ __launch_bounds__(256) void pool_nhwc_kernel(const float* __restrict_
     }
 }
 
-inline unsigned grid_for(int64_t n, int64_t per_block, int64_t cap) {
-    const int64_t g = mcd_cdiv(n, per_block);
-    return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 }  // namespace
 
 extern "C" int mcd_conv_stem_nhwc(const float* x, int64_t B, int64_t Cin, int64_t H, int64_t W, const float* w,
@@ -260,10 +249,9 @@ extern "C" int mcd_conv_stem_nhwc(const float* x, int64_t B, int64_t Cin, int64_
     MCD_REQUIRE(B >= 0 && Cin >= 1 && Cin <= 4 && H >= 1 && W >= 1 && Cout >= 4 && Cout % 4 == 0, MCD_E_ARG,
                 "mcd_conv_stem_nhwc: bad shape B=%lld Cin=%lld H=%lld W=%lld Cout=%lld (Cin <= 4, Cout %% 4 == 0)",
                 (long long)B, (long long)Cin, (long long)H, (long long)W, (long long)Cout);
-    MCD_REQUIRE(((uintptr_t)w) % 16 == 0 && ((uintptr_t)bias) % 16 == 0 && ((uintptr_t)y) % 16 == 0, MCD_E_ARG,
-                "mcd_conv_stem_nhwc: w, bias and y must be 16-byte aligned");
+    MCD_REQUIRE(aligned16(w, bias, y), MCD_E_ARG, "mcd_conv_stem_nhwc: w, bias and y must be 16-byte aligned");
     const int64_t Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-    MCD_REQUIRE(Cin * H * W * 4 < kImageLimit && Ho * Wo * Cout * 4 < kImageLimit && B <= 65535, MCD_E_UNSUPPORTED,
+    MCD_REQUIRE(Cin * H * W * 4 < kImageLimit && Ho * Wo * Cout * 4 < kImageLimit && B <= kBatchLimit, MCD_E_UNSUPPORTED,
                 "mcd_conv_stem_nhwc: one image's tensor reaches 2^31 bytes, or B > 65535");
     if (B == 0) return MCD_OK;
     const int pt = same_pad_front(H, 3, 2), pl = same_pad_front(W, 3, 2);
@@ -282,14 +270,12 @@ extern "C" int mcd_dwconv_bn_silu(const float* x, int64_t B, int64_t H, int64_t 
                 (long long)W, (long long)C);
     MCD_REQUIRE((k == 3 || k == 5) && (stride == 1 || stride == 2), MCD_E_UNSUPPORTED,
                 "mcd_dwconv_bn_silu: k=%d stride=%d (k in {3, 5}, stride in {1, 2})", k, stride);
-    MCD_REQUIRE(((uintptr_t)x) % 16 == 0 && ((uintptr_t)w) % 16 == 0 && ((uintptr_t)bias) % 16 == 0 &&
-                ((uintptr_t)y) % 16 == 0 && ((uintptr_t)psum) % 16 == 0, MCD_E_ARG,
-                "mcd_dwconv_bn_silu: pointers must be 16-byte aligned");
+    MCD_REQUIRE(aligned16(x, w, bias, y, psum), MCD_E_ARG, "mcd_dwconv_bn_silu: pointers must be 16-byte aligned");
     const int64_t Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
     const int64_t ntx = mcd_cdiv(Wo, DW_TILE), nty = mcd_cdiv(Ho, DW_TILE);
     MCD_REQUIRE(T == ntx * nty, MCD_E_ARG, "mcd_dwconv_bn_silu: T=%lld, the %lld x %lld output has %lld tiles of 8 x 8",
                 (long long)T, (long long)Ho, (long long)Wo, (long long)(ntx * nty));
-    MCD_REQUIRE(H * W * C * 4 < kImageLimit && T * C * 4 < kImageLimit && B <= 65535 && T < (1LL << 31),
+    MCD_REQUIRE(H * W * C * 4 < kImageLimit && T * C * 4 < kImageLimit && B <= kBatchLimit && T < (1LL << 31),
                 MCD_E_UNSUPPORTED, "mcd_dwconv_bn_silu: one image's tensor reaches 2^31 bytes, or B > 65535");
     if (B == 0) return MCD_OK;
     const int nq = (int)(C / 4);
@@ -332,9 +318,8 @@ extern "C" int mcd_channel_scale(float* y, int64_t B, int64_t HW, int64_t C, con
     MCD_REQUIRE(y && s, MCD_E_ARG, "mcd_channel_scale: NULL pointer");
     MCD_REQUIRE(B >= 0 && HW >= 1 && C >= 4 && C % 4 == 0, MCD_E_ARG,
                 "mcd_channel_scale: bad shape B=%lld HW=%lld C=%lld (C %% 4 == 0)", (long long)B, (long long)HW, (long long)C);
-    MCD_REQUIRE(((uintptr_t)y) % 16 == 0 && ((uintptr_t)s) % 16 == 0, MCD_E_ARG,
-                "mcd_channel_scale: pointers must be 16-byte aligned");
-    MCD_REQUIRE(HW * C * 4 < kImageLimit && B <= 65535, MCD_E_UNSUPPORTED,
+    MCD_REQUIRE(aligned16(y, s), MCD_E_ARG, "mcd_channel_scale: pointers must be 16-byte aligned");
+    MCD_REQUIRE(HW * C * 4 < kImageLimit && B <= kBatchLimit, MCD_E_UNSUPPORTED,
                 "mcd_channel_scale: one image's tensor reaches 2^31 bytes, or B > 65535");
     if (B == 0) return MCD_OK;
     const int64_t n4 = HW * C / 4;
@@ -350,7 +335,7 @@ extern "C" int mcd_hook_pool_nhwc(const float* x, int64_t B, int64_t C, int64_t 
     MCD_REQUIRE(B >= 0 && C > 0 && HW > 0 && row0 >= 0 && col0 >= 0, MCD_E_ARG, "mcd_hook_pool_nhwc: bad shape");
     MCD_REQUIRE(mode == MCD_POOL_AVG || mode == MCD_POOL_MAX || mode == MCD_POOL_SILU_AVG, MCD_E_ARG,
                 "mcd_hook_pool_nhwc: bad mode %d (avg, max or silu_avg)", mode);
-    MCD_REQUIRE(HW * C * 4 < kImageLimit && B <= 65535, MCD_E_UNSUPPORTED,
+    MCD_REQUIRE(HW * C * 4 < kImageLimit && B <= kBatchLimit, MCD_E_UNSUPPORTED,
                 "mcd_hook_pool_nhwc: one image's tensor reaches 2^31 bytes, or B > 65535");
     if (B == 0) return MCD_OK;
     const dim3 grid((unsigned)mcd_cdiv(C, 64), (unsigned)B);

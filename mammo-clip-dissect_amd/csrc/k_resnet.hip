@@ -1,38 +1,38 @@
-// k_resnet.hip -- K16 / K17 / K18: the ResNet-50 target's inference route on channels-last (NHWC) activations with batch
-// norm folded into the weights.  The stride-1 1x1 convolutions around these kernels (conv1, conv3 + skip + ReLU, the
-// stride-1 downsample) are GEMMs on libmcd_blaslt.so; the stem, the pooling and every convolution whose rows are not a
-// strided matrix (3x3, 1x1 / 2) are here.
+// k_resnet.hip -- K16 / K17 / K18 / K19: the ResNet targets' inference route on channels-last (NHWC) activations with
+// batch norm folded into the weights, and the image stem of OpenAI-CLIP's ResNet, which is K16's kernel at another size.
+// The stride-1 1x1 convolutions around these kernels (conv1, conv3 + skip + ReLU, the stride-1 downsample) are GEMMs on
+// libmcd_blaslt.so; the stems, the pooling and every convolution whose rows are not a strided matrix (3x3, 1x1 / 2) are
+// here.
 //   replaces  conv1 (raw: it is a hook point), bn1 + relu + maxpool, and Bottleneck.conv2 + bn2 + relu /
 //             downsample[0] + downsample[1] of the torchvision layout    concept_vit/data_utils.py:85-93 (resnet50)
+//             ModifiedResNet's conv1 + bn1 + relu                        concept_vit/clip/model.py:107-108, :136-138
 // ResNet's symmetric padding: out = (n + 2p - k) / s + 1 (floor).  Every kernel addresses an image from a 64-bit base
 // with 32-bit offsets inside it (the entries refuse an image of 2^31 bytes or more), uses no atomics and never splits a
-// reduction: each output element is one fmaf chain in a fixed order (K16: channel, row, column; K18: tap, then channel),
-// so an image's bits depend neither on the batch it is in nor on its place in it.
-#include "mcd_common.h"
+// reduction: each output element is one fmaf chain in a fixed order (K16, K19: channel, row, column; K18: tap, then
+// channel), so an image's bits depend neither on the batch it is in nor on its place in it.
+#include "k_nhwc.h"
 
 namespace {
 
-constexpr int64_t kImageLimit = (int64_t)1 << 31;   // bytes of one image's tensor
-
-__device__ __forceinline__ float relu1(float v) { return v < 0.f ? 0.f : v; }      // keeps a NaN, like ATen's
-__device__ __forceinline__ float4 relu4(float4 v) { return make_float4(relu1(v.x), relu1(v.y), relu1(v.z), relu1(v.w)); }
-
-// ---- K16: 7x7 / 2 stem, raw ---------------------------------------------------------------------------------------
-// A workgroup owns a 16 x 16 tile of output pixels of one image and stages its 37 x 37 x Cin input window in LDS (zeros
-// outside the image = the padding).  A thread owns one pixel and CO output channels at a time (32, or 4 for a width
-// that is no multiple of 32): the weight index depends on loop counters only, so the weights come through the scalar
-// cache and every LDS read feeds CO FMAs.
+// ---- K16 / K19: the KS x KS / 2 image stems, pad KS / 2 -------------------------------------------------------------
+// K16 = <7, CO, false>: the ResNet stem, raw sums (conv1 is a hook point).  K19 = <3, CO, true>: CLIP's anti-aliased
+// stem, + bias (the folded batch norm), then the optional ReLU.
+// A workgroup owns a 16 x 16 tile of output pixels of one image and stages its ST_WIN x ST_WIN x Cin input window (37 or
+// 33 wide) in LDS (zeros outside the image = the padding).  A thread owns one pixel and CO output channels at a time (32,
+// or 4 for a width that is no multiple of 32): the weight and bias indices depend on loop counters only, so they come
+// through the scalar cache and every LDS read feeds CO FMAs.  One fmaf chain from 0 over (channel, row, column).
 constexpr int ST_TILE = 16;
-constexpr int ST_WIN = (ST_TILE - 1) * 2 + 7;      // 37
 
-template <int CO>                                  // 32 when Cout % 32 == 0, else 4
-__global__ __launch_bounds__(256) void conv7x7s2_kernel(const float* __restrict__ x, int Cin, int H, int W,
-                                                         const float* __restrict__ w, int Cout, int Ho, int Wo, int ntx,
+template <int KS, int CO, bool EPI>                // CO: 32 when Cout % 32 == 0, else 4
+__global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict__ x, int Cin, int H, int W,
+                                                         const float* __restrict__ w, const float* __restrict__ bias,
+                                                         int Cout, int Ho, int Wo, int ntx, int relu,
                                                          float* __restrict__ y) {
+    constexpr int ST_WIN = (ST_TILE - 1) * 2 + KS, PAD = KS / 2;
     __shared__ float win[4 * ST_WIN * ST_WIN];
     const int64_t b = blockIdx.y;
     const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
-    const int iy0 = ty * ST_TILE * 2 - 3, ix0 = tx * ST_TILE * 2 - 3;
+    const int iy0 = ty * ST_TILE * 2 - PAD, ix0 = tx * ST_TILE * 2 - PAD;
     const float* xb = x + b * Cin * H * W;
     for (int i = threadIdx.x; i < Cin * ST_WIN * ST_WIN; i += 256) {
         const int ci = i / (ST_WIN * ST_WIN), r = i - ci * (ST_WIN * ST_WIN);
@@ -49,21 +49,37 @@ __global__ __launch_bounds__(256) void conv7x7s2_kernel(const float* __restrict_
         float acc[CO];
 #pragma unroll
         for (int j = 0; j < CO; ++j) acc[j] = 0.f;
-        for (int ci = 0; ci < Cin; ++ci)
-            for (int dy = 0; dy < 7; ++dy) {
-                const float* wrow = win + (ci * ST_WIN + py * 2 + dy) * ST_WIN + px * 2;
-                const float* wt = w + (int64_t)((ci * 7 + dy) * 7) * Cout + c0;
+        // One window row of one channel.  A macro, so that both loops below hold the very text the two kernels had: as a
+        // lambda or a __forceinline__ function the same lines compile to other registers and another schedule.
+#define MCD_STEM_ROW                                                                         \
+    {                                                                                        \
+        const float* wrow = win + (ci * ST_WIN + py * 2 + dy) * ST_WIN + px * 2;             \
+        const float* wt = w + (int64_t)((ci * KS + dy) * KS) * Cout + c0;                    \
+        _Pragma("unroll") for (int dx = 0; dx < KS; ++dx) {                                  \
+            const float v = wrow[dx];                                                        \
+            _Pragma("unroll") for (int j = 0; j < CO; ++j) acc[j] = fmaf(wt[dx * Cout + j], v, acc[j]); \
+        }                                                                                    \
+    }
+        // the rows of a 3 x 3 are unrolled, those of a 7 x 7 left to the compiler's heuristic (`unroll 1` is not the same)
+        for (int ci = 0; ci < Cin; ++ci) {
+            if constexpr (KS == 3) {
 #pragma unroll
-                for (int dx = 0; dx < 7; ++dx) {
-                    const float v = wrow[dx];
-#pragma unroll
-                    for (int j = 0; j < CO; ++j) acc[j] = fmaf(wt[dx * Cout + j], v, acc[j]);
-                }
+                for (int dy = 0; dy < KS; ++dy) MCD_STEM_ROW
+            } else {
+                for (int dy = 0; dy < KS; ++dy) MCD_STEM_ROW
             }
+        }
+#undef MCD_STEM_ROW
         if (live) {
 #pragma unroll
-            for (int j = 0; j < CO; j += 4)
-                *reinterpret_cast<float4*>(yp + c0 + j) = make_float4(acc[j], acc[j + 1], acc[j + 2], acc[j + 3]);
+            for (int j = 0; j < CO; j += 4) {
+                float4 o = make_float4(acc[j], acc[j + 1], acc[j + 2], acc[j + 3]);
+                if constexpr (EPI) {
+                    o = add4(o, make_float4(bias[c0 + j], bias[c0 + j + 1], bias[c0 + j + 2], bias[c0 + j + 3]));
+                    if (relu) o = relu4(o);
+                }
+                *reinterpret_cast<float4*>(yp + c0 + j) = o;
+            }
         }
     }
 }
@@ -312,11 +328,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const float* __restr
     }
 }
 
-inline unsigned grid_for(int64_t n, int64_t per_block, int64_t cap) {
-    const int64_t g = mcd_cdiv(n, per_block);
-    return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
 template <int BC, int KS, bool RES>
 int launch_igemm(const float* x, int64_t B, int64_t H, int64_t W, int64_t Cin, const float* wt, const float* bias,
                  const float* res, int64_t Cout, int stride, int pad, int64_t Ho, int64_t Wo, int relu_in, int relu_out,
@@ -341,31 +352,53 @@ int launch_igemm(const float* x, int64_t B, int64_t H, int64_t W, int64_t Cin, c
     return MCD_OK;
 }
 
+// The checks and the dispatch of both stem entries (`name` is the entry's, for the messages).  k = 7: K16, raw, no bias;
+// k = 3: K19, with its epilogue.
+int stem_conv_entry(const char* name, int k, const float* x, int64_t B, int64_t Cin, int64_t H, int64_t W, const float* w,
+                    const float* bias, int64_t Cout, int relu, float* y, mcd_stream_t stream) {
+    const bool epi = k == 3;
+    MCD_REQUIRE(x && w && y && (bias || !epi), MCD_E_ARG, "%s: NULL pointer", name);
+    MCD_REQUIRE(B >= 0 && Cin >= 1 && Cin <= 4 && H >= 1 && W >= 1 && Cout >= 4 && Cout % 4 == 0, MCD_E_ARG,
+                "%s: bad shape B=%lld Cin=%lld H=%lld W=%lld Cout=%lld (Cin <= 4, Cout %% 4 == 0)", name, (long long)B,
+                (long long)Cin, (long long)H, (long long)W, (long long)Cout);
+    MCD_REQUIRE((!epi || ((uintptr_t)x) % 4 == 0) && aligned16(w, bias, y), MCD_E_ARG,
+                "%s: w, bias and y must be 16-byte aligned (x: 4-byte)", name);
+    const int pad = k / 2;
+    const int64_t Ho = (H + 2 * pad - k) / 2 + 1, Wo = (W + 2 * pad - k) / 2 + 1;
+    const int64_t ntx = mcd_cdiv(Wo, ST_TILE), nty = mcd_cdiv(Ho, ST_TILE);
+    MCD_REQUIRE(Cin * H * W * 4 < kImageLimit && Ho * Wo * Cout * 4 < kImageLimit && B <= kBatchLimit &&
+                    ntx * nty < ((int64_t)1 << 31), MCD_E_UNSUPPORTED,
+                "%s: one image's tensor reaches 2^31 bytes, or B > 65535", name);
+    if (B == 0) return MCD_OK;
+    const int64_t ybytes = B * Ho * Wo * Cout * 4;
+    MCD_REQUIRE(!overlaps(x, B * Cin * H * W * 4, y, ybytes) && !overlaps(w, Cin * k * k * Cout * 4, y, ybytes) &&
+                    !(bias && overlaps(bias, Cout * 4, y, ybytes)), MCD_E_ARG, "%s: x, w or bias overlaps y", name);
+    const dim3 grid((unsigned)(ntx * nty), (unsigned)B);
+#define MCD_STEM(KS, CO, EPI)                                                                                            \
+    hipLaunchKernelGGL((stem_conv_kernel<KS, CO, EPI>), grid, dim3(256), 0, (hipStream_t)stream, x, (int)Cin, (int)H,   \
+                       (int)W, w, bias, (int)Cout, (int)Ho, (int)Wo, (int)ntx, relu ? 1 : 0, y)
+    if (epi) {
+        if (Cout % 32 == 0) MCD_STEM(3, 32, true);
+        else MCD_STEM(3, 4, true);
+    } else {
+        if (Cout % 32 == 0) MCD_STEM(7, 32, false);
+        else MCD_STEM(7, 4, false);
+    }
+#undef MCD_STEM
+    MCD_LAUNCH_CHECK("stem_conv_kernel");
+    return MCD_OK;
+}
+
 }  // namespace
 
 extern "C" int mcd_conv7x7s2_nhwc(const float* x, int64_t B, int64_t Cin, int64_t H, int64_t W, const float* w,
                                   int64_t Cout, float* y, mcd_stream_t stream) {
-    MCD_REQUIRE(x && w && y, MCD_E_ARG, "mcd_conv7x7s2_nhwc: NULL pointer");
-    MCD_REQUIRE(B >= 0 && Cin >= 1 && Cin <= 4 && H >= 1 && W >= 1 && Cout >= 4 && Cout % 4 == 0, MCD_E_ARG,
-                "mcd_conv7x7s2_nhwc: bad shape B=%lld Cin=%lld H=%lld W=%lld Cout=%lld (Cin <= 4, Cout %% 4 == 0)",
-                (long long)B, (long long)Cin, (long long)H, (long long)W, (long long)Cout);
-    MCD_REQUIRE(((uintptr_t)w) % 16 == 0 && ((uintptr_t)y) % 16 == 0, MCD_E_ARG,
-                "mcd_conv7x7s2_nhwc: w and y must be 16-byte aligned");
-    const int64_t Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
-    const int64_t ntx = mcd_cdiv(Wo, ST_TILE), nty = mcd_cdiv(Ho, ST_TILE);
-    MCD_REQUIRE(Cin * H * W * 4 < kImageLimit && Ho * Wo * Cout * 4 < kImageLimit && B <= 65535 &&
-                    ntx * nty < ((int64_t)1 << 31), MCD_E_UNSUPPORTED,
-                "mcd_conv7x7s2_nhwc: one image's tensor reaches 2^31 bytes, or B > 65535");
-    if (B == 0) return MCD_OK;
-    const dim3 grid((unsigned)(ntx * nty), (unsigned)B);
-    if (Cout % 32 == 0)
-        hipLaunchKernelGGL(conv7x7s2_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, x, (int)Cin, (int)H, (int)W, w,
-                           (int)Cout, (int)Ho, (int)Wo, (int)ntx, y);
-    else
-        hipLaunchKernelGGL(conv7x7s2_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, (int)Cin, (int)H, (int)W, w,
-                           (int)Cout, (int)Ho, (int)Wo, (int)ntx, y);
-    MCD_LAUNCH_CHECK("conv7x7s2_kernel");
-    return MCD_OK;
+    return stem_conv_entry("mcd_conv7x7s2_nhwc", 7, x, B, Cin, H, W, w, nullptr, Cout, 0, y, stream);
+}
+
+extern "C" int mcd_conv3x3s2_nhwc(const float* x, int64_t B, int64_t Cin, int64_t H, int64_t W, const float* w,
+                                  const float* bias, int64_t Cout, int relu, float* y, mcd_stream_t stream) {
+    return stem_conv_entry("mcd_conv3x3s2_nhwc", 3, x, B, Cin, H, W, w, bias, Cout, relu, y, stream);
 }
 
 extern "C" int mcd_bn_relu_maxpool_nhwc(const float* x, int64_t B, int64_t H, int64_t W, int64_t C, const float* scale,
@@ -374,9 +407,8 @@ extern "C" int mcd_bn_relu_maxpool_nhwc(const float* x, int64_t B, int64_t H, in
     MCD_REQUIRE(B >= 0 && H >= 1 && W >= 1 && C >= 4 && C % 4 == 0, MCD_E_ARG,
                 "mcd_bn_relu_maxpool_nhwc: bad shape B=%lld H=%lld W=%lld C=%lld (C %% 4 == 0)", (long long)B,
                 (long long)H, (long long)W, (long long)C);
-    MCD_REQUIRE(((uintptr_t)x) % 16 == 0 && ((uintptr_t)scale) % 16 == 0 && ((uintptr_t)shift) % 16 == 0 &&
-                    ((uintptr_t)y) % 16 == 0, MCD_E_ARG, "mcd_bn_relu_maxpool_nhwc: pointers must be 16-byte aligned");
-    MCD_REQUIRE(H * W * C * 4 < kImageLimit && B <= 65535, MCD_E_UNSUPPORTED,
+    MCD_REQUIRE(aligned16(x, scale, shift, y), MCD_E_ARG, "mcd_bn_relu_maxpool_nhwc: pointers must be 16-byte aligned");
+    MCD_REQUIRE(H * W * C * 4 < kImageLimit && B <= kBatchLimit, MCD_E_UNSUPPORTED,
                 "mcd_bn_relu_maxpool_nhwc: one image's tensor reaches 2^31 bytes, or B > 65535");
     if (B == 0) return MCD_OK;
     const int64_t Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
@@ -400,17 +432,15 @@ int conv_igemm_entry(const char* name, const float* x, int64_t B, int64_t H, int
     MCD_REQUIRE(((k == 3 && (stride == 1 || stride == 2)) || (k == 1 && stride == 2)) && Cin % 32 == 0 && Cout % 32 == 0,
                 MCD_E_UNSUPPORTED, "%s: k=%d stride=%d Cin=%lld Cout=%lld (3x3 / 1 or 2, 1x1 / 2; Cin, Cout %% 32 == 0)",
                 name, k, stride, (long long)Cin, (long long)Cout);
-    MCD_REQUIRE(((uintptr_t)x) % 16 == 0 && ((uintptr_t)w) % 16 == 0 && ((uintptr_t)bias) % 16 == 0 &&
-                    ((uintptr_t)y) % 16 == 0 && ((uintptr_t)res) % 16 == 0, MCD_E_ARG,
-                "%s: pointers must be 16-byte aligned", name);
+    MCD_REQUIRE(aligned16(x, w, bias, y, res), MCD_E_ARG, "%s: pointers must be 16-byte aligned", name);
     const int pad = k == 3 ? 1 : 0;
     const int64_t Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
     MCD_REQUIRE(H * W * Cin * 4 < kImageLimit && Ho * Wo * Cout * 4 < kImageLimit && (int64_t)k * k * Cin * Cout * 4 < kImageLimit &&
-                    B <= 65535, MCD_E_UNSUPPORTED,
+                    B <= kBatchLimit, MCD_E_UNSUPPORTED,
                 "%s: one image's tensor (or the weight) reaches 2^31 bytes, or B > 65535", name);
     if (res) {      // every workgroup reads its residual pieces before it stores, but another may have stored there already
-        const uintptr_t r0 = (uintptr_t)res, y0 = (uintptr_t)y, bytes = (uintptr_t)(B * Ho * Wo * Cout * 4);
-        MCD_REQUIRE(r0 != y0 && (r0 + bytes <= y0 || y0 + bytes <= r0), MCD_E_ARG, "%s: res overlaps y", name);
+        const int64_t bytes = B * Ho * Wo * Cout * 4;
+        MCD_REQUIRE(res != y && !overlaps(res, bytes, y, bytes), MCD_E_ARG, "%s: res overlaps y", name);
     }
     if (B == 0) return MCD_OK;
     hipStream_t st = (hipStream_t)stream;

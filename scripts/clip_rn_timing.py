@@ -1,5 +1,5 @@
-"""The OpenAI-CLIP RN50 / RN101 dissectors' HIP route (K19-K21, csrc/k_clip_rn.hip, with K18, K9C and the library GEMMs)
-measured against the ATen route of the same modules.  Dev tool.
+"""The OpenAI-CLIP RN50 / RN101 dissectors' HIP route (K19 in csrc/k_resnet.hip, K20-K21 in csrc/k_clip_rn.hip, with K18,
+K9C and the library GEMMs) measured against the ATen route of the same modules.  Dev tool.
 
   --target NAME   clip_rn50 (default) or clip_rn101.
   --kernels [B]   K19 at the stem's shape, K20 at every shape the network pools (the stem, the three stride-2 blocks'

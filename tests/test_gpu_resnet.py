@@ -6,6 +6,8 @@ routing, and the driver: two extractions give the same bytes, at one rank and at
 The bound used throughout, as in test_gpu_mbconv.py: normalised error max|got - ref| / max|ref| at most twice that of
 ATen's fp32 result on the same inputs (measured in the same test) plus 1e-6; the factor 2 is the project's allowance for
 a different summation order."""
+import ctypes
+import ctypes.util
 import glob
 import os
 import sys
@@ -150,6 +152,83 @@ def test_k16_against_float64(core, dev, B, Cin, Cout, H, W):
     got = core.conv7x7s2_nhwc(x.to(dev), w.permute(1, 2, 3, 0).contiguous().to(dev))
     assert tuple(got.shape) == tuple(r64.shape) and got.is_contiguous()
     _bound(_nerr(got, r64), _nerr(aten, r64), "K16 %s" % ((B, Cin, Cout, H, W),))
+
+
+# (B, Cin, H, W, Cout): a tile edge crossed both ways, CO = 32; an image smaller than the window, CO = 4; one pixel and a
+# width that is no multiple of 32; Cin = 4 and three tiles across
+@pytest.mark.parametrize("shape", [(2, 3, 65, 47, 64), (2, 1, 7, 7, 8), (1, 3, 1, 1, 36), (1, 4, 33, 70, 32)])
+def test_k16_exact_on_integer_data(core, dev, shape):
+    """Small integers in x and w: every product and partial sum is exact in fp32 in any order (at most 4 * 49 * 64), so
+    the result equals the float64 one bit for bit, and any difference is an indexing or padding error."""
+    B, Cin, H, W, Cout = shape
+    g = torch.Generator().manual_seed(7 + H)
+    x = torch.randint(-8, 9, (B, Cin, H, W), generator=g).float()
+    w = torch.randint(-8, 9, (Cout, Cin, 7, 7), generator=g).float()
+    ref = F.conv2d(x.double(), w.double(), None, 2, 3).permute(0, 2, 3, 1)
+    got = core.conv7x7s2_nhwc(x.to(dev), w.permute(1, 2, 3, 0).contiguous().to(dev)).cpu()
+    assert torch.equal(got.double(), ref)
+
+
+def _stem_in_documented_order(x, w, bias, relu):
+    """The stem convolution (k x k / 2, pad k // 2) of x [B, Cin, H, W] with w [Cout, Cin, k, k] on the host, in the order
+    the stem kernel documents: per output element one libm fmaf chain from 0.0 in ascending (channel, row, column), a
+    padded tap entering as fmaf(w, 0, acc); then + bias, then the ReLU, where the kernel has them.  NHWC fp32."""
+    libm = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+    fmaf = libm.fmaf
+    fmaf.restype, fmaf.argtypes = ctypes.c_float, [ctypes.c_float] * 3
+    (B, Cin, H, W), Cout, k = x.shape, w.shape[0], w.shape[2]
+    pad = k // 2
+    Ho, Wo = (H + 2 * pad - k) // 2 + 1, (W + 2 * pad - k) // 2 + 1
+    xp, wl = F.pad(x, (pad,) * 4).tolist(), w.tolist()
+    out = torch.empty(B, Ho, Wo, Cout)
+    for b in range(B):
+        for oy in range(Ho):
+            for ox in range(Wo):
+                for co in range(Cout):
+                    acc = 0.0
+                    for ci in range(Cin):
+                        for dy in range(k):
+                            row, wrow = xp[b][ci][2 * oy + dy], wl[co][ci][dy]
+                            for dx in range(k):
+                                acc = fmaf(wrow[dx], row[2 * ox + dx], acc)
+                    out[b, oy, ox, co] = acc
+    if bias is not None:
+        out = out + bias                                             # one fp32 addition per element
+    return F.relu(out) if relu else out
+
+
+# tiny shapes, (B, Cin, H, W, Cout): the 4-channel pass and the 32-channel pass
+@pytest.mark.parametrize("shape", [(2, 3, 9, 11, 8), (1, 2, 5, 7, 32)])
+@pytest.mark.parametrize("kernel", ["K16", "K19"])
+def test_stem_kernels_keep_their_summation_order(core, dev, kernel, shape):
+    """Random float data: the bits depend on the order of the sum, and they must be those of the documented order."""
+    B, Cin, H, W, Cout = shape
+    k = 7 if kernel == "K16" else 3
+    g = torch.Generator().manual_seed(k + Cout)
+    x = torch.randn(B, Cin, H, W, generator=g)
+    w = torch.randn(Cout, Cin, k, k, generator=g)
+    w_tap = w.permute(1, 2, 3, 0).contiguous().to(dev)
+    if kernel == "K16":
+        assert torch.equal(core.conv7x7s2_nhwc(x.to(dev), w_tap).cpu(), _stem_in_documented_order(x, w, None, False))
+        return
+    bias = torch.randn(Cout, generator=g)
+    for relu in (False, True):
+        got = core.conv3x3s2_nhwc(x.to(dev), w_tap, bias.to(dev), relu=relu).cpu()
+        assert torch.equal(got, _stem_in_documented_order(x, w, bias, relu)), relu
+
+
+def test_k16_refuses_overlap(mcd, core, dev):
+    """y aliased onto x: MCD_E_ARG, and nothing is launched (x keeps its bits).  The output, 8 * 8 * 4 floats, is
+    smaller than x: the call stays inside the tensor whatever the entry does."""
+    x = torch.randn(1, 3, 16, 16, device=dev)
+    w = torch.randn(3, 7, 7, 4, device=dev)
+    before = x.clone()
+    L = mcd._lib.load()
+    with pytest.raises(mcd._lib.McdError, match="overlaps") as e:
+        mcd._lib.check(L.mcd_conv7x7s2_nhwc(x.data_ptr(), 1, 3, 16, 16, w.data_ptr(), 4, x.data_ptr(), core._stream()))
+    assert e.value.code == mcd._lib.MCD_E_ARG
+    torch.cuda.synchronize()
+    assert torch.equal(x, before)
 
 
 @pytest.mark.parametrize("B,C,H,W", [(2, 64, 112, 112), (2, 64, 80, 48), (3, 64, 33, 24), (2, 8, 7, 7), (2, 4, 1, 1),

@@ -206,6 +206,27 @@ def test_stem_folding_float64(du):
         assert (pooled - F.max_pool2d(F.relu(ref), 3, 2, 1)).abs().max() <= 1e-12 * ref.abs().max()
 
 
+def test_fold_conv_layouts(du):
+    """_fold_conv's three layouts against the expressions the _fold methods spelled out before it, bit for bit."""
+    g = torch.Generator().manual_seed(5)
+    conv, bn = torch.nn.Conv2d(4, 8, 3, bias=False), torch.nn.BatchNorm2d(8).eval()
+    with torch.no_grad():
+        conv.weight.copy_(torch.randn(8, 4, 3, 3, generator=g))
+        _randomise_bn(bn, g)
+        w, b = du.fold_bn(conv.weight, bn)
+        assert not torch.equal(w, conv.weight) and b.abs().min() > 0      # a batch norm that does something
+        for layout, want in (("gemm", w.flatten(1).contiguous()), ("igemm", du.igemm_weight(w)),
+                             ("tap", w.permute(1, 2, 3, 0).contiguous())):
+            got_w, got_b = du._fold_conv(conv, bn, layout)
+            assert got_w.shape == want.shape and got_w.dtype == want.dtype and torch.equal(got_w, want), layout
+            assert got_w.is_contiguous() and got_b.is_contiguous() and torch.equal(got_b, b), layout
+        assert tuple(du._fold_conv(conv, bn, "gemm")[0].shape) == (8, 36)
+        assert tuple(du._fold_conv(conv, bn, "igemm")[0].shape) == (8, 36)
+        assert tuple(du._fold_conv(conv, bn, "tap")[0].shape) == (4, 3, 3, 8)
+    with pytest.raises(KeyError):
+        du._fold_conv(conv, bn, "nchw")
+
+
 def test_fold_cache_follows_the_parameters(du):
     blk = du._Bottleneck(256, 128, 2).eval()
     f1 = du._folded(blk, du._BOTTLENECK_SKIPPED, du._Bottleneck._fold)
@@ -245,6 +266,9 @@ def test_entries_reject_bad_arguments(mcd):
     assert _rc(mcd, "mcd_conv7x7s2_nhwc", P, 2, 3, 8, 8, P + 4, 64, P, s) == E_ARG           # alignment
     assert _rc(mcd, "mcd_conv7x7s2_nhwc", P, 2, 3, 40000, 40000, P, 64, P, s) == E_UNS       # one image >= 2^31 B
     assert _rc(mcd, "mcd_conv7x7s2_nhwc", P, 65536, 3, 8, 8, P, 64, P, s) == E_UNS
+    assert _rc(mcd, "mcd_conv7x7s2_nhwc", P, 2, 3, 8, 8, P + 65536, 64, P + 16, s) == E_ARG  # y starts inside x
+    assert b"overlap" in mcd._lib.load().mcd_last_error()
+    assert _rc(mcd, "mcd_conv7x7s2_nhwc", P, 2, 3, 8, 8, P + 65536 + 1024, 64, P + 65536, s) == E_ARG   # w inside y
     assert _rc(mcd, "mcd_conv7x7s2_nhwc", P, 0, 3, 8, 8, P, 64, P, s) == 0                   # B = 0: nothing to do
     # K17 mcd_bn_relu_maxpool_nhwc(x, B, H, W, C, scale, shift, y, stream)
     assert _rc(mcd, "mcd_bn_relu_maxpool_nhwc", P, 2, 8, 8, 64, NULL, P, P, s) == E_ARG
