@@ -199,7 +199,7 @@ int mcd_wpmi_score_bf16(const uint16_t* E, int64_t ldE, int64_t N, int64_t C, co
  *        prob_d = logsumexp_u(pdge[u,c]) - log(U_s);   out[u,c] = pdge[u,c] - lam*prob_d
  * replaces  prob_d = torch.logsumexp(prob_d_given_e, dim=0, keepdim=True) - torch.log(U*ones([1]))
  *           mutual_info = prob_d_given_e - lam*prob_d                     concept_vit/similarity.py:70-72, :92-96
- * seg_offsets is a HOST array of n_seg+1 row offsets (n_seg <= 64); out may alias pdge.
+ * seg_offsets is a HOST array of n_seg+1 ascending row offsets (n_seg <= 64; a segment without rows is skipped); out may alias pdge.
  * ws: device scratch of mcd_logsumexp_sub_workspace(total rows, C, n_seg) bytes (column maxima and the
  * 16-row partial sums that ATen's summation order chains).
  * ------------------------------------------------------------------------------------------- */

@@ -414,7 +414,7 @@ __global__ __launch_bounds__(256, KT == 16 ? 3 : 2) void gemm_nt_f32_dma_kernel(
         // matrix's last row: a row past it is dropped by the hardware's range check, a column past the last one by an offset
         // past any range -- one v_add + one store per value.  (The plain form below spends ~14 instructions per value on 64-bit
         // address products, compares and a branch: ~900 instructions, the 2.4 us per workgroup of profiles/r05_k1_notes.txt.)
-        const int room = __builtin_amdgcn_readfirstlane((int)((((M - row0) * ldc) - col0) * 4));      // host: M * ldc * 4 < 2^31
+        const int room = __builtin_amdgcn_readfirstlane((int)((((M - row0) * ldc) - col0) * 4));      // host: max(M, BM) * ldc * 4 < 2^31 (every row of the tile, real or not, gets an offset) -- test_embed_gemm_wide_pitch_keeps_the_gap
         const __amdgpu_buffer_rsrc_t rs_c = __builtin_amdgcn_make_buffer_rsrc((void*)(Cc + (row0 * ldc + col0)), 0, room, 0x00020000);
         const int ldc4 = (int)ldc * 4;
         const unsigned vbase = (unsigned)((wr * 64 + 4 * fk) * ldc4 + (wc * 64 + fr) * 4);
@@ -1284,6 +1284,16 @@ __global__ __launch_bounds__(256) void rowsum_finish_kernel(const float* __restr
     if (tg == 0 && n < Ni) rinv[n] = 1.0f / ((s_p[0][li] + s_p[1][li]) + (s_p[2][li] + s_p[3][li]));
 }
 
+// columns [c0, ldE) of every row of E cleared with 16-byte stores (c0 and ldE multiples of 16 concepts, E 16-byte aligned): the
+// padding past the last 256-concept tile, which the GEMM kernel never visits
+__global__ __launch_bounds__(256) void gexp_zero_pad_kernel(unsigned short* __restrict__ E, int64_t ldE, int64_t Ni, int64_t c0) {
+    const int64_t per_row = (ldE - c0) / 8, total = Ni * per_row;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / per_row, q = i - r * per_row;
+        *reinterpret_cast<uint4*>(E + r * ldE + c0 + 8 * q) = make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
 }  // namespace
 
 // Development knobs (timing ablations and kernel variants for scripts/*.sh) are read from the environment ONLY in the dev build
@@ -1413,7 +1423,9 @@ extern "C" int mcd_embed_gemm(const float* I, int64_t ldi, const float* T, int64
         const int k1_spread = mcd_dev_knob("MCD_GEMM_K1_SPREAD", 1);
         (void)k1_spread;
         // the output through a buffer descriptor: 31-bit byte offsets from the tile's first element (dev knob MCD_GEMM_K1_BST=0: the plain stores)
-        const bool bst = N * ldp * 4 < (1LL << 31) && mcd_dev_knob("MCD_GEMM_K1_BST", 1) != 0;
+        // (the kernel forms 32-bit offsets for all BM rows of a tile: with N < BM the tile's extent bounds them, or rows past N wrap
+        // back inside the descriptor -- pinned by tests/test_gpu_abi_contracts.py::test_embed_gemm_wide_pitch_keeps_the_gap)
+        const bool bst = (N > BM ? N : BM) * ldp * 4 < (1LL << 31) && mcd_dev_knob("MCD_GEMM_K1_BST", 1) != 0;
 #ifdef MCD_DEV_KNOBS
         // dev build, MCD_GEMM_K1_STAMPS=1: s_memrealtime stamps of every workgroup (scripts/k1_stamps.py reads them through mcd_dev_k1_stamps)
         if (mcd_dev_knob("MCD_GEMM_K1_STAMPS", 0) && g64 <= 4096) {
@@ -1702,5 +1714,14 @@ extern "C" int mcd_embed_gemm_exp(const float* I, int64_t ldi, const float* T, i
     hipLaunchKernelGGL(rowsum_finish_kernel, dim3((unsigned)mcd_cdiv(N, 64)), dim3(256), 0, st, part, ldpart,
                        2 * (int)mcd_cdiv(C, 256), N, rinv);
     MCD_LAUNCH_CHECK("rowsum_finish_kernel");
+    // "columns C..ldE-1 written as 0": the kernel clears up to the end of its last 256-concept tile; a wider pitch's remainder is
+    // cleared here (never at the binding's pitches) -- pinned by tests/test_gpu_abi_contracts.py::test_embed_gemm_exp_pitches
+    const int64_t c_span = mcd_cdiv(C, 256) * 256;
+    if (ldE > c_span) {
+        const int64_t pieces = N * ((ldE - c_span) / 8);
+        hipLaunchKernelGGL(gexp_zero_pad_kernel, dim3((unsigned)(mcd_cdiv(pieces, 256) < 4096 ? mcd_cdiv(pieces, 256) : 4096)), dim3(256), 0,
+                           st, E, ldE, N, c_span);
+        MCD_LAUNCH_CHECK("gexp_zero_pad_kernel");
+    }
     return MCD_OK;
 }

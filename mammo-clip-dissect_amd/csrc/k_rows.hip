@@ -414,7 +414,9 @@ extern "C" int mcd_row_softmax(const float* P, int64_t ldp, int64_t N, int64_t C
     // (763 concepts: 0.021 ms against 0.028 for the register kernel; 10 000: 0.57 against 1.24 for the streaming one)
     const int vec4 = (ldp % 4 == 0) && (lds % 4 == 0) && (((uintptr_t)P) % 16 == 0) && (((uintptr_t)S) % 16 == 0);
     const size_t sh = (size_t)((C + 3) / 4 * 4) * sizeof(float);
-    if (lds <= 16 * 16)
+    // (rows shorter than one 16-float vector at ANY pitch: only the register kernel has ATen's left-to-right sum for them, and its
+    // padding loop runs to lds; the LDS kernels' 16 chains would start from elements the row does not have)
+    if (lds <= 16 * 16 || C < 16)
         hipLaunchKernelGGL(row_softmax_kernel<16>, grid, block, 0, st, P, ldp, N, C, a, S, lds);
     else if (C <= 1024 && N <= 0x7fffffffLL)
         hipLaunchKernelGGL(row_softmax_lds_kernel<128>, dim3((unsigned)N), dim3(128), sh, st, P, ldp, C, a, S, lds, vec4);

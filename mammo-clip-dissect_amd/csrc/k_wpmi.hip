@@ -112,9 +112,17 @@ __device__ __forceinline__ v2f log_tab2(v2f w, const LogTab& T) {
     low = low + err;
     return H + low;
 }
+// one argument of a group that failed its common range check: the table where IT is in range, libm's logf where it is not, so
+// that an element's bits never depend on what shares its lane -- a neighbouring column, or the padding of S behind column C
+// (tests/test_gpu_abi_contracts.py::test_wpmi_score_pitches)
+__device__ __noinline__ float log_acc_alone(float w, LogTab T) {
+    const unsigned b = __float_as_uint(w);
+    if (log_in_table(b, b)) return log_tab2(v2f{w, w}, T).x;
+    return logf(w);
+}
 __device__ __forceinline__ v2f log_acc2(v2f w, const LogTab& T) {
     const unsigned b0 = __float_as_uint(w.x), b1 = __float_as_uint(w.y);
-    if (__builtin_expect(!log_in_table(min(b0, b1), max(b0, b1)), 0)) return v2f{logf(w.x), logf(w.y)};
+    if (__builtin_expect(!log_in_table(min(b0, b1), max(b0, b1)), 0)) return v2f{log_acc_alone(w.x, T), log_acc_alone(w.y, T)};
     return log_tab2(w, T);
 }
 __device__ __forceinline__ float log_acc(float w, const LogTab& T) { return log_acc2(v2f{w, w}, T).x; }
@@ -133,9 +141,9 @@ __device__ __forceinline__ void log_acc2x3(v2f w0, v2f w1, v2f w2, const LogTab&
     const unsigned mn = min(min(min(a0, a1), min(b0, b1)), min(c0, c1));
     const unsigned mx = max(max(max(a0, a1), max(b0, b1)), max(c0, c1));
     if (__builtin_expect(!log_in_table(mn, mx), 0)) {
-        t0 = v2f{logf(w0.x), logf(w0.y)};
-        t1 = v2f{logf(w1.x), logf(w1.y)};
-        t2 = v2f{logf(w2.x), logf(w2.y)};
+        t0 = v2f{log_acc_alone(w0.x, T), log_acc_alone(w0.y, T)};
+        t1 = v2f{log_acc_alone(w1.x, T), log_acc_alone(w1.y, T)};
+        t2 = v2f{log_acc_alone(w2.x, T), log_acc_alone(w2.y, T)};
         return;
     }
     t0 = log_tab2(w0, T);
@@ -1165,21 +1173,24 @@ extern "C" int mcd_logsumexp_sub(const float* pdge, int64_t ld, int64_t C, const
     SegTable seg;
     int64_t max_super = 0;
     seg.msoff[0] = 0;
-    for (int s = 0; s <= n_seg; ++s) {
-        seg.off[s] = seg_offsets[s];
-        MCD_REQUIRE(s == 0 || seg.off[s] > seg.off[s - 1], MCD_E_ARG, "mcd_logsumexp_sub: empty or unordered segment %d",
-                    s - 1);
-        MCD_REQUIRE(s == 0 || seg.off[s] - seg.off[s - 1] < (1 << 19), MCD_E_UNSUPPORTED,
+    seg.off[0] = seg_offsets[0];
+    int n_live = 0;      // a segment without rows (a layer without neurons) has nothing to compute: it is left out of the table
+    for (int s = 1; s <= n_seg; ++s) {
+        const int64_t rows = seg_offsets[s] - seg_offsets[s - 1];
+        MCD_REQUIRE(rows >= 0, MCD_E_ARG, "mcd_logsumexp_sub: unordered segment %d", s - 1);
+        MCD_REQUIRE(rows < (1 << 19), MCD_E_UNSUPPORTED,
                     "mcd_logsumexp_sub: segment of 2^19 rows or more changes ATen's chunk size");
-        if (s > 0) {
-            const int64_t ns = (seg.off[s] - seg.off[s - 1]) >> 6;
-            seg.msoff[s] = seg.msoff[s - 1] + (int32_t)(4 * ns);
-            if (ns > max_super) max_super = ns;
-        }
+        if (rows == 0) continue;
+        ++n_live;
+        seg.off[n_live] = seg_offsets[s];
+        const int64_t ns = rows >> 6;
+        seg.msoff[n_live] = seg.msoff[n_live - 1] + (int32_t)(4 * ns);
+        if (ns > max_super) max_super = ns;
     }
-    const int64_t U_total = seg.off[n_seg] - seg.off[0];
-    const size_t need = mcd_logsumexp_sub_workspace(U_total, C, n_seg);
-    MCD_REQUIRE(ws && ws_bytes >= need, MCD_E_WORKSPACE, "mcd_logsumexp_sub: workspace %zu < %zu bytes", ws_bytes, need);
+    const size_t need_given = mcd_logsumexp_sub_workspace(seg_offsets[n_seg] - seg_offsets[0], C, n_seg);
+    MCD_REQUIRE(ws && ws_bytes >= need_given, MCD_E_WORKSPACE, "mcd_logsumexp_sub: workspace %zu < %zu bytes", ws_bytes, need_given);
+    n_seg = n_live;
+    if (n_seg == 0) return MCD_OK;
     if (split < 0) split = (int)(C >= 8 ? (C / 32) * 32 : (C / 4) * 4);
     hipStream_t st = (hipStream_t)stream;
     {   // one-pass panel kernel when the largest segment fits in LDS

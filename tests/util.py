@@ -402,3 +402,58 @@ def nhwc_input(c, h=9, w=7):
 def entry_rc(mcd, name, *args):
     """The return code of the C entry `name` called with raw arguments (the argument checks: no device call happens)."""
     return getattr(mcd._lib.load(), name)(*args)
+
+
+# ---- framed buffers: the C ABI's pitch, padding and aliasing contracts (test_gpu_abi_contracts.py, test_abi_frame_cpu.py) -----
+OUT_FILL = -7.0e30                    # what an output frame holds before the call: finite, and no kernel here produces it
+GAP_FILLS = (float("nan"), 1.0e30)    # what the gaps of an input frame hold, one run each: the outputs must not differ
+
+
+def int_bits(t):
+    """The integer view of a tensor or numpy array (int32 / int16 for 4- / 2-byte floats), so that NaNs compare."""
+    if isinstance(t, np.ndarray):
+        t = torch.from_numpy(np.ascontiguousarray(t))
+    if t.is_floating_point():
+        return t.view({4: torch.int32, 2: torch.int16}[t.element_size()])
+    return t
+
+
+def framed(rows, width, pitch, base_off, guard, fill, dtype, device, tail=0):
+    """(flat, view): ONE allocation of `guard` elements, `base_off` elements, (rows-1)*pitch + width elements (+ `tail` more
+    that the last row's padding may take: an entry that is entitled to write the pad columns of the last row needs them)
+    and `guard` elements again, all of it `fill`; view = the [rows, width] matrix of pitch `pitch` that starts behind
+    guard + base_off.  guard is kept a multiple of 16 bytes, so base_off alone decides the alignment of the view."""
+    assert rows >= 1 and pitch >= width >= 1 and 0 <= tail <= pitch - width
+    flat = torch.full((2 * guard + base_off + (rows - 1) * pitch + width + tail,), fill, dtype=dtype, device=device)
+    assert flat.data_ptr() % 16 == 0 and (guard * flat.element_size()) % 16 == 0
+    return flat, torch.as_strided(flat, (rows, width), (pitch, 1), guard + base_off)
+
+
+def check_frame(flat, view_spec, expected_bits, zero_pad=False, what=""):
+    """view_spec = (rows, width, pitch, base_off, guard, fill) of framed().  On the integer views:
+    (a) the logical [rows, width] region equals expected_bits;
+    (b) every other element of flat still holds the fill -- except, with zero_pad, the padding columns width..pitch-1 of
+        every row (the last row's as far as flat holds them in front of the trailing guard), which must be +0."""
+    rows, width, pitch, base_off, guard, fill = view_spec
+    fb = int_bits(flat)
+    start, end = guard + base_off, fb.numel() - guard
+    assert start + (rows - 1) * pitch + width <= end
+    exp = int_bits(expected_bits).to(fb.device).reshape(rows, width)
+    got = torch.as_strided(fb, (rows, width), (pitch, 1), start)
+    bad = (got != exp).nonzero()
+    assert bad.numel() == 0, "%s: %d elements of the logical region differ, the first at (row %d, column %d)" % (
+        what, bad.shape[0], int(bad[0, 0]), int(bad[0, 1]))
+    want = torch.full_like(fb, int(int_bits(torch.full((1,), fill, dtype=flat.dtype))[0]))
+    if zero_pad and pitch > width:
+        if rows > 1:
+            torch.as_strided(want, (rows - 1, pitch - width), (pitch, 1), start + width).zero_()
+        last = start + (rows - 1) * pitch
+        want[last + width:min(last + pitch, end)] = 0
+    torch.as_strided(want, (rows, width), (pitch, 1), start).copy_(exp)
+    bad = (fb != want).nonzero()
+    if bad.numel():
+        o = int(bad[0, 0]) - start
+        where = "row %d, column %d of the pitch" % (o // pitch, o % pitch) if 0 <= o < end - start else \
+            ("the leading guard / base offset" if o < 0 else "the trailing guard")
+        raise AssertionError("%s: %d elements outside the logical region changed (or a promised zero is not +0), the first "
+                             "at flat[%d] = %s" % (what, bad.shape[0], int(bad[0, 0]), where))
