@@ -250,7 +250,9 @@ int mcd_rank_reorder(const float* P, int64_t ldP, int64_t N, int64_t C, const fl
  *      LDS, flash-style online softmax, v_mfma_f32_32x32x2_f32 for both products.  Both pointers 16-byte aligned.
  *      Encoder-side op (the forwards that the extraction loop drives, concept_vit/utils.py:117-148): fp32-accurate
  *      (<= 2e-6 from torch's SDPA), no bit-exactness claim -- the reference's own encoders run on whatever
- *      backend torch picks.
+ *      backend torch picks.  A NaN propagates as in the reference (in q: that output row of that head; in k: every
+ *      query of that image and head; in v: that column of them) and reaches nothing else; results for +-Inf inputs
+ *      are unspecified (K9, K9L and K9C alike: a masked key multiplies the clamped last V row by p = 0).
  * replaces  the attention inside ViTModel(...)                             model/modules/image_encoder.py:37
  *           nn.MultiheadAttention(x, x, x, need_weights=False)            concept_vit/clip/model.py:171-183
  * ------------------------------------------------------------------------------------------- */

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import GAP_FILLS, OUT_FILL, check_frame, framed
+from util import GAP_FILLS, OUT_FILL, check_frame, framed, framed_dense
 
 ROWS, W, PX, PY, GUARD = 5, 7, 11, 12, 16
 X = np.random.default_rng(0).standard_normal((ROWS, W)).astype(np.float32)
@@ -78,3 +78,30 @@ def test_a_wrong_value_and_a_nan_payload_are_caught():
     check_frame(f, (1, 1, 1, 0, GUARD, OUT_FILL), a.view(np.float32))
     with pytest.raises(AssertionError):
         check_frame(f, (1, 1, 1, 0, GUARD, OUT_FILL), np.array([[0x7fc00002]], np.int32).view(np.float32))
+
+
+@pytest.mark.parametrize("defect", [None, "one_past_the_end", "one_before_the_start", "wrong_element", "empty_but_written"])
+def test_a_contiguous_nd_operand_is_a_frame_of_one_row(defect):
+    """util.framed_dense: y [2, 3, 4] = 2 * x on a contiguous N-d output.  A store one element past the tensor or one in
+    front of it lands in a guard and is caught, as is a wrong element; an empty output ([2, 0, 4]: nothing is written) must
+    leave the whole allocation as it was, and one stray store into it is caught too."""
+    shape = (2, 0, 4) if defect == "empty_but_written" else (2, 3, 4)
+    x = np.random.default_rng(1).standard_normal(shape).astype(np.float32)
+    yf, yv, spec = framed_dense(shape, 0, GUARD, OUT_FILL, torch.float32, "cpu")
+    assert tuple(yv.shape) == shape and yv.is_contiguous() and spec[:2] == (1, x.size)
+    yv.copy_(torch.from_numpy(2 * x))
+    y = yf.numpy()
+    if defect == "one_past_the_end":
+        y[GUARD + x.size] = 5.0
+    elif defect == "one_before_the_start":
+        y[GUARD - 1] = 5.0
+    elif defect == "wrong_element":
+        y[GUARD + 13] = np.nextafter(y[GUARD + 13], np.float32(9))
+    elif defect == "empty_but_written":
+        y[GUARD] = 5.0
+    if defect is None:
+        check_frame(yf, spec, 2 * x)
+        return
+    match = r"\(row 0, column 13\)" if defect == "wrong_element" else "outside the logical region"
+    with pytest.raises(AssertionError, match=match):
+        check_frame(yf, spec, 2 * x)

@@ -429,6 +429,20 @@ def framed(rows, width, pitch, base_off, guard, fill, dtype, device, tail=0):
     return flat, torch.as_strided(flat, (rows, width), (pitch, 1), guard + base_off)
 
 
+def framed_dense(shape, base_off, guard, fill, dtype, device):
+    """(flat, view, view_spec) for a CONTIGUOUS N-d operand (an NHWC activation, a [B, T, C] token block): a frame of one row
+    of prod(shape) elements -- guard, base_off, the elements, guard, all of it `fill` -- view = the contiguous `shape` tensor
+    behind guard + base_off, view_spec what check_frame() takes.  An empty shape (an output nothing is written to) is a row of
+    no elements: check_frame() then wants the whole allocation to keep its fill."""
+    n = 1
+    for s in shape:
+        n *= int(s)
+    assert n >= 0 and base_off >= 0
+    flat = torch.full((2 * guard + base_off + n,), fill, dtype=dtype, device=device)
+    assert flat.data_ptr() % 16 == 0 and (guard * flat.element_size()) % 16 == 0
+    return flat, flat[guard + base_off:guard + base_off + n].view(*shape), (1, n, max(n, 1), base_off, guard, fill)
+
+
 def check_frame(flat, view_spec, expected_bits, zero_pad=False, what=""):
     """view_spec = (rows, width, pitch, base_off, guard, fill) of framed().  On the integer views:
     (a) the logical [rows, width] region equals expected_bits;
