@@ -299,10 +299,13 @@ int mcd_layer_norm(const float* x, int64_t rows, int64_t D, const float* gamma, 
 /* ---------------------------------------------------------------------------------------------
  * K11  patch extraction for the ViT patch embedding: x [B, Cin, H, W] -> out [B, 1 + (H/P)(W/P), Cin*P*P], row 0 of
  *      every image zero (class-token slot), row 1 + patch in (c, dy, dx) order, so that the Conv2d(Cin, dim, P, P) is
- *      the GEMM  out . weight.view(dim, Cin*P*P)^T  (P, W multiples of 4; pointers 16-byte aligned).  A permutation
- *      of the pixels: exact.
+ *      the GEMM  out . weight.view(dim, Cin*P*P)^T.  A permutation of the pixels: exact.  P is any even size >= 2 that
+ *      divides H and W (16 for ViT-B/16, 14 for DINOv2): 16-byte accesses when P % 4 == 0, 8-byte ones otherwise (W is
+ *      a multiple of P, so every piece of a patch row is aligned to its size); an odd P is MCD_E_UNSUPPORTED.  Pointers
+ *      16-byte aligned.
  * replaces  the patch-embedding convolution of the image tower              model/modules/image_encoder.py:37
  *           (ViTPatchEmbeddings.projection), conv1                          concept_vit/clip/model.py:206-223
+ *           Dinov2PatchEmbeddings.projection of the `dino` targets          concept_vit/data_utils.py:24,63-69
  * ------------------------------------------------------------------------------------------- */
 int mcd_patchify(const float* x, int64_t B, int64_t Cin, int64_t H, int64_t W, int64_t P, float* out, mcd_stream_t stream);
 

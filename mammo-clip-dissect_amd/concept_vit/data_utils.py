@@ -17,6 +17,8 @@ dissection core they feed is the HIP library.
     resnet18 / 34          conv1, layer1..layer4                       64/64/128/256/512
     resnet18_places        as resnet18, 365 classes (reference :70-79)
     clip_rn50 / clip_rn101 visual.layer1..layer4, visual.attnpool      CLIP RN50 / RN101: 256/512/1024/2048, 1024 | 512
+    vit / -cub / -bloodmnist   vit.encoder.layer[0..11]                HF ViT-B/16 classifier: 12 x 768
+    dino / -cub / -bloodmnist  dinov2.encoder.layer[0..11]             HF DINOv2-base classifier (patch 14): 12 x 768
 """
 import math
 import os
@@ -143,6 +145,13 @@ def cls_tail_route(flag, fused_ok, masked, training, T, D, heads, depth, hooks_c
                 and 1 <= T <= core.VIT_ATTENTION_CLS_MAX_T and depth >= 1 and hooks_clear and last_hooks_token0)
 
 
+def embed_gate(P, H, W, table_rows):
+    """Whether ViTTower.embed may write the patch embedding as K11 + one GEMM: an even patch size (K11 reads 16-byte
+    pieces of a patch row at P % 4 == 0, 8-byte pieces at any other even P, and nothing narrower), an image of whole
+    patches, and a position table with one row per token."""
+    return bool(P >= 2 and P % 2 == 0 and H % P == 0 and W % P == 0 and 1 + (H // P) * (W // P) == table_rows)
+
+
 def _token0_hooks(m):
     """Every forward hook on m declares (attribute token0_only) that of a [B, T, D] output it reads token 0 only."""
     return all(getattr(h, "token0_only", False) for h in m._forward_hooks.values())
@@ -184,27 +193,64 @@ class _Attention(nn.Module):
         return o.transpose(1, 2).reshape(B, T, D)
 
 
-class _Block(nn.Module):
-    def __init__(self, dim, heads, mlp):
+class _LayerScale(nn.Module):
+    """DINOv2's per-channel scale of a branch in front of its residual add (Dinov2LayerScale: the parameter lambda1)."""
+
+    def __init__(self, dim, init):
         super().__init__()
-        self.norm1 = _LayerNorm(dim, eps=1e-12)
+        self.lambda1 = nn.Parameter(init * torch.ones(dim))
+
+    def forward(self, x):
+        return x * self.lambda1
+
+
+class _Block(nn.Module):
+    """Pre-norm transformer block.  eps: the LayerNorms' (HF ViT 1e-12, DINOv2 1e-6).  layer_scale: None, or the initial
+    value of the two LayerScales a DINOv2 block has, x + layer_scale1(proj(.)) and x + layer_scale2(fc2(.)); None builds
+    no such module (the state dict and the arithmetic of a plain block)."""
+
+    def __init__(self, dim, heads, mlp, eps=1e-12, layer_scale=None):
+        super().__init__()
+        self.norm1 = _LayerNorm(dim, eps=eps)
         self.attn = _Attention(dim, heads)
-        self.norm2 = _LayerNorm(dim, eps=1e-12)
+        self.norm2 = _LayerNorm(dim, eps=eps)
         self.fc1 = nn.Linear(dim, mlp)
         self.fc2 = nn.Linear(mlp, dim)
+        self.scaled = layer_scale is not None
+        if self.scaled:
+            self.layer_scale1 = _LayerScale(dim, layer_scale)
+            self.layer_scale2 = _LayerScale(dim, layer_scale)
 
     def forward(self, x, mask=None, cls_only=False):
         if cls_only and mask is None:      # a masked call keeps the full block whatever the caller asked for
             return self._forward_cls(x)
         if _fused_residual_ok(x):
             x = x.contiguous()
+            wp, bp, w2, b2 = self._residual_weights()
             # x1 is a new tensor (the block's input is left alone); the second update is in place on x1
-            x1 = core.linear_residual(x, self.attn.heads_out(self.norm1(x), mask).contiguous(), self.attn.proj.weight,
-                                      self.attn.proj.bias)
+            x1 = core.linear_residual(x, self.attn.heads_out(self.norm1(x), mask).contiguous(), wp, bp)
             h = F.gelu(_linear(self.fc1, self.norm2(x1)))
-            return core.linear_residual(x1, h, self.fc2.weight, self.fc2.bias, out=x1)
+            return core.linear_residual(x1, h, w2, b2, out=x1)
+        if self.scaled:
+            x = x + self.layer_scale1(self.attn(self.norm1(x), mask))
+            return x + self.layer_scale2(self.fc2(F.gelu(self.fc1(self.norm2(x)))))
         x = x + self.attn(self.norm1(x), mask)
         return x + self.fc2(F.gelu(self.fc1(self.norm2(x))))
+
+    def _residual_weights(self):
+        """(proj weight, proj bias, fc2 weight, fc2 bias) of the two fused residual GEMMs.  With LayerScale,
+        lambda * (W h + b) = (lambda (.) W) h + lambda (.) b: the scale is folded into the rows of the weight and into the
+        bias once (_folded: nothing is registered, the cache follows the parameters), so the GEMM's epilogue still does
+        the residual add and no pass over the activations is added."""
+        a = self.attn
+        if not self.scaled:
+            return a.proj.weight, a.proj.bias, self.fc2.weight, self.fc2.bias
+
+        def build(m):
+            l1, l2 = m.layer_scale1.lambda1.detach(), m.layer_scale2.lambda1.detach()
+            return ((l1[:, None] * m.attn.proj.weight.detach()).contiguous(), (l1 * m.attn.proj.bias.detach()).contiguous(),
+                    (l2[:, None] * m.fc2.weight.detach()).contiguous(), (l2 * m.fc2.bias.detach()).contiguous())
+        return _folded(self, ("layer_scale1", "layer_scale2", "attn", "fc2"), build)
 
     def _forward_cls(self, x):
         """The class-token row of forward(x), as [B, 1, D] (the caller has checked cls_tail_route): K and V need every
@@ -219,15 +265,16 @@ class _Block(nn.Module):
         kv = core.linear_residual(None, n, w[D:], None if b is None else b[D:]).view(B, T, 2, a.heads, D // a.heads)
         q = core.linear_residual(None, n[:, 0], w[:D], None if b is None else b[:D])
         o = core.vit_attention_cls(q, kv[:, :, 0], kv[:, :, 1])                          # K9C
-        x1 = core.linear_residual(x[:, 0], o, a.proj.weight, a.proj.bias)                # [B, D], a new tensor
+        wp, bp, w2, b2 = self._residual_weights()
+        x1 = core.linear_residual(x[:, 0], o, wp, bp)                                    # [B, D], a new tensor
         h = F.gelu(core.linear_residual(None, self.norm2(x1), self.fc1.weight, self.fc1.bias))
-        return core.linear_residual(x1, h, self.fc2.weight, self.fc2.bias, out=x1).unsqueeze(1)
+        return core.linear_residual(x1, h, w2, b2, out=x1).unsqueeze(1)
 
 
 class _Encoder(nn.Module):
-    def __init__(self, depth, dim, heads, mlp, list_name):
+    def __init__(self, depth, dim, heads, mlp, list_name, eps=1e-12, layer_scale=None):
         super().__init__()
-        setattr(self, list_name, nn.ModuleList([_Block(dim, heads, mlp) for _ in range(depth)]))
+        setattr(self, list_name, nn.ModuleList([_Block(dim, heads, mlp, eps, layer_scale) for _ in range(depth)]))
         self._list_name = list_name
 
     def forward(self, x, mask=None, cls_only=False):
@@ -259,18 +306,29 @@ def _parse_hw(text):
 
 class ViTTower(nn.Module):
     """[B,3,H,W] -> token sequence [B, 1+(H/16)*(W/16), 768]; hook points encoder.<list_name>[i].  image_size is an int
-    (square) or (H, W): (H/16)*(W/16) + 1 position embeddings, e.g. 5 416 for Mammo-CLIP's 1520 x 912."""
+    (square) or (H, W): (H/16)*(W/16) + 1 position embeddings, e.g. 5 416 for Mammo-CLIP's 1520 x 912.  eps and
+    layer_scale: the blocks' (_Block) and the final LayerNorm's."""
 
-    def __init__(self, image_size=224, patch=16, dim=768, depth=12, heads=12, mlp=3072, list_name="layer"):
+    def __init__(self, image_size=224, patch=16, dim=768, depth=12, heads=12, mlp=3072, list_name="layer", eps=1e-12,
+                 layer_scale=None):
         super().__init__()
         self.out_dim = dim
-        self.patch_embed = nn.Conv2d(3, dim, patch, patch)
         h, w = image_hw(image_size)
-        n = (h // patch) * (w // patch)
+        self._build_embedding(dim, patch, (h // patch) * (w // patch))
+        self.encoder = _Encoder(depth, dim, heads, mlp, list_name, eps, layer_scale)
+        self.layernorm = _LayerNorm(dim, eps=eps)
+
+    def _build_embedding(self, dim, patch, n):
+        """The embedding parameters, as this tower's own patch_embed / cls_token / pos_embed (HFTower keeps them in an
+        `embeddings` submodule under transformers' names)."""
+        self.patch_embed = nn.Conv2d(3, dim, patch, patch)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, n + 1, dim))
-        self.encoder = _Encoder(depth, dim, heads, mlp, list_name)
-        self.layernorm = _LayerNorm(dim, eps=1e-12)
+
+    def pos_table(self, H, W):
+        """The [1, T, dim] position table for an H x W image: pos_embed as it is (HFTower: interpolated to the image's
+        patch grid when `interpolate` is set)."""
+        return self.pos_embed
 
     def forward(self, x, cls_only=False):
         """cls_only=True: the caller reads [:, 0] of the result and nothing else.  Where cls_tail_route allows, the last
@@ -300,24 +358,26 @@ class ViTTower(nn.Module):
         """Patch embedding + class token + position embedding -> [B, 1 + n, dim]."""
         P = self.patch_embed.kernel_size[0]
         if (_fused_residual_ok(x) and x.is_contiguous() and x.dim() == 4 and self.patch_embed.bias is not None
-                and P % 4 == 0 and x.shape[2] % P == 0 and x.shape[3] % P == 0
-                and 1 + (x.shape[2] // P) * (x.shape[3] // P) == self.pos_embed.shape[1]):
+                and embed_gate(P, x.shape[2], x.shape[3], self.pos_table(x.shape[2], x.shape[3]).shape[1])):
             # the convolution as ONE GEMM that writes the token sequence directly (K11 + libmcd_blaslt.so): rows of
             # patch pixels (a zero row in every image's class-token slot) times the conv weight, plus the bias, plus a
             # residual operand that holds the position embedding (and cls + pos[0] - bias in the class-token rows).
             # No MIOpen call (its choice of algorithm varied between 0.5 and 1.2 ms from box to box), no cat, no add.
-            return core.linear_residual(self._embed_residual(x.shape[0]), core.patchify(x, P),
+            return core.linear_residual(self._embed_residual(x.shape[0], x.shape[2], x.shape[3]), core.patchify(x, P),
                                         self.patch_embed.weight.view(self.patch_embed.out_channels, -1), self.patch_embed.bias)
+        H, W = x.shape[2:]
         x = self.patch_embed(x).flatten(2).transpose(1, 2)
-        return torch.cat([self.cls_token.expand(x.shape[0], -1, -1), x], dim=1) + self.pos_embed
+        return torch.cat([self.cls_token.expand(x.shape[0], -1, -1), x], dim=1) + self.pos_table(H, W)
 
-    def _embed_residual(self, B):
-        """[B, 1 + n, dim]: pos_embed, with cls_token + pos_embed[0] - bias in row 0 (the GEMM adds the bias back)."""
+    def _embed_residual(self, B, H, W):
+        """[B, 1 + n, dim]: the position table of an H x W image (pos_table), with cls_token + its row 0 - bias in row 0
+        (the GEMM adds the bias back)."""
         def build(m):
-            r = m.pos_embed.detach().expand(B, -1, -1).contiguous()
-            r[:, 0] = m.cls_token.detach()[0, 0] + m.pos_embed.detach()[0, 0] - m.patch_embed.bias.detach()
+            pos = m.pos_table(H, W).detach()
+            r = pos.expand(B, -1, -1).contiguous()
+            r[:, 0] = m.cls_token.detach()[0, 0] + pos[0, 0] - m.patch_embed.bias.detach()
             return r
-        return _folded(self, ("pos_embed", "cls_token", "patch_embed"), build, extra=(B,))
+        return _folded(self, ("pos_embed", "cls_token", "patch_embed"), build, extra=(B, H, W))
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -683,6 +743,160 @@ class ClipViT(nn.Module):
 
     def forward(self, image):
         return self.encode_image(image)
+
+
+# ------------------------------------------------------------------------------------------------------
+# HF ViT / DINOv2 image classifiers (the `vit` / `dino` rows of the reference's MODELS table, data_utils.py:21-36:
+# ViTForImageClassification / Dinov2ForImageClassification behind AutoModelForImageClassification)
+# ------------------------------------------------------------------------------------------------------
+class _PatchEmbeddings(nn.Module):
+    def __init__(self, dim, patch):
+        super().__init__()
+        self.projection = nn.Conv2d(3, dim, patch, patch)
+
+
+class _HFEmbeddings(nn.Module):
+    """The embedding parameters under transformers' names: cls_token, position_embeddings,
+    patch_embeddings.projection."""
+
+    def __init__(self, dim, patch, n):
+        super().__init__()
+        self.cls_token = nn.Parameter(torch.zeros(1, 1, dim))
+        self.position_embeddings = nn.Parameter(torch.zeros(1, n + 1, dim))
+        self.patch_embeddings = _PatchEmbeddings(dim, patch)
+
+
+def interpolate_pos_table(pos, patch, H, W):
+    """transformers' interpolate_pos_encoding (Dinov2Embeddings, the `size=` form of the current releases): the class
+    row as it is, the square grid of patch rows resampled to (H / patch) x (W / patch), bicubic, align_corners=False,
+    computed in fp32 whatever the table's dtype.  The table is returned untouched when the grid is already the image's
+    and H == W."""
+    n = pos.shape[1] - 1
+    gh, gw = H // patch, W // patch
+    if gh * gw == n and H == W:
+        return pos
+    side = int(n ** 0.5)
+    grid = pos[:, 1:].reshape(1, side, side, -1).permute(0, 3, 1, 2)
+    grid = F.interpolate(grid.float(), size=(gh, gw), mode="bicubic", align_corners=False).to(pos.dtype)
+    return torch.cat([pos[:, :1], grid.permute(0, 2, 3, 1).reshape(1, gh * gw, -1)], dim=1)
+
+
+class HFTower(ViTTower):
+    """ViTTower with its embedding parameters in an `embeddings` submodule (the module tree of transformers' ViTModel /
+    Dinov2Model: embeddings, encoder.layer[i], layernorm).  interpolate=True (DINOv2): the position table is resampled to
+    the image's patch grid (interpolate_pos_table), once per (H, W)."""
+
+    def __init__(self, interpolate=False, **kw):
+        super().__init__(**kw)
+        self.interpolate = interpolate
+
+    def _build_embedding(self, dim, patch, n):
+        self.embeddings = _HFEmbeddings(dim, patch, n)
+
+    patch_embed = property(lambda self: self.embeddings.patch_embeddings.projection)
+    cls_token = property(lambda self: self.embeddings.cls_token)
+    pos_embed = property(lambda self: self.embeddings.position_embeddings)
+
+    def pos_table(self, H, W):
+        pos, P = self.pos_embed, self.patch_embed.kernel_size[0]
+        if not self.interpolate or ((H // P) * (W // P) == pos.shape[1] - 1 and H == W):
+            return pos
+        if torch.is_grad_enabled() and pos.requires_grad:      # training: the interpolation is part of the graph
+            return interpolate_pos_table(pos, P, H, W)
+        # cached on the embeddings module: the tower's own cache slot holds the fused path's residual operand
+        return _folded(self.embeddings, ("position_embeddings",), lambda m: interpolate_pos_table(
+            m.position_embeddings.detach(), P, H, W), extra=(H, W))
+
+
+def _hf_layer_map(prefix, i, dino):
+    """transformers-4.41.1 module names of encoder layer i -> this mirror's (q / k / v are handled apart)."""
+    base = "%s.encoder.layer.%d." % (prefix, i)
+    names = {"attention.output.dense": "attn.proj"}
+    if dino:                                         # norm1 / norm2 / layer_scale1 / layer_scale2 keep their names
+        names.update({"mlp.fc1": "fc1", "mlp.fc2": "fc2"})
+    else:
+        names.update({"layernorm_before": "norm1", "layernorm_after": "norm2", "intermediate.dense": "fc1",
+                      "output.dense": "fc2"})
+    return {base + a + "." + leaf: base + b + "." + leaf for a, b in names.items() for leaf in ("weight", "bias")}
+
+
+def hf_state_dict(sd, prefix, depth):
+    """A ViTForImageClassification / Dinov2ForImageClassification state dict with transformers-4.41.1 key names (the
+    reference's pin) -> the mirror's: the query / key / value projections of a layer concatenated into attn.qkv, the
+    other modules renamed, DINOv2's mask_token dropped (it only enters masked-image pre-training).  Keys that are the
+    mirror's already pass through, so a dict saved from the mirror loads as well."""
+    dino = prefix == "dinov2"
+    sd = dict(sd)
+    sd.pop(prefix + ".embeddings.mask_token", None)
+    out = {}
+    for i in range(depth):
+        base = "%s.encoder.layer.%d." % (prefix, i)
+        for leaf in ("weight", "bias"):
+            parts = [sd.pop(base + "attention.attention.%s.%s" % (n, leaf), None) for n in ("query", "key", "value")]
+            if all(t is not None for t in parts):
+                out[base + "attn.qkv." + leaf] = torch.cat(parts, dim=0)
+            elif any(t is not None for t in parts):
+                raise KeyError("%sattention.attention: query, key and value %s must come together" % (base, leaf))
+        for old, new in _hf_layer_map(prefix, i, dino).items():
+            if old in sd:
+                out[new] = sd.pop(old)
+    out.update(sd)
+    return out
+
+
+class _HFClassifier(nn.Module):
+    """What HFViT and HFDinov2 share: the tower under `prefix`, the linear classifier, the checkpoint mapping."""
+    prefix = None
+
+    @property
+    def tower(self):
+        return getattr(self, self.prefix)
+
+    def convert_state_dict(self, sd):
+        enc = self.tower.encoder
+        return hf_state_dict(sd, self.prefix, len(getattr(enc, enc._list_name)))
+
+    def encode_image(self, image):
+        return self(image)
+
+
+class HFViT(_HFClassifier):
+    """google/vit-base-patch16-224-in21k shaped target (ViTForImageClassification): hook points vit.encoder.layer[i];
+    LayerNorm eps 1e-12, exact GELU, the classifier on the class token of vit.layernorm's output.  Only the class token
+    is read, so the tower is asked for cls_only (cls_tail_route prunes the last block when the hooks allow)."""
+    prefix = "vit"
+
+    def __init__(self, num_labels=2, image_size=224, **kw):
+        super().__init__()
+        self.vit = HFTower(image_size=image_size, **kw)
+        self.classifier = nn.Linear(self.vit.out_dim, num_labels)
+
+    def forward(self, image):
+        return _linear(self.classifier, self.vit(image, cls_only=True)[:, 0].contiguous())
+
+
+class HFDinov2(_HFClassifier):
+    """facebook/dinov2-base shaped target (Dinov2ForImageClassification): hook points dinov2.encoder.layer[i]; patch 14,
+    LayerNorm eps 1e-6, LayerScale behind the attention projection and behind fc2, the classifier on cat(class token,
+    mean of the patch tokens) of dinov2.layernorm's output.  The mean reads every token: the tower always runs whole.
+    image_size sizes the position table (Dinov2Config's default 224: 16 x 16 + 1 rows); any other patch grid, or
+    H != W, gets the table interpolated."""
+    prefix = "dinov2"
+
+    def __init__(self, num_labels=2, image_size=224, patch=14, layer_scale=1.0, **kw):
+        super().__init__()
+        self.dinov2 = HFTower(interpolate=True, image_size=image_size, patch=patch, eps=1e-6, layer_scale=layer_scale, **kw)
+        self.classifier = nn.Linear(2 * self.dinov2.out_dim, num_labels)
+
+    def forward(self, image):
+        t = self.dinov2(image)
+        return _linear(self.classifier, torch.cat([t[:, 0], t[:, 1:].mean(dim=1)], dim=1))
+
+
+# name -> (class, classifier width; None: n_class, or transformers' default of 2): reference data_utils.py:21-36.  The
+# -cub / -bloodmnist names are the same architectures fine-tuned on CUB-200 and BloodMNIST (8 classes).
+HF_TARGETS = {"vit": (HFViT, None), "vit-cub": (HFViT, 200), "vit-bloodmnist": (HFViT, 8),
+              "dino": (HFDinov2, None), "dino-cub": (HFDinov2, 200), "dino-bloodmnist": (HFDinov2, 8)}
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -1170,6 +1384,8 @@ def _load_local(model, ckpt):
     if isinstance(ckpt, str):
         ckpt = torch.load(ckpt, map_location="cpu", weights_only=True)
     sd = ckpt["model"] if isinstance(ckpt, dict) and "model" in ckpt else ckpt
+    if isinstance(model, _HFClassifier):             # transformers' key names -> the mirror's
+        sd = model.convert_state_dict(sd)
     model.load_state_dict(sd, strict=False)
     return model
 
@@ -1230,10 +1446,15 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
                                  % (target_name, image_size))
             layers, embed = CLIP_RESNETS[target_name]
             model = ClipResNet(layers, embed, image_size=image_size)
+        elif target_name in HF_TARGETS:
+            cls, width = HF_TARGETS[target_name]
+            model = cls(num_labels=width if width is not None else (2 if n_class is None else n_class),
+                        image_size=image_size)
         else:
             raise ValueError("unknown target model %r (offline build: breastclip, breastclip_vit, "
                              "breastclip_classifier, clip, clip_rn50, clip_rn101, resnet18, resnet18_places, resnet34, "
-                             "resnet50, resnet101, resnet152)" % (target_name,))
+                             "resnet50, resnet101, resnet152, vit, vit-cub, vit-bloodmnist, dino, dino-cub, "
+                             "dino-bloodmnist)" % (target_name,))
     if target_name == "resnet18_places":
         _load_places(model, ckpt)
     else:

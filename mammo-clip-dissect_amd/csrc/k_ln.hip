@@ -78,28 +78,41 @@ extern "C" int mcd_layer_norm(const float* x, int64_t rows, int64_t D, const flo
 
 // ---- K11: patch extraction for the ViT patch embedding ---------------------------------------------------------
 //   replaces  the Conv2d(3, dim, P, stride P) of the patch embedding (ViTPatchEmbeddings / conv1, the same reference
-//             sites as K9) by its GEMM form: rows of P*P*Cin pixels per patch, times the [dim, Cin*P*P] weight.
+//             sites as K9; Dinov2PatchEmbeddings at P = 14) by its GEMM form: rows of P*P*Cin pixels per patch, times
+//             the [dim, Cin*P*P] weight.
 // out is [B, 1 + nP, Cin*P*P]: row 0 of every image is zero (the class-token slot: the GEMM that follows adds the
 // residual operand there), row 1 + (py*nW + px) is patch (py, px) in (c, dy, dx) order -- the order of the conv
-// weight viewed as [dim, Cin*P*P].  One thread per float4 of the output: coalesced writes, 16-byte reads (P % 4 == 0).
+// weight viewed as [dim, Cin*P*P].  A pure permutation: one thread per vector V of the output, coalesced writes.
+//   P % 4 == 0: V = float4.  A patch row starts at float ((b*Cin + c)*H + y)*W + px*P of x, and W is a multiple of P:
+//               every term is a multiple of 4 floats, so each 16-byte piece of a patch row is 16-byte aligned.
+//   other even P (14 for DINOv2: a patch row is 56 bytes): V = float2.  W is a multiple of P, hence even, so the same
+//               sum is a multiple of 2 floats and so is every piece's offset 2*dx inside the row: 8-byte aligned
+//               wherever x is (16 bytes are asked of it).  On the output side Cin*P*P is a multiple of 4 for any even P.
+// Odd P would need 4-byte accesses and is refused.
 namespace {
 
+template <typename V> __device__ __forceinline__ V patchify_zero();
+template <> __device__ __forceinline__ float4 patchify_zero<float4>() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+template <> __device__ __forceinline__ float2 patchify_zero<float2>() { return make_float2(0.f, 0.f); }
+
+template <typename V>
 __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__ x, int B, int Cin, int H, int W, int P,
                                                         float* __restrict__ out) {
-    const int nW = W / P, nP = (H / P) * nW, F = Cin * P * P, F4 = F >> 2, P4 = P >> 2;
-    const int64_t total = (int64_t)B * (1 + nP) * F4;
+    constexpr int N = sizeof(V) / sizeof(float);
+    const int nW = W / P, nP = (H / P) * nW, F = Cin * P * P, FV = F / N, PV = P / N;
+    const int64_t total = (int64_t)B * (1 + nP) * FV;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int f4 = (int)(i % F4);
-        const int64_t row = i / F4;
+        const int fv = (int)(i % FV);
+        const int64_t row = i / FV;
         const int r = (int)(row % (1 + nP));
         const int64_t b = row / (1 + nP);
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        V v = patchify_zero<V>();
         if (r > 0) {
             const int p = r - 1, py = p / nW, px = p % nW;
-            const int dx4 = f4 % P4, dy = (f4 / P4) % P, c = f4 / (P4 * P);
-            v = *reinterpret_cast<const float4*>(x + ((b * Cin + c) * H + (py * P + dy)) * (int64_t)W + px * P + dx4 * 4);
+            const int dxv = fv % PV, dy = (fv / PV) % P, c = fv / (PV * P);
+            v = *reinterpret_cast<const V*>(x + ((b * Cin + c) * H + (py * P + dy)) * (int64_t)W + px * P + dxv * N);
         }
-        reinterpret_cast<float4*>(out)[i] = v;
+        reinterpret_cast<V*>(out)[i] = v;
     }
 }
 
@@ -108,16 +121,21 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
 extern "C" int mcd_patchify(const float* x, int64_t B, int64_t Cin, int64_t H, int64_t W, int64_t P, float* out,
                             mcd_stream_t stream) {
     MCD_REQUIRE(x && out, MCD_E_ARG, "mcd_patchify: NULL pointer");
-    MCD_REQUIRE(B >= 0 && Cin > 0 && P >= 4 && P % 4 == 0 && H > 0 && W > 0 && H % P == 0 && W % P == 0 && W % 4 == 0,
+    MCD_REQUIRE(B >= 0 && Cin > 0 && P >= 2 && P % 2 == 0 && H > 0 && W > 0 && H % P == 0 && W % P == 0,
                 MCD_E_UNSUPPORTED, "mcd_patchify: bad shape B=%lld Cin=%lld H=%lld W=%lld P=%lld", (long long)B,
                 (long long)Cin, (long long)H, (long long)W, (long long)P);
     MCD_REQUIRE(B < (1 << 30) && Cin * H * W < (1LL << 31), MCD_E_UNSUPPORTED, "mcd_patchify: image too large");
     MCD_REQUIRE(((uintptr_t)x) % 16 == 0 && ((uintptr_t)out) % 16 == 0, MCD_E_ARG, "mcd_patchify: pointers must be 16-byte aligned");
     if (B == 0) return MCD_OK;
-    const int64_t total = B * (1 + (H / P) * (W / P)) * (Cin * P * P / 4);
+    const int nvec = P % 4 == 0 ? 4 : 2;                  // floats per thread
+    const int64_t total = B * (1 + (H / P) * (W / P)) * (Cin * P * P / nvec);
     const unsigned grid = (unsigned)(mcd_cdiv(total, 256) < (1 << 20) ? mcd_cdiv(total, 256) : (1 << 20));
-    hipLaunchKernelGGL(patchify_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (int)B, (int)Cin, (int)H, (int)W,
-                       (int)P, out);
+    if (nvec == 4)
+        hipLaunchKernelGGL(patchify_kernel<float4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (int)B, (int)Cin, (int)H,
+                           (int)W, (int)P, out);
+    else
+        hipLaunchKernelGGL(patchify_kernel<float2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (int)B, (int)Cin, (int)H,
+                           (int)W, (int)P, out);
     MCD_LAUNCH_CHECK("patchify_kernel");
     return MCD_OK;
 }
