@@ -185,38 +185,24 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f32_kernel(const float* __rest
 // ds_read_b32 at ((q * 128 + row) * 4 + e) words -- rows r and r + 16 share a bank (two passes per read; the reads are 1/60 of the
 // MFMA time).  One barrier per K-tile hands over the tile that has landed and frees the stage the next one is issued into.
 // Same MFMA instruction over the same k order as the kernel above: the same bits.  10 000 x 763 x 512: 0.0812-0.0816 against
-// 0.0845-0.0848 ms; 3.95 against 4.14 us per K-tile in the steady state (profiles/r04_k1_ksweep.txt).  (KT = 16, three workgroups
-// per CU instead of two: the same time -- with one or two tiles per CU the launch is as long as a CU's two tiles.)
-// Round 5 (SPREAD = 1, the product): the NEXT K-tile's eight DMA instructions no longer sit back to back behind the barrier -- an LDS-DMA
+// 0.0845-0.0848 ms; 3.95 against 4.14 us per K-tile in the steady state (profiles/r04_k1_ksweep.txt).  (K-tiles of 16, three
+// workgroups per CU instead of two: the same time -- with one or two tiles per CU the launch is as long as a CU's two tiles.)
+// Round 5: the NEXT K-tile's eight DMA instructions do not sit back to back behind the barrier -- an LDS-DMA
 // instruction with no MFMA in flight costs its wave ~150 issue cycles, ~1 200 idle cycles of the matrix pipe per K-tile for a workgroup
 // that has its CU to itself -- but one behind every fourth MFMA of the tile's first half, with the fragments double-buffered one k-quad
 // ahead: 85.3 -> 81.4 us in cold-clock traces, 74.9 -> 70.9 us (0.70 of the fp32 MFMA peak) once the clock has ramped
 // (profiles/r05_k1_notes.txt, r05_k1_spread.txt; tests/test_k1s_isa_cpu.py pins the placement).
-template <bool KBLOCKS, int KT, int SPREAD = 1 /* 0: the next K-tile's DMA instructions all behind the barrier; 1: between this tile's MFMAs; 2: and the hand-over in front of the tile's last quad (the K loop below) */,
-          bool BST = true /* the output through a buffer descriptor (the epilogue below); host: M * ldc * 4 < 2^31 */>
-__global__ __launch_bounds__(256, KT == 16 ? 3 : 2) void gemm_nt_f32_dma_kernel(const float* __restrict__ A, int64_t lda,
+// (What else rounds 4-5 measured on this kernel and retired -- all DMA instructions behind the barrier, the hand-over moved in front
+// of the tile's last quad, wave priorities by progress, a 256 x 128 tile with one 512-thread workgroup per CU and two K-tiles in
+// flight: none faster, profiles/r05_k1_notes.txt, r05_k1_spread.txt, r05_k1_wide.txt; the code: scripts/README.md, archive row.)
+// BST: the output through a buffer descriptor (the epilogue below); host: max(M, BM) * ldc * 4 < 2^31, else the plain stores.
+template <bool KBLOCKS, bool BST>
+__global__ __launch_bounds__(256, 2) void gemm_nt_f32_dma_kernel(const float* __restrict__ A, int64_t lda,
                                                                const float* __restrict__ B, int64_t ldb, int64_t M,
                                                                int64_t Nc, int64_t Kd, float* __restrict__ Cc,
-                                                               int64_t ldc, int64_t kb_first, int64_t kb_step,
-                                                               unsigned long long* __restrict__ stamps /* dev build: s_memrealtime per workgroup, or null */,
-                                                               int fair /* dev build: priority experiment, see the K loop */) {
-    static_assert(KT == 32 || KT == 16, "K-tile depth");
-#ifdef MCD_DEV_KNOBS
-#define MCD_K1_STAMP(i_)                                                                                                 \
-    do {                                                                                                                 \
-        if (stamps && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 32 + (i_)] = __builtin_amdgcn_s_memrealtime();        \
-    } while (0)
-    if (stamps && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 32 + 7] = __builtin_amdgcn_s_getreg(63492);   // HW_ID
-#else
-#define MCD_K1_STAMP(i_) do { } while (0)
-    (void)stamps;
-#endif
-    MCD_K1_STAMP(0);
-#ifdef MCD_DEV_KNOBS
-    if (stamps && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 32 + 6] = __builtin_amdgcn_s_memtime();      // shader clock at entry ...
-#endif
-    constexpr int NI = KT / 8;                                                // DMA instructions per operand, wave and K-tile
-    __shared__ __attribute__((aligned(16))) float s_t[2][2 * BM * KT];      // [stage][A: KT/4 quads x 128 rows x 4 | B: likewise]
+                                                               int64_t ldc, int64_t kb_first, int64_t kb_step) {
+    constexpr int NI = BK / 8;                                                // DMA instructions per operand, wave and K-tile: 4
+    __shared__ __attribute__((aligned(16))) float s_t[2][2 * BM * BK];      // [stage][A: 8 quads x 128 rows x 4 | B: likewise]
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int wr = wave >> 1, wc = wave & 1;
@@ -224,17 +210,12 @@ __global__ __launch_bounds__(256, KT == 16 ? 3 : 2) void gemm_nt_f32_dma_kernel(
     if (!xcd_tile(M, Nc, tile_r, tile_c)) return;
     const int64_t row0 = (int64_t)tile_r * BM, col0 = (int64_t)tile_c * BN;
     const int fr = lane & 31, fk = lane >> 5;
-#ifdef MCD_DEV_KNOBS
-    const int wslot = (int)(__builtin_amdgcn_s_getreg(63492) & 0xfu);      // HW_ID.WAVE_ID: this wave's slot on its SIMD
-#else
-    (void)fair;
-#endif
 
     // DMA side: instruction j (0..3) of this wave moves the 16-byte units p = j * 256 + wave * 64 + lane, unit p = quad (p >> 7)
     // of row (p & 127); rows past the operand's last clamp to it (their products are never stored)
     const __amdgpu_buffer_rsrc_t ra_ = __builtin_amdgcn_make_buffer_rsrc((void*)A, 0, (int)(M * lda * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t rb_ = __builtin_amdgcn_make_buffer_rsrc((void*)B, 0, (int)(Nc * ldb * 4), 0x00020000);
-    unsigned va[4], vb[4];
+    unsigned va[NI], vb[NI];
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
         const int pu = j * 256 + (int)threadIdx.x;
@@ -244,28 +225,25 @@ __global__ __launch_bounds__(256, KT == 16 ? 3 : 2) void gemm_nt_f32_dma_kernel(
         vb[j] = (unsigned)((gb * ldb + 4 * q) * 4);
     }
     char* sb = reinterpret_cast<char*>(&s_t[0][0]);
+    // all 2 NI instructions of a K-tile (the prologue's)
 #define MCD_K1_DMA(stage_, k0_)                                                                                              \
     do {                                                                                                                     \
-        char* d_ = sb + (stage_) * (2 * BM * KT * 4) + wave * 1024;                                                          \
+        char* d_ = sb + (stage_) * (2 * BM * BK * 4) + wave * 1024;                                                          \
         const int so_ = (int)(k0_) * 4;                                                                                      \
         __builtin_amdgcn_raw_ptr_buffer_load_lds(ra_, (__attribute__((address_space(3))) void*)(d_), 16, va[0], so_, 0, 0);          \
         __builtin_amdgcn_raw_ptr_buffer_load_lds(ra_, (__attribute__((address_space(3))) void*)(d_ + 4096), 16, va[1], so_, 0, 0);   \
-        if constexpr (NI == 4) {                                                                                             \
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra_, (__attribute__((address_space(3))) void*)(d_ + 8192), 16, va[2], so_, 0, 0);  \
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(ra_, (__attribute__((address_space(3))) void*)(d_ + 12288), 16, va[3], so_, 0, 0); \
-        }                                                                                                                    \
-        char* e_ = d_ + BM * KT * 4;                                                                                         \
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra_, (__attribute__((address_space(3))) void*)(d_ + 8192), 16, va[2], so_, 0, 0);   \
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra_, (__attribute__((address_space(3))) void*)(d_ + 12288), 16, va[3], so_, 0, 0);  \
+        char* e_ = d_ + BM * BK * 4;                                                                                         \
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rb_, (__attribute__((address_space(3))) void*)(e_), 16, vb[0], so_, 0, 0);          \
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rb_, (__attribute__((address_space(3))) void*)(e_ + 4096), 16, vb[1], so_, 0, 0);   \
-        if constexpr (NI == 4) {                                                                                             \
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rb_, (__attribute__((address_space(3))) void*)(e_ + 8192), 16, vb[2], so_, 0, 0);  \
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rb_, (__attribute__((address_space(3))) void*)(e_ + 12288), 16, vb[3], so_, 0, 0); \
-        }                                                                                                                    \
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb_, (__attribute__((address_space(3))) void*)(e_ + 8192), 16, vb[2], so_, 0, 0);   \
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb_, (__attribute__((address_space(3))) void*)(e_ + 12288), 16, vb[3], so_, 0, 0);  \
     } while (0)
     // ONE of the wave's 2 NI instructions of a K-tile: j < NI operand A's unit block j, else operand B's j - NI
 #define MCD_K1_DMA1(stage_, k0_, j_)                                                                                         \
     do {                                                                                                                     \
-        char* d_ = sb + (stage_) * (2 * BM * KT * 4) + wave * 1024 + ((j_) < NI ? 0 : BM * KT * 4) + ((j_) % NI) * 4096;     \
+        char* d_ = sb + (stage_) * (2 * BM * BK * 4) + wave * 1024 + ((j_) < NI ? 0 : BM * BK * 4) + ((j_) % NI) * 4096;     \
         if ((j_) < NI) __builtin_amdgcn_raw_ptr_buffer_load_lds(ra_, (__attribute__((address_space(3))) void*)(d_), 16, va[(j_) % NI], (int)(k0_) * 4, 0, 0); \
         else __builtin_amdgcn_raw_ptr_buffer_load_lds(rb_, (__attribute__((address_space(3))) void*)(d_), 16, vb[(j_) % NI], (int)(k0_) * 4, 0, 0); \
     } while (0)
@@ -288,108 +266,58 @@ __global__ __launch_bounds__(256, KT == 16 ? 3 : 2) void gemm_nt_f32_dma_kernel(
     }
     // fragment reads: row (w? * 64 + m * 32 + fr), quad kk >> 2, element (kk & 3) + fk -- kk is even, so the quad is a compile-time
     // constant and the lane's own part of the address does not change over the K-tile
-    const int a_lane = ((wr * 64 + fr) * 4 + fk) * 4, b_lane = (BM * KT + (wc * 64 + fr) * 4 + fk) * 4;   // bytes
+    const int a_lane = ((wr * 64 + fr) * 4 + fk) * 4, b_lane = (BM * BK + (wc * 64 + fr) * 4 + fk) * 4;   // bytes
     int64_t k_end = KBLOCKS ? kb_first : Kd;
     MCD_K1_DMA(0, 0);
     int cur = 0;
-    [[maybe_unused]] float fa[2][2][2], fb[2][2][2];         // SPREAD: fragment registers, [buffer][mi | ni][k pair within the quad]
-    static_assert((KT / 4) % 2 == 0, "the fragment buffers' parity carries over from a K-tile's last quad to the next one's first");
-    for (int64_t k0 = 0; k0 < Kd; k0 += KT, cur ^= 1) {
-        if (SPREAD != 2 || k0 == 0) {                            // (SPREAD 2: the hand-over sits inside the previous tile's last quad)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // this wave's pieces of the tile have landed ...
-            __syncthreads();                                     // ... everyone's have, and everyone is done with the other stage
-        }
-        if (k0 == 0) MCD_K1_STAMP(1);
-        if (k0 == KT) MCD_K1_STAMP(2);
-        if (k0 / KT < 24) MCD_K1_STAMP(8 + (int)(k0 / KT));     // (dev build) every K-tile's start
-#ifdef MCD_DEV_KNOBS
-        // (dev build, MCD_GEMM_K1_FAIR: an experiment that lost.  Two workgroups share a CU, one wave of each per SIMD, and at equal
-        // priority the OLDER wave wins every MFMA issue slot both are ready for: the older workgroup runs almost as if alone, the
-        // younger gets what is left and finishes alone -- stamps of all 474 workgroups: K loop done after 44 us (alone on a CU) / 60
-        // (median) / 83 (max).  1: K-tile t of the wave in hardware wave slot w runs at priority (t ^ w) & 1; 2: a four-level ladder
-        // by progress.  Both make the pairs finish together, at 78-81 us, and the launch 1-3 % LONGER: the pair's throughput is what
-        // it is, profiles/r05_k1_notes.txt.)
-        if (fair == 1) {
-            if ((((int)(k0 / KT)) ^ wslot) & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-        } else if (fair == 2) {
-            const int lv = 3 - (int)((k0 / KT) >> 2);
-            if (lv >= 3) __builtin_amdgcn_s_setprio(3); else if (lv == 2) __builtin_amdgcn_s_setprio(2); else if (lv == 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-        }
-#endif
-        const char* st_ = sb + cur * (2 * BM * KT * 4);
-        if constexpr (SPREAD) {
-            // The next K-tile's 2 NI DMA instructions go out BETWEEN this tile's MFMAs, two per quad of k (8 MFMAs) in the tile's first
-            // half -- an LDS-DMA instruction that is not under MFMAs costs its wave ~150 cycles of issue (MI355X_MICROARCH.md, cycle
-            // constants), and eight of them behind the barrier were ~1 200 of the ~1 570 cycles a K-tile took beyond its 4 096 cycles
-            // of MFMAs when its workgroup had the CU to itself (profiles/r05_k1_notes.txt: 2.75 us per K-tile alone, 4.8 per pair).
-            // The fragments of quad q + 1 are read at the top of quad q (double-buffered registers); sched_barriers hold the
-            // written order.  Same MFMAs over the same k in the same order per accumulator: the same bits.
-            // SPREAD 2: the HAND-OVER to the next tile -- own pieces landed, own reads of this stage done, workgroup barrier, first
-            // fragments of the next tile -- sits in front of this tile's LAST quad of MFMAs, whose fragments are in registers: the
-            // eight MFMAs cover the LDS latency of the next tile's first reads, which the barrier at the loop's top left exposed.
-            const bool more = k0 + KT < Kd;
-            auto frag = [&](const char* stg, int qd, int bf) __attribute__((always_inline)) {
-                const char* base = stg + qd * (BM * 16);
+    float fa[2][2][2], fb[2][2][2];         // fragment registers, [buffer][mi | ni][k pair within the quad]
+    static_assert((BK / 4) % 2 == 0, "the fragment buffers' parity carries over from a K-tile's last quad to the next one's first");
+    for (int64_t k0 = 0; k0 < Kd; k0 += BK, cur ^= 1) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // this wave's pieces of the tile have landed ...
+        __syncthreads();                                     // ... everyone's have, and everyone is done with the other stage
+        const char* st_ = sb + cur * (2 * BM * BK * 4);
+        // The next K-tile's 2 NI DMA instructions go out BETWEEN this tile's MFMAs, two per quad of k (8 MFMAs) in the tile's first
+        // half -- an LDS-DMA instruction that is not under MFMAs costs its wave ~150 cycles of issue (MI355X_MICROARCH.md, cycle
+        // constants), and eight of them behind the barrier were ~1 200 of the ~1 570 cycles a K-tile took beyond its 4 096 cycles
+        // of MFMAs when its workgroup had the CU to itself (profiles/r05_k1_notes.txt: 2.75 us per K-tile alone, 4.8 per pair).
+        // The fragments of quad q + 1 are read at the top of quad q (double-buffered registers); sched_barriers hold the
+        // written order.  Same MFMAs over the same k in the same order per accumulator: the same bits.
+        const bool more = k0 + BK < Kd;
+        auto frag = [&](const char* stg, int qd, int bf) __attribute__((always_inline)) {
+            const char* base = stg + qd * (BM * 16);
 #pragma unroll
-                for (int m = 0; m < 2; ++m)
+            for (int m = 0; m < 2; ++m)
 #pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        fa[bf][m][h] = *reinterpret_cast<const float*>(base + a_lane + h * 8 + m * 32 * 16);
-                        fb[bf][m][h] = *reinterpret_cast<const float*>(base + b_lane + h * 8 + m * 32 * 16);
-                    }
-            };
-            if (SPREAD != 2 || k0 == 0) frag(st_, 0, 0);
+                for (int h = 0; h < 2; ++h) {
+                    fa[bf][m][h] = *reinterpret_cast<const float*>(base + a_lane + h * 8 + m * 32 * 16);
+                    fb[bf][m][h] = *reinterpret_cast<const float*>(base + b_lane + h * 8 + m * 32 * 16);
+                }
+        };
+        frag(st_, 0, 0);
 #pragma unroll
-            for (int qd = 0; qd < KT / 4; ++qd) {
-                const int c = qd & 1;
-                if (qd + 1 < KT / 4) frag(st_, qd + 1, c ^ 1);
-                else if (SPREAD == 2) {
-                    // (unconditional: behind the LAST tile the barrier is one more uniform barrier and the reads fetch a stale stage
-                    // into registers nobody uses -- a branch here would make hipcc's wait-count pass merge the two paths and wait
-                    // for the new reads in front of the quad's second MFMA)
-                    __builtin_amdgcn_sched_barrier(0);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __syncthreads();
-                    frag(sb + (cur ^ 1) * (2 * BM * KT * 4), 0, c ^ 1);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][0][0], fb[c][0][0], acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][0][0], fb[c][1][0], acc[0][1], 0, 0, 0);
-                if (qd < NI) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (more) MCD_K1_DMA1(cur ^ 1, k0 + KT, 2 * qd);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][1][0], fb[c][1][0], acc[1][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][1][0], fb[c][0][0], acc[1][0], 0, 0, 0);
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][0][1], fb[c][0][1], acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][0][1], fb[c][1][1], acc[0][1], 0, 0, 0);
-                if (qd < NI) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (more) MCD_K1_DMA1(cur ^ 1, k0 + KT, 2 * qd + 1);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][1][1], fb[c][1][1], acc[1][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][1][1], fb[c][0][1], acc[1][0], 0, 0, 0);
+        for (int qd = 0; qd < BK / 4; ++qd) {
+            const int c = qd & 1;
+            if (qd + 1 < BK / 4) frag(st_, qd + 1, c ^ 1);
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][0][0], fb[c][0][0], acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][0][0], fb[c][1][0], acc[0][1], 0, 0, 0);
+            if (qd < NI) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (more) MCD_K1_DMA1(cur ^ 1, k0 + BK, 2 * qd);
+                __builtin_amdgcn_sched_barrier(0);
             }
-        } else {
-        if (k0 + KT < Kd) MCD_K1_DMA(cur ^ 1, k0 + KT);
-#pragma unroll
-        for (int kk = 0; kk < KT; kk += 2) {
-            float a[2], b[2];
-            const int ko = ((kk >> 2) * BM * 4 + (kk & 3)) * 4;
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) a[mi] = *reinterpret_cast<const float*>(st_ + a_lane + ko + mi * 32 * 16);
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) b[ni] = *reinterpret_cast<const float*>(st_ + b_lane + ko + ni * 32 * 16);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni)
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][1][0], fb[c][1][0], acc[1][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][1][0], fb[c][0][0], acc[1][0], 0, 0, 0);
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][0][1], fb[c][0][1], acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][0][1], fb[c][1][1], acc[0][1], 0, 0, 0);
+            if (qd < NI) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (more) MCD_K1_DMA1(cur ^ 1, k0 + BK, 2 * qd + 1);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][1][1], fb[c][1][1], acc[1][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][1][1], fb[c][0][1], acc[1][0], 0, 0, 0);
         }
-        }   // !SPREAD
-        if (KBLOCKS && k0 + KT >= k_end) {                   // the block's chain ends with this tile: fold it
+        if (KBLOCKS && k0 + BK >= k_end) {                   // the block's chain ends with this tile: fold it
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
@@ -404,10 +332,6 @@ __global__ __launch_bounds__(256, KT == 16 ? 3 : 2) void gemm_nt_f32_dma_kernel(
     }
 #undef MCD_K1_DMA
 #undef MCD_K1_DMA1
-    MCD_K1_STAMP(3);
-#ifdef MCD_DEV_KNOBS
-    if (stamps && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 32 + 31] = __builtin_amdgcn_s_memtime();     // ... and behind the K loop
-#endif
     // C/D layout of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
     if constexpr (BST) {
         // The 64 values of a lane leave through ONE buffer descriptor based at the tile's first element and ending with the
@@ -434,187 +358,18 @@ __global__ __launch_bounds__(256, KT == 16 ? 3 : 2) void gemm_nt_f32_dma_kernel(
             }
     } else {
 #pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int64_t gr = row0 + wr * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * fk;
-                const int64_t gc = col0 + wc * 64 + ni * 32 + fr;
-                const float v = KBLOCKS ? tot[mi * KBLOCKS][ni * KBLOCKS][r] : acc[mi][ni][r];
-                if (gr < M && gc < Nc) Cc[gr * ldc + gc] = v;
-            }
-    }
-#ifdef MCD_DEV_KNOBS
-    if (stamps) {
-        MCD_K1_STAMP(4);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        MCD_K1_STAMP(5);
-    }
-#endif
-#undef MCD_K1_STAMP
-}
-
-#ifdef MCD_DEV_KNOBS
-// (DEV BUILD ONLY, MCD_GEMM_K1_WIDE=1 -- an experiment that lost: bit-identical, and 83.8 us against 80.6 at 10 000 x 763 x 512, 4.15
-// against 3.99 us per pair of K-tiles at K = 2 048: with BOTH waves of a SIMD in one workgroup every barrier idles the matrix pipe,
-// which the 128 x 128 form's second workgroup fills; profiles/r05_k1_notes.txt.)
-// WIDE form of the DMA kernel: ONE 512-thread workgroup per CU on a 256 x 128 tile (8 waves as 4 x 2, each 64 x 64 as above), a
-// ring of THREE 48 KB stages (A: 8 k-quads x 256 rows x 16 B, B: 8 x 128 x 16), so that TWO K-tiles are in flight behind the one
-// the MFMAs run on -- the 128 x 128 form's two workgroups per CU leave room for two stages each, one K-tile in flight, and its
-// K-tile period followed the L2's latency under load (profiles/r05_k1_notes.txt).  A wave's six DMA instructions of K-tile t + 2
-// go out between the MFMAs of tile t (one per quad of k, quads 0-5); the sync point in front of tile t waits for the wave's OWN
-// pieces of tile t by count (vmcnt(6): tile t + 1's six stay in flight) and the barrier behind it says that everyone's have landed
-// and that everyone is done reading tile t - 1, whose stage tile t + 2 is about to overwrite.  10 000 x 763: 40 x 6 = 240 tiles,
-// one round on 256 CUs.  Same MFMA instruction over the same k in the same order per accumulator as both kernels above: the same
-// bits.
-constexpr int WM = 256, W_STAGE = (WM + BN) * BK * 4, W_NSTAGE = 3;
-__device__ __forceinline__ bool xcd_tile_wide(int64_t M, int64_t Nc, int& tile_r, int& tile_c) {
-    const int ncol = (int)((Nc + BN - 1) / BN), nrow = (int)((M + WM - 1) / WM);
-    const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
-    tile_r = (seq / ncol) * 8 + xcd;
-    tile_c = seq % ncol;
-    return tile_r < nrow;
-}
-template <bool KBLOCKS>
-__global__ __launch_bounds__(512, 1) void gemm_nt_f32_wide_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ B,
-                                                                  int64_t ldb, int64_t M, int64_t Nc, int64_t Kd,
-                                                                  float* __restrict__ Cc, int64_t ldc, int64_t kb_first,
-                                                                  int64_t kb_step) {
-    constexpr int KT = BK, NQ = KT / 4;                  // k-quads per K-tile
-    extern __shared__ __attribute__((aligned(1024))) char w_smem[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int wr = wave >> 1, wc = wave & 1;
-    int tile_r, tile_c;
-    if (!xcd_tile_wide(M, Nc, tile_r, tile_c)) return;
-    const int64_t row0 = (int64_t)tile_r * WM, col0 = (int64_t)tile_c * BN;
-    const int fr = lane & 31, fk = lane >> 5;
-
-    // DMA side: A's 16-byte units p = j * 512 + thread (j = 0..3) = quad (p >> 8) of row (p & 255); B's p = j * 512 + thread
-    // (j = 0, 1) = quad (p >> 7) of row (p & 127); unit p of an operand lies at p * 16 in its part of the stage, so a wave's
-    // instruction fills 1 KB linearly.  Rows past the operand's last clamp to it (their products are never stored).
-    const __amdgpu_buffer_rsrc_t ra_ = __builtin_amdgcn_make_buffer_rsrc((void*)A, 0, (int)(M * lda * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb_ = __builtin_amdgcn_make_buffer_rsrc((void*)B, 0, (int)(Nc * ldb * 4), 0x00020000);
-    unsigned va[4], vb[2];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int pu = j * 512 + (int)threadIdx.x;
-        const int q = pu >> 8, r = pu & 255;
-        const int64_t ga = row0 + r < M ? row0 + r : M - 1;
-        va[j] = (unsigned)((ga * lda + 4 * q) * 4);
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int pu = j * 512 + (int)threadIdx.x;
-        const int q = pu >> 7, r = pu & 127;
-        const int64_t gb = col0 + r < Nc ? col0 + r : Nc - 1;
-        vb[j] = (unsigned)((gb * ldb + 4 * q) * 4);
-    }
-    // piece j (0..3: A, 4..5: B) of the K-tile at k0 into stage s
-#define MCD_KW_DMA1(s_, k0_, j_)                                                                                             \
-    do {                                                                                                                     \
-        char* d_ = w_smem + (s_) * W_STAGE + wave * 1024 + ((j_) < 4 ? (j_) * 8192 : WM * KT * 4 + ((j_) - 4) * 8192);      \
-        if ((j_) < 4) __builtin_amdgcn_raw_ptr_buffer_load_lds(ra_, (__attribute__((address_space(3))) void*)(d_), 16, va[(j_) & 3], (int)(k0_) * 4, 0, 0); \
-        else __builtin_amdgcn_raw_ptr_buffer_load_lds(rb_, (__attribute__((address_space(3))) void*)(d_), 16, vb[(j_) & 1], (int)(k0_) * 4, 0, 0); \
-    } while (0)
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
-    f32x16 tot[KBLOCKS ? 2 : 1][KBLOCKS ? 2 : 1];
-    if (KBLOCKS) {
-#pragma unroll
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) tot[mi * KBLOCKS][ni * KBLOCKS][r] = 0.f;
-    }
-    // fragment reads: A row (wr * 64 + m * 32 + fr), B row (wc * 64 + m * 32 + fr); quad q at q * rows * 16; element 2 h + fk
-    const int a_lane = ((wr * 64 + fr) * 4 + fk) * 4, b_lane = WM * KT * 4 + ((wc * 64 + fr) * 4 + fk) * 4;   // bytes
-    int64_t k_end = KBLOCKS ? kb_first : Kd;
-    // prologue: K-tiles 0 and 1 (host: Kd % KT == 0, Kd >= KT)
-#pragma unroll
-    for (int j = 0; j < 6; ++j) MCD_KW_DMA1(0, 0, j);
-    if (Kd > KT) {
-#pragma unroll
-        for (int j = 0; j < 6; ++j) MCD_KW_DMA1(1, KT, j);
-    }
-    float fa[2][2][2], fb[2][2][2];         // fragment registers, [buffer][mi | ni][k pair within the quad]
-    int cur = 0;
-    for (int64_t k0 = 0; k0 < Kd; k0 += KT) {
-        // own pieces of this tile landed (the six of the next tile, when there is one, stay in flight) ...
-        // (the bare barrier: __syncthreads() is a fence and waits vmcnt(0) -- it would take the second tile out of flight)
-        if (k0 + KT < Kd) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();     // ... everyone's have, and everyone is done with the stage of the tile before
-        asm volatile("" ::: "memory");
-        const char* st_ = w_smem + cur * W_STAGE;
-        const int nxt2 = cur >= 1 ? cur - 1 : 2;                 // (cur + 2) % 3: the stage of the tile before = of tile t + 2
-        const bool more2 = k0 + 2 * KT < Kd;
-        auto frag = [&](int qd, int bf) __attribute__((always_inline)) {
-            const char* ba = st_ + a_lane + qd * (WM * 16);
-            const char* bb = st_ + b_lane + qd * (BN * 16);
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    fa[bf][m][h] = *reinterpret_cast<const float*>(ba + h * 8 + m * 32 * 16);
-                    fb[bf][m][h] = *reinterpret_cast<const float*>(bb + h * 8 + m * 32 * 16);
+                for (int r = 0; r < 16; ++r) {
+                    const int64_t gr = row0 + wr * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * fk;
+                    const int64_t gc = col0 + wc * 64 + ni * 32 + fr;
+                    const float v = KBLOCKS ? tot[mi * KBLOCKS][ni * KBLOCKS][r] : acc[mi][ni][r];
+                    if (gr < M && gc < Nc) Cc[gr * ldc + gc] = v;
                 }
-        };
-        frag(0, 0);
-#pragma unroll
-        for (int qd = 0; qd < NQ; ++qd) {
-            const int c = qd & 1;
-            if (qd + 1 < NQ) frag(qd + 1, c ^ 1);
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][0][0], fb[c][0][0], acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][0][0], fb[c][1][0], acc[0][1], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][1][0], fb[c][1][0], acc[1][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][1][0], fb[c][0][0], acc[1][0], 0, 0, 0);
-            if (qd < 6) {
-                __builtin_amdgcn_sched_barrier(0);
-                if (more2) MCD_KW_DMA1(nxt2, k0 + 2 * KT, qd);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][0][1], fb[c][0][1], acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][0][1], fb[c][1][1], acc[0][1], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][1][1], fb[c][1][1], acc[1][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c][1][1], fb[c][0][1], acc[1][0], 0, 0, 0);
-        }
-        if (KBLOCKS && k0 + KT >= k_end) {                   // the block's chain ends with this tile: fold it
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        tot[mi * KBLOCKS][ni * KBLOCKS][r] += acc[mi][ni][r];
-                        acc[mi][ni][r] = 0.f;
-                    }
-            k_end = kb_step > 0 ? (k_end + kb_step < Kd ? k_end + kb_step : Kd) : Kd;
-        }
-        cur = cur == 2 ? 0 : cur + 1;
     }
-#undef MCD_KW_DMA1
-    // C/D layout of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int64_t gr = row0 + wr * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * fk;
-                const int64_t gc = col0 + wc * 64 + ni * 32 + fr;
-                const float v = KBLOCKS ? tot[mi * KBLOCKS][ni * KBLOCKS][r] : acc[mi][ni][r];
-                if (gr < M && gc < Nc) Cc[gr * ldc + gc] = v;
-            }
 }
-#endif   // MCD_DEV_KNOBS
 
 // MKL's K cut as observed (see the kernel comment): first boundary and the distance between the following ones
 // (0: none follow).  Returns false when there is a single block.
@@ -751,15 +506,13 @@ __global__ __launch_bounds__(256) void gemm_nt_bf16_kernel(const float* __restri
 
 // ---- large bf16 GEMM (stress shape: tens of thousands of images x thousands of concepts) -------------------
 // Operands are converted ONCE to bf16 (hi, and lo for the split mode) by split_bf16_kernel: rows of Kp = D rounded
-// up to 64 elements, zero padded, so the GEMM stages raw bytes.  256 x 256 output tile per 512-thread workgroup,
+// up to 64 elements, zero padded, so the GEMM stages raw bytes.  This kernel is the split mode's (MCD_GEMM_BF16X3; the
+// single-pass mode runs the persistent kernel further down): 256 x 256 output tile per 512-thread workgroup,
 // 8 waves as 2 (M) x 4 (N), each wave 128 x 64 = 4 x 2 tiles of v_mfma_f32_32x32x16_bf16 (128 accumulator
 // registers).  K-tiles of 32 elements go global -> LDS by global_load_lds_dwordx4 (no VGPR round trip, 16 B per
-// lane, the wave's 1 KB lands contiguously) into a RING of LDS stages: 4 stages of 32 KB (bf16) with the DMAs of
-// three K-tiles in flight across the barriers, or 2 stages of 64 KB (split mode, four arrays).
-// Why a ring: at D = 512 a tile's operands (512 KB) stream through L2 once per tile and the MFMA work of a K-tile
-// (0.4 us) is far shorter than an L2 round trip, so the loop runs at (bytes in flight per CU) / (L2 latency);
-// 96 KB in flight per CU instead of 24-32 KB is worth 1.7x.  The wait for stage t is a COUNTED s_waitcnt vmcnt
-// (the later stages stay in flight) followed by a raw s_barrier -- __syncthreads() would drain the DMAs.
+// lane, the wave's 1 KB lands contiguously) into two LDS stages of 64 KB (four arrays: A hi, A lo, B hi, B lo), the
+// DMAs of the next K-tile in flight under the MFMAs of this one.  The wait for stage t is an s_waitcnt vmcnt
+// followed by a raw s_barrier.
 // LDS image of a tile: row r (64 bytes) holds its four 16-byte chunks permuted, chunk c at position
 //   c ^ ((r / 4) % 4)
 // (the permutation is applied to the per-lane GLOBAL address, the LDS side of the DMA is lane-linear); the 16 lanes
@@ -845,25 +598,14 @@ __device__ __forceinline__ void stage_tile(const unsigned short* __restrict__ G,
     }
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else static_assert(N == 0, "add the literal");
-}
-
-template <bool SPLIT, bool NT_STORE>
 __global__ __launch_bounds__(GB_THREADS) void gemm_nt_bf16_big_kernel(
     const unsigned short* __restrict__ Ahi, const unsigned short* __restrict__ Alo,
     const unsigned short* __restrict__ Bhi, const unsigned short* __restrict__ Blo, int64_t Kp, int64_t M, int64_t Nc,
     float* __restrict__ Cc, int64_t ldc, int tiles_m, int tiles_n) {
-    constexpr int NARR = SPLIT ? 2 : 1;
-    constexpr int STAGE = 2 * NARR * GB_T_BYTES;   // A and B arrays of one K-tile: 32 KB / 64 KB
-    constexpr int NSTAGE = SPLIT ? 2 : 4;          // 128 KB of LDS either way
+    constexpr int STAGE = 4 * GB_T_BYTES;          // the four arrays of one K-tile: 64 KB
+    constexpr int NSTAGE = 2;                      // 128 KB of LDS
     constexpr int PD = NSTAGE - 1;                 // K-tiles in flight ahead of the one being consumed
-    constexpr int IPS = 4 * NARR;                  // DMA instructions per stage per wave
-    extern __shared__ __attribute__((aligned(1024))) char smem[];  // [NSTAGE][A hi, (A lo), B hi, (B lo)]
+    extern __shared__ __attribute__((aligned(1024))) char smem[];  // [NSTAGE][A hi, A lo, B hi, B lo]
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // tile of this workgroup (see the header comment)
@@ -889,29 +631,25 @@ __global__ __launch_bounds__(GB_THREADS) void gemm_nt_bf16_big_kernel(
     auto stage = [&](int t) {
         char* base = smem + (t % NSTAGE) * STAGE;
         stage_tile(Ahi, Kp, M, row0, t * GB_K, base, wave, lane);
-        if (SPLIT) stage_tile(Alo, Kp, M, row0, t * GB_K, base + GB_T_BYTES, wave, lane);
-        stage_tile(Bhi, Kp, Nc, col0, t * GB_K, base + NARR * GB_T_BYTES, wave, lane);
-        if (SPLIT) stage_tile(Blo, Kp, Nc, col0, t * GB_K, base + (NARR + 1) * GB_T_BYTES, wave, lane);
+        stage_tile(Alo, Kp, M, row0, t * GB_K, base + GB_T_BYTES, wave, lane);
+        stage_tile(Bhi, Kp, Nc, col0, t * GB_K, base + 2 * GB_T_BYTES, wave, lane);
+        stage_tile(Blo, Kp, Nc, col0, t * GB_K, base + 3 * GB_T_BYTES, wave, lane);
     };
     const int nt = (int)(Kp / GB_K);   // >= 2 (Kp is a multiple of 64)
 #pragma unroll
     for (int s0 = 0; s0 < PD; ++s0)
         if (s0 < nt) stage(s0);
     for (int t = 0; t < nt; ++t) {
-        // Stage t must have landed: everything issued so far except the min(PD-1, nt-1-t) later stages.  The counted
-        // wait covers this wave's DMAs, the barrier the other waves'; the barrier also says every wave is done with
-        // stage t-1, whose buffer the refill below overwrites.
-        const int later = nt - 1 - t;
-        if (PD >= 3 && later >= 2) wait_vmcnt<(PD >= 3 ? 2 : 0) * IPS>();
-        else if (PD >= 2 && later >= 1) wait_vmcnt<(PD >= 2 ? 1 : 0) * IPS>();
-        else wait_vmcnt<0>();
+        // Stage t must have landed: the wait covers this wave's DMAs, the barrier the other waves'; the barrier also
+        // says every wave is done with stage t-1, whose buffer the refill below overwrites.
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (t + PD < nt) stage(t + PD);
         const char* base = smem + (t % NSTAGE) * STAGE;
         const char* a_hi = base;
         const char* a_lo = base + GB_T_BYTES;
-        const char* b_hi = base + NARR * GB_T_BYTES;
+        const char* b_hi = base + 2 * GB_T_BYTES;
         const char* b_lo = b_hi + GB_T_BYTES;
 #pragma unroll
         for (int ks = 0; ks < GB_K / 16; ++ks) {
@@ -921,23 +659,22 @@ __global__ __launch_bounds__(GB_THREADS) void gemm_nt_bf16_big_kernel(
                 const int r = wr * 128 + mi * 32 + fr;
                 const int o = r * GB_RB + gb_pos(r, 2 * ks + fh) * 16;
                 ah[mi] = *reinterpret_cast<const bf16x8*>(a_hi + o);
-                if (SPLIT) al[mi] = *reinterpret_cast<const bf16x8*>(a_lo + o);
+                al[mi] = *reinterpret_cast<const bf16x8*>(a_lo + o);
             }
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni) {
                 const int r = wc * 64 + ni * 32 + fr;
                 const int o = r * GB_RB + gb_pos(r, 2 * ks + fh) * 16;
                 bh[ni] = *reinterpret_cast<const bf16x8*>(b_hi + o);
-                if (SPLIT) bl[ni] = *reinterpret_cast<const bf16x8*>(b_lo + o);
+                bl[ni] = *reinterpret_cast<const bf16x8*>(b_lo + o);
             }
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
                 for (int ni = 0; ni < 2; ++ni) {
-                    if (SPLIT) {  // small terms first
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[mi], bh[ni], acc[mi][ni], 0, 0, 0);
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bl[ni], acc[mi][ni], 0, 0, 0);
-                    }
+                    // small terms first
+                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[mi], bh[ni], acc[mi][ni], 0, 0, 0);
+                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bl[ni], acc[mi][ni], 0, 0, 0);
                     acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mi], bh[ni], acc[mi][ni], 0, 0, 0);
                 }
         }
@@ -952,10 +689,7 @@ __global__ __launch_bounds__(GB_THREADS) void gemm_nt_bf16_big_kernel(
             for (int r = 0; r < 16; ++r) {
                 const int64_t gr = row0 + wr * 128 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
                 const int64_t gc = col0 + wc * 64 + ni * 32 + fr;
-                if (interior || (gr < M && gc < Nc)) {
-                    if (NT_STORE) __builtin_nontemporal_store(acc[mi][ni][r], Cc + gr * ldc + gc);
-                    else Cc[gr * ldc + gc] = acc[mi][ni][r];
-                }
+                if (interior || (gr < M && gc < Nc)) __builtin_nontemporal_store(acc[mi][ni][r], Cc + gr * ldc + gc);
             }
 }
 
@@ -978,10 +712,7 @@ __global__ __launch_bounds__(GB_THREADS) void gemm_nt_bf16_big_kernel(
 // Ablation at 50 000 x 10 000 x 512 (whole call, 0.06 ms of it the bf16 conversion): MFMAs + barriers + fragment
 // reads alone 0.39 ms; + DMA 0.53; + stores 0.54; everything 0.70 ms.  Loads and stores ADD: the kernel sits on the
 // CU <-> L2 interface (about 40 GB/s per CU for 28 KB staged + 12 KB stored per K-tile), not on the matrix pipe.
-#ifndef MCD_GP_LW
-#define MCD_GP_LW 4
-#endif
-constexpr int GP_LW = MCD_GP_LW;   // loader waves
+constexpr int GP_LW = 4;   // loader waves
 constexpr int GP_M = 192, GP_N = 256, GP_WAVES = 8 + GP_LW, GP_THREADS = 64 * GP_WAVES, GP_NSTAGE = 5, GP_PD = GP_NSTAGE - 1;
 constexpr int GP_A_BYTES = GP_M * GB_RB, GP_B_BYTES = GP_N * GB_RB, GP_STAGE = GP_A_BYTES + GP_B_BYTES;  // 12 + 16 KB
 constexpr int GP_AP = GP_A_BYTES / 1024 / GP_LW, GP_BP = GP_B_BYTES / 1024 / GP_LW;   // 1 KB pieces per loader: 6 + 8
@@ -1013,7 +744,6 @@ struct TileWalk {   // the tiles of one persistent workgroup, in order
     __device__ __forceinline__ int count() const { return slot < n_seq ? (n_seq - slot + nslot - 1) / nslot : 0; }
 };
 
-template <bool NT_STORE>
 __global__ __launch_bounds__(GP_THREADS) void gemm_nt_bf16_persist_kernel(
     const unsigned short* __restrict__ A, const unsigned short* __restrict__ B, int64_t Kp, int64_t M, int64_t Nc,
     float* __restrict__ Cc, int64_t ldc, int tiles_m, int tiles_n) {
@@ -1129,8 +859,7 @@ __global__ __launch_bounds__(GP_THREADS) void gemm_nt_bf16_persist_kernel(
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         float* dst = tile + (int64_t)(mi * 32 + (r & 3) + 8 * (r >> 2)) * ldc + ni * 32 + c_lane;
-                        if (NT_STORE) __builtin_nontemporal_store(acc[mi][ni][r], dst);
-                        else *dst = acc[mi][ni][r];
+                        __builtin_nontemporal_store(acc[mi][ni][r], dst);
                     }
         } else {
 #pragma unroll
@@ -1257,9 +986,6 @@ __global__ __launch_bounds__(256) void normalize_to_bf16_kernel(const float* __r
 }
 
 #include "k_gexp_v6.inc"
-#ifdef MCD_DEV_KNOBS
-#include "k_gexp_v7.inc"   // the two-accumulator-set form (VERDICT r4 #1b): built, measured, lost (profiles/r05_gexp_v6.txt (m)); dev library only
-#endif
 
 // rinv[n] = 1 / sum_t part[t][n]: the partial row sums of the 2 * tiles_m (concept tile, wave row) pairs.  64 images
 // per workgroup x 4 interleaved slices of t, folded in a fixed order.
@@ -1296,29 +1022,31 @@ __global__ __launch_bounds__(256) void gexp_zero_pad_kernel(unsigned short* __re
 
 }  // namespace
 
-// Development knobs (timing ablations and kernel variants for scripts/*.sh) are read from the environment ONLY in the dev build
-// (`make dev` -> libmcd_hip_dev.so, -DMCD_DEV_KNOBS, selected with MCD_LIB_PATH) through mcd_dev_knob (mcd_common.h).  The product
-// library compiles them out: it takes the defaults, carries none of the ablation kernels (several of which return wrong results
-// by design), and refuses a set MCD_GEMM_EXP_ABLATE instead of silently measuring something else.
+// This file reads no development knob: the variants rounds 4-5 measured against these kernels were retired (DESIGN.md section 8;
+// scripts/README.md, archive row, names the commit that builds them).  The one environment variable it looks at is a retired knob
+// that mcd_embed_gemm_exp refuses instead of silently measuring something else.
 static int64_t gemm_kp(int64_t D) { return (D + 63) / 64 * 64; }
 // the 256 x 256-tile kernel pays once the tiles outnumber the 256 CUs several times over
 static bool gemm_use_big(int64_t N, int64_t C) { return mcd_cdiv(N, GB_M) * mcd_cdiv(C, GB_N) >= 512; }
+
+// CUs of the current device (the persistent kernels launch one workgroup per CU)
+static int gemm_cu_count() {
+    static int n_cu_dev[MCD_MAX_DEVICES];
+    const int dev = mcd_cur_device();
+    int& n_cu = n_cu_dev[dev];
+    if (n_cu == 0) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
+        if (n_cu < 8) n_cu = 256;
+    }
+    return n_cu;
+}
 
 extern "C" size_t mcd_embed_gemm_workspace(int64_t N, int64_t C, int64_t D, int mode) {
     if (mode == MCD_GEMM_F32 || !gemm_use_big(N, C)) return 0;
     const size_t arrays = (mode == MCD_GEMM_BF16X3) ? 2 : 1;
     return arrays * (size_t)(N + C) * (size_t)gemm_kp(D) * sizeof(unsigned short);
 }
-
-#ifdef MCD_DEV_KNOBS
-static unsigned long long* g_k1_stamps = nullptr;
-// dev build only: the stamps of the last fp32 DMA-form launch (32 per workgroup: entry, first tile landed, second tile landed, K loop
-// done, stores issued, stores done, -, HW_ID, then the start of every K-tile), copied to the host
-extern "C" int mcd_dev_k1_stamps(unsigned long long* out, int workgroups) {
-    if (!g_k1_stamps || workgroups > 4096) return -1;
-    return hipMemcpy(out, g_k1_stamps, (size_t)workgroups * 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
-}
-#endif
 
 extern "C" int mcd_embed_gemm(const float* I, int64_t ldi, const float* T, int64_t ldt, int64_t N, int64_t C,
                               int64_t D, int mode, float* P, int64_t ldp, void* ws, size_t ws_bytes,
@@ -1332,7 +1060,7 @@ extern "C" int mcd_embed_gemm(const float* I, int64_t ldi, const float* T, int64
     hipStream_t st = (hipStream_t)stream;
     const size_t need = mcd_embed_gemm_workspace(N, C, D, mode);
     if (need > 0 && ws && ws_bytes >= need && ((uintptr_t)ws) % 16 == 0 && N < (1LL << 31) && C < (1LL << 31)) {
-        // ---- large bf16 path: convert once, then the 256 x 256 DMA-staged kernel ----
+        // ---- large bf16 path: convert once, then a DMA-staged kernel (split: 256 x 256 tiles; single pass: persistent) ----
         const bool split = mode == MCD_GEMM_BF16X3;
         const int64_t Kp = gemm_kp(D);
         unsigned short* a_hi = (unsigned short*)ws;
@@ -1344,64 +1072,37 @@ extern "C" int mcd_embed_gemm(const float* I, int64_t ldi, const float* T, int64
         hipLaunchKernelGGL(split_bf16_kernel, dim3(ga), dim3(256), 0, st, I, ldi, N, D, Kp, a_hi, a_lo);
         hipLaunchKernelGGL(split_bf16_kernel, dim3(gb), dim3(256), 0, st, T, ldt, C, D, Kp, b_hi, b_lo);
         MCD_LAUNCH_CHECK("split_bf16_kernel");
-        const int tiles_m = (int)mcd_cdiv(N, GB_M), tiles_n = (int)mcd_cdiv(C, GB_N);
-        const int64_t nbands = mcd_cdiv(tiles_m, GB_RS);
-        const int64_t grid64 = mcd_cdiv(nbands, 8) * 8 * GB_RS * tiles_n;
-        MCD_REQUIRE(grid64 < (1LL << 31), MCD_E_UNSUPPORTED, "mcd_embed_gemm: too many tiles for one launch");
-        const size_t shmem = 8u * (size_t)GB_T_BYTES;   // 4 stages x 2 arrays, or 2 stages x 4 arrays: 128 KB
-        static const int nt_store = mcd_dev_knob("MCD_GEMM_NT_STORE", 1);
-        static bool attr_done_dev[MCD_MAX_DEVICES];
-        bool& attr_done = attr_done_dev[mcd_cur_device()];
-        if (!attr_done) {
-            hipError_t e1 = hipFuncSetAttribute((const void*)gemm_nt_bf16_big_kernel<true, false>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 8 * GB_T_BYTES);
-            hipError_t e2 = hipFuncSetAttribute((const void*)gemm_nt_bf16_big_kernel<true, true>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 8 * GB_T_BYTES);
-            hipError_t e3 = hipFuncSetAttribute((const void*)gemm_nt_bf16_big_kernel<false, false>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 8 * GB_T_BYTES);
-            hipError_t e4 = hipFuncSetAttribute((const void*)gemm_nt_bf16_big_kernel<false, true>,
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 8 * GB_T_BYTES);
-            MCD_REQUIRE(e1 == hipSuccess && e2 == hipSuccess && e3 == hipSuccess && e4 == hipSuccess, MCD_E_LAUNCH,
-                        "mcd_embed_gemm: cannot reserve 128 KB of LDS");
-            attr_done = true;
-        }
-#define MCD_GEMM_BIG(SP, NTS)                                                                                       \
-    hipLaunchKernelGGL((gemm_nt_bf16_big_kernel<SP, NTS>), dim3((unsigned)grid64), dim3(GB_THREADS), shmem, st, a_hi, \
-                       a_lo, b_hi, b_lo, Kp, N, C, P, ldp, tiles_m, tiles_n)
-        static const int no_persist = mcd_dev_knob("MCD_GEMM_NO_PERSIST", 0);
-        if (split) { if (nt_store) MCD_GEMM_BIG(true, true); else MCD_GEMM_BIG(true, false); }
-        else if (no_persist) { if (nt_store) MCD_GEMM_BIG(false, true); else MCD_GEMM_BIG(false, false); }
-        else {
-            static int n_cu_dev[MCD_MAX_DEVICES];
-            int& n_cu = n_cu_dev[mcd_cur_device()];
-            if (n_cu == 0) {
-                int dev = 0;
-                hipDeviceProp_t prop;
-                if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-                    n_cu = prop.multiProcessorCount;
-                if (n_cu < 8) n_cu = 256;
+        if (split) {
+            const int tiles_m = (int)mcd_cdiv(N, GB_M), tiles_n = (int)mcd_cdiv(C, GB_N);
+            const int64_t nbands = mcd_cdiv(tiles_m, GB_RS);
+            const int64_t grid64 = mcd_cdiv(nbands, 8) * 8 * GB_RS * tiles_n;
+            MCD_REQUIRE(grid64 < (1LL << 31), MCD_E_UNSUPPORTED, "mcd_embed_gemm: too many tiles for one launch");
+            const size_t shmem = 8u * (size_t)GB_T_BYTES;   // 2 stages x 4 arrays: 128 KB
+            static bool attr_done_dev[MCD_MAX_DEVICES];
+            bool& attr_done = attr_done_dev[mcd_cur_device()];
+            if (!attr_done) {
+                MCD_REQUIRE(hipFuncSetAttribute((const void*)gemm_nt_bf16_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                8 * GB_T_BYTES) == hipSuccess,
+                            MCD_E_LAUNCH, "mcd_embed_gemm: cannot reserve 128 KB of LDS");
+                attr_done = true;
             }
+            hipLaunchKernelGGL(gemm_nt_bf16_big_kernel, dim3((unsigned)grid64), dim3(GB_THREADS), shmem, st, a_hi, a_lo, b_hi,
+                               b_lo, Kp, N, C, P, ldp, tiles_m, tiles_n);
+        } else {
             static bool attr2_dev[MCD_MAX_DEVICES];
             bool& attr2 = attr2_dev[mcd_cur_device()];
             if (!attr2) {
-                hipError_t e1 = hipFuncSetAttribute((const void*)gemm_nt_bf16_persist_kernel<true>,
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, GP_NSTAGE * GP_STAGE);
-                hipError_t e2 = hipFuncSetAttribute((const void*)gemm_nt_bf16_persist_kernel<false>,
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, GP_NSTAGE * GP_STAGE);
-                MCD_REQUIRE(e1 == hipSuccess && e2 == hipSuccess, MCD_E_LAUNCH, "mcd_embed_gemm: cannot reserve 128 KB of LDS");
+                MCD_REQUIRE(hipFuncSetAttribute((const void*)gemm_nt_bf16_persist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                GP_NSTAGE * GP_STAGE) == hipSuccess,
+                            MCD_E_LAUNCH, "mcd_embed_gemm: cannot reserve 128 KB of LDS");
                 attr2 = true;
             }
             const int ptiles_m = (int)mcd_cdiv(N, GP_M), ptiles_n = (int)mcd_cdiv(C, GP_N);
             MCD_REQUIRE((int64_t)GP_M * ldp < (1LL << 31), MCD_E_UNSUPPORTED, "mcd_embed_gemm: ldp too large");
-            const unsigned pgrid = (unsigned)((n_cu / 8) * 8);   // one workgroup per CU, a multiple of the 8 XCDs
-            if (nt_store)
-                hipLaunchKernelGGL(gemm_nt_bf16_persist_kernel<true>, dim3(pgrid), dim3(GP_THREADS), GP_NSTAGE * GP_STAGE, st,
-                                   a_hi, b_hi, Kp, N, C, P, ldp, ptiles_m, ptiles_n);
-            else
-                hipLaunchKernelGGL(gemm_nt_bf16_persist_kernel<false>, dim3(pgrid), dim3(GP_THREADS), GP_NSTAGE * GP_STAGE, st,
-                                   a_hi, b_hi, Kp, N, C, P, ldp, ptiles_m, ptiles_n);
+            const unsigned pgrid = (unsigned)((gemm_cu_count() / 8) * 8);   // one workgroup per CU, a multiple of the 8 XCDs
+            hipLaunchKernelGGL(gemm_nt_bf16_persist_kernel, dim3(pgrid), dim3(GP_THREADS), GP_NSTAGE * GP_STAGE, st, a_hi, b_hi, Kp,
+                               N, C, P, ldp, ptiles_m, ptiles_n);
         }
-#undef MCD_GEMM_BIG
         MCD_LAUNCH_CHECK("gemm_nt_bf16_big_kernel");
         return MCD_OK;
     }
@@ -1413,70 +1114,24 @@ extern "C" int mcd_embed_gemm(const float* I, int64_t ldi, const float* T, int64
     if (mode == MCD_GEMM_F32) {
         int64_t kb_first = D, kb_step = 0;
         const bool kblocks = gemm_kblocks(D, kb_first, kb_step);
-#define MCD_GEMM_LAUNCH_F32(AL, KB)                                                                                     \
-    hipLaunchKernelGGL((gemm_nt_f32_kernel<AL, KB>), grid, dim3(256), 0, st, I, ldi, T, ldt, N, C, D, P, ldp, kb_first, \
-                       kb_step)
-        unsigned long long* k1_stamps = nullptr;
-        const int k1_fair = mcd_dev_knob("MCD_GEMM_K1_FAIR", 0);
-        // (dev knob: 0 = the next K-tile's DMA instructions all behind the barrier, as in rounds 4-5; 1 = between the tile's MFMAs, the product;
-        // 2 = and the hand-over to the next tile in front of the last quad's MFMAs -- measured equal to 1, profiles/r05_k1_notes.txt)
-        const int k1_spread = mcd_dev_knob("MCD_GEMM_K1_SPREAD", 1);
-        (void)k1_spread;
-        // the output through a buffer descriptor: 31-bit byte offsets from the tile's first element (dev knob MCD_GEMM_K1_BST=0: the plain stores)
-        // (the kernel forms 32-bit offsets for all BM rows of a tile: with N < BM the tile's extent bounds them, or rows past N wrap
-        // back inside the descriptor -- pinned by tests/test_gpu_abi_contracts.py::test_embed_gemm_wide_pitch_keeps_the_gap)
-        const bool bst = (N > BM ? N : BM) * ldp * 4 < (1LL << 31) && mcd_dev_knob("MCD_GEMM_K1_BST", 1) != 0;
-#ifdef MCD_DEV_KNOBS
-        // dev build, MCD_GEMM_K1_STAMPS=1: s_memrealtime stamps of every workgroup (scripts/k1_stamps.py reads them through mcd_dev_k1_stamps)
-        if (mcd_dev_knob("MCD_GEMM_K1_STAMPS", 0) && g64 <= 4096) {
-            if (!g_k1_stamps) (void)hipMalloc((void**)&g_k1_stamps, 4096 * 32 * sizeof(unsigned long long));
-            k1_stamps = g_k1_stamps;
-        }
-#endif
         // the DMA form: every K-tile whole and inside one K-block, 16-byte aligned rows, 31-bit byte offsets
         const bool dma = aligned && D % BK == 0 && kb_first % BK == 0 && kb_step % BK == 0 && N * ldi < (1LL << 29) &&
                          C * ldt < (1LL << 29);
-#ifdef MCD_DEV_KNOBS
-        // (dev build, MCD_GEMM_K1_WIDE=1: the wide form -- 256 x 128 tiles, one workgroup per CU, two K-tiles in flight -- wherever the DMA
-        // preconditions hold; measured slower than the 128 x 128 form, see the kernel)
-        {
-            const bool wide = dma && mcd_dev_knob("MCD_GEMM_K1_WIDE", 0) == 1 && !k1_stamps;
-            if (wide) {
-                static bool wattr[MCD_MAX_DEVICES];
-                bool& wa = wattr[mcd_cur_device()];
-                if (!wa) {
-                    hipError_t e1 = hipFuncSetAttribute((const void*)gemm_nt_f32_wide_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, W_NSTAGE * W_STAGE);
-                    hipError_t e2 = hipFuncSetAttribute((const void*)gemm_nt_f32_wide_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, W_NSTAGE * W_STAGE);
-                    MCD_REQUIRE(e1 == hipSuccess && e2 == hipSuccess, MCD_E_LAUNCH, "mcd_embed_gemm: cannot reserve 144 KB of LDS");
-                    wa = true;
-                }
-                const int64_t wg64 = mcd_cdiv(mcd_cdiv(N, WM), 8) * 8 * mcd_cdiv(C, BN);   // see xcd_tile_wide()
-                if (kblocks) hipLaunchKernelGGL((gemm_nt_f32_wide_kernel<true>), dim3((unsigned)wg64), dim3(512), W_NSTAGE * W_STAGE, st, I, ldi, T, ldt, N, C, D, P, ldp, kb_first, kb_step);
-                else hipLaunchKernelGGL((gemm_nt_f32_wide_kernel<false>), dim3((unsigned)wg64), dim3(512), W_NSTAGE * W_STAGE, st, I, ldi, T, ldt, N, C, D, P, ldp, kb_first, kb_step);
-                MCD_LAUNCH_CHECK("gemm_nt_f32_wide_kernel");
-                return MCD_OK;
-            }
-        }
-#endif
-        if (kblocks) {
-#ifdef MCD_DEV_KNOBS
-            if (dma && k1_spread == 0) hipLaunchKernelGGL((gemm_nt_f32_dma_kernel<true, BK, 0>), grid, dim3(256), 0, st, I, ldi, T, ldt, N, C, D, P, ldp, kb_first, kb_step, k1_stamps, k1_fair);
-            else if (dma && k1_spread == 2) hipLaunchKernelGGL((gemm_nt_f32_dma_kernel<true, BK, 2>), grid, dim3(256), 0, st, I, ldi, T, ldt, N, C, D, P, ldp, kb_first, kb_step, k1_stamps, k1_fair);
-            else
-#endif
-            if (dma && bst) hipLaunchKernelGGL((gemm_nt_f32_dma_kernel<true, BK, 1, true>), grid, dim3(256), 0, st, I, ldi, T, ldt, N, C, D, P, ldp, kb_first, kb_step, k1_stamps, k1_fair);
-            else if (dma) hipLaunchKernelGGL((gemm_nt_f32_dma_kernel<true, BK, 1, false>), grid, dim3(256), 0, st, I, ldi, T, ldt, N, C, D, P, ldp, kb_first, kb_step, k1_stamps, k1_fair);
-            else if (aligned) MCD_GEMM_LAUNCH_F32(true, true); else MCD_GEMM_LAUNCH_F32(false, true);
-        } else {
-#ifdef MCD_DEV_KNOBS
-            if (dma && k1_spread == 0) hipLaunchKernelGGL((gemm_nt_f32_dma_kernel<false, BK, 0>), grid, dim3(256), 0, st, I, ldi, T, ldt, N, C, D, P, ldp, kb_first, kb_step, k1_stamps, k1_fair);
-            else if (dma && k1_spread == 2) hipLaunchKernelGGL((gemm_nt_f32_dma_kernel<false, BK, 2>), grid, dim3(256), 0, st, I, ldi, T, ldt, N, C, D, P, ldp, kb_first, kb_step, k1_stamps, k1_fair);
-            else
-#endif
-            if (dma && bst) hipLaunchKernelGGL((gemm_nt_f32_dma_kernel<false, BK, 1, true>), grid, dim3(256), 0, st, I, ldi, T, ldt, N, C, D, P, ldp, kb_first, kb_step, k1_stamps, k1_fair);
-            else if (dma) hipLaunchKernelGGL((gemm_nt_f32_dma_kernel<false, BK, 1, false>), grid, dim3(256), 0, st, I, ldi, T, ldt, N, C, D, P, ldp, kb_first, kb_step, k1_stamps, k1_fair);
-            else if (aligned) MCD_GEMM_LAUNCH_F32(true, false); else MCD_GEMM_LAUNCH_F32(false, false);
-        }
+        // its output through a buffer descriptor: 31-bit byte offsets from the tile's first element
+        // (the kernel forms 32-bit offsets for all BM rows of a tile: with N < BM the tile's extent bounds them, or rows past N wrap
+        // back inside the descriptor -- pinned by tests/test_gpu_abi_contracts.py::test_embed_gemm_wide_pitch_keeps_the_gap)
+        const bool bst = (N > BM ? N : BM) * ldp * 4 < (1LL << 31);
+#define MCD_GEMM_LAUNCH_F32(...) \
+    hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(256), 0, st, I, ldi, T, ldt, N, C, D, P, ldp, kb_first, kb_step)
+#define MCD_GEMM_F32_FORM(KB)                                                 \
+    do {                                                                      \
+        if (dma && bst) MCD_GEMM_LAUNCH_F32(gemm_nt_f32_dma_kernel<KB, true>); \
+        else if (dma) MCD_GEMM_LAUNCH_F32(gemm_nt_f32_dma_kernel<KB, false>);  \
+        else if (aligned) MCD_GEMM_LAUNCH_F32(gemm_nt_f32_kernel<true, KB>);   \
+        else MCD_GEMM_LAUNCH_F32(gemm_nt_f32_kernel<false, KB>);               \
+    } while (0)
+        if (kblocks) MCD_GEMM_F32_FORM(true); else MCD_GEMM_F32_FORM(false);
+#undef MCD_GEMM_F32_FORM
 #undef MCD_GEMM_LAUNCH_F32
     } else if (mode == MCD_GEMM_BF16X3) {
         if (aligned) MCD_GEMM_LAUNCH(gemm_nt_bf16_kernel<true, true>); else MCD_GEMM_LAUNCH(gemm_nt_bf16_kernel<false, true>);
@@ -1492,13 +1147,7 @@ extern "C" int mcd_embed_gemm(const float* I, int64_t ldi, const float* T, int64
 // ---- K1s host side ---------------------------------------------------------------------------------------------
 static int64_t gexp_ldpart(int64_t N) { return (N + 63) / 64 * 64; }
 // the kernel walks K in ring rounds of four 32-deep k-steps: the operand image is zero-padded to a multiple of 128
-static int64_t gexp_kp(int64_t D) {
-    int64_t kp = (D + 127) / 128 * 128;
-#ifdef MCD_DEV_KNOBS
-    if (kp < 512 && mcd_dev_knob("MCD_GEMM_EXP_V7", 0)) kp = 512;      // k_gexp_v7.inc: sixteen k-steps carry a tile's epilogue
-#endif
-    return kp;
-}
+static int64_t gexp_kp(int64_t D) { return (D + 127) / 128 * 128; }
 
 // bytes of the two bf16 operand copies (fragment-major: the row counts rounded up to whole 16-row blocks, the concept blocks
 // in pairs), rounded to 256 bytes
@@ -1596,120 +1245,33 @@ extern "C" int mcd_embed_gemm_exp(const float* I, int64_t ldi, const float* T, i
         hipLaunchKernelGGL(split_bf16_kernel, dim3(gb), dim3(256), 0, st, I, ldi, N, D, Kp, b_bf, (unsigned short*)nullptr, (int64_t)-2, 1.0f);
         MCD_LAUNCH_CHECK("split_bf16_kernel");
     }
-    static int n_cu_dev[MCD_MAX_DEVICES];
     const int dev = mcd_cur_device();
-    if (n_cu_dev[dev] == 0) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu_dev[dev] = prop.multiProcessorCount;
-        if (n_cu_dev[dev] < 8) n_cu_dev[dev] = 256;
-    }
-    const unsigned pgrid = (unsigned)((n_cu_dev[dev] / 8) * 8);       // one persistent workgroup per CU, a multiple of the 8 XCDs
-#ifndef MCD_DEV_KNOBS
-    // the product library reads no environment variable: a set ablation knob is refused instead of silently ignored
-    MCD_REQUIRE(!(getenv("MCD_GEMM_EXP_ABLATE") && atoi(getenv("MCD_GEMM_EXP_ABLATE")) != 0), MCD_E_UNSUPPORTED,
-                "mcd_embed_gemm_exp: MCD_GEMM_EXP_ABLATE is set but this is the product library (the ablation kernels live in "
-                "libmcd_hip_dev.so: make -C mammo-clip-dissect_amd/csrc dev; MCD_LIB_PATH)");
-#endif
+    const unsigned pgrid = (unsigned)((gemm_cu_count() / 8) * 8);       // one persistent workgroup per CU, a multiple of the 8 XCDs
+    // A set ablation knob is refused instead of silently ignored.  Read on EVERY call, not cached: a caller may set
+    // it after earlier calls in the same process (tests/test_gpu_kernels.py::test_product_library_refuses_the_ablation_knob).
+    const char* ablate_env = getenv("MCD_GEMM_EXP_ABLATE");
+    MCD_REQUIRE(!(ablate_env && atoi(ablate_env) != 0), MCD_E_UNSUPPORTED,
+                "mcd_embed_gemm_exp: MCD_GEMM_EXP_ABLATE is set, but the ablation kernels were retired: neither the product library "
+                "nor libmcd_hip_dev.so carries them (their measurements: profiles/r05_gexp_v6.txt; the commit that builds them: "
+                "scripts/README.md, archive row)");
     // late start of the workgroups with the shorter tile walk (k_gexp_v6.inc), in cycles of one tile period: ~1 200 per k-step
-    // + ~7 000 of boundary phase (dev knob MCD_GEMM_EXP_STAGGER: 0 = off)
-    const int stagger = mcd_dev_knob("MCD_GEMM_EXP_STAGGER", (int)(Kp / 32) * 1200 + 7000);
-#define MCD_GEXP6(AB, OV, AX)                                                                                            \
-    do {                                                                                                                 \
-        static bool attr[MCD_MAX_DEVICES];                                                                               \
-        if (!attr[dev]) {                                                                                                \
-            MCD_REQUIRE(hipFuncSetAttribute((const void*)gemm_nt_bf16_exp_v6_kernel<AB, G6_PLACE_PRODUCT, OV, AX>,                      \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, G6_LDS) == hipSuccess,           \
-                        MCD_E_LAUNCH, "mcd_embed_gemm_exp: cannot reserve the LDS ring");                                \
-            attr[dev] = true;                                                                                            \
-        }                                                                                                                \
-        hipLaunchKernelGGL((gemm_nt_bf16_exp_v6_kernel<AB, G6_PLACE_PRODUCT, OV, AX>), dim3(pgrid), dim3(256), G6_LDS, st, a_bf, b_bf, Kp, C, N, \
-                           E, ldE, part, ldpart, s1, (int)mcd_cdiv(C, 256), (int)mcd_cdiv(N, 256), stagger);             \
-        ++launches;                                                                                                      \
-    } while (0)
-#ifdef MCD_DEV_KNOBS
-#define MCD_GEXP7(AB)                                                                                                    \
-    do {                                                                                                                 \
-        static bool attr7[MCD_MAX_DEVICES];                                                                              \
-        if (!attr7[dev]) {                                                                                               \
-            MCD_REQUIRE(hipFuncSetAttribute((const void*)gemm_nt_bf16_exp_v7_kernel<AB, 2>,                              \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, G7_LDS) == hipSuccess,           \
-                        MCD_E_LAUNCH, "mcd_embed_gemm_exp: cannot reserve the LDS ring");                                \
-            attr7[dev] = true;                                                                                           \
-        }                                                                                                                \
-        hipLaunchKernelGGL((gemm_nt_bf16_exp_v7_kernel<AB, 2>), dim3(pgrid), dim3(256), G7_LDS, st, a_bf, b_bf, Kp, C, N, \
-                           E, ldE, part, ldpart, s1, (int)mcd_cdiv(C, 256), (int)mcd_cdiv(N, 128));                      \
-        ++launches;                                                                                                      \
-    } while (0)
-#endif
+    // + ~7 000 of boundary phase
+    const int stagger = (int)(Kp / 32) * 1200 + 7000;
+    static bool attr[MCD_MAX_DEVICES];
+    if (!attr[dev]) {
+        MCD_REQUIRE(hipFuncSetAttribute((const void*)gemm_nt_bf16_exp_v6_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, G6_LDS) ==
+                        hipSuccess,
+                    MCD_E_LAUNCH, "mcd_embed_gemm_exp: cannot reserve the LDS ring");
+        attr[dev] = true;
+    }
     int launches = 0;
     gexp_time_mark(dev, 0, st, 0);
-#ifdef MCD_DEV_KNOBS
-    // timing experiments (scripts/r05_*.sh; several return wrong results by design).  MCD_GEMM_EXP_ABLATE: 1 no E stores, 2 all
-    // stores into one L2-sized window, 4 K loop only, 8 / 9 in-kernel stamps (product / no stores: scripts/gexp_v4_stamps.py);
-    // MCD_GEMM_EXP_OVERLAP: 0 / 1 / 2 k-steps of the next tile riding the epilogue (product: 2); MCD_GEMM_EXP_STAUX: cache-policy
-    // bits of the E stores, 0 plain / 1 sc0 / 16 sc1 (product: 2 = nt)
-    const int ablate = mcd_dev_knob("MCD_GEMM_EXP_ABLATE", 0), ov = mcd_dev_knob("MCD_GEMM_EXP_OVERLAP", 2), ax = mcd_dev_knob("MCD_GEMM_EXP_STAUX", 2);
-    if (mcd_dev_knob("MCD_GEMM_EXP_V7", 0) && Kp >= 512) {
-        const int ab7 = ablate;
-        for (int rep_ = 0; rep_ < (g_gexp_time > 1 ? g_gexp_time : 1); ++rep_) {
-            if (ab7 == 1) MCD_GEXP7(1); else if (ab7 == 4) MCD_GEXP7(4); else if (ab7 == 8) MCD_GEXP7(8); else if (ab7 == 9) MCD_GEXP7(9); else MCD_GEXP7(0);
-        }
-    } else if (ablate == 4) MCD_GEXP6(4, 0, 2);
-    else if (ov == 0) { if (ablate == 1) MCD_GEXP6(1, 0, 2); else if (ablate == 8) MCD_GEXP6(8, 0, 2); else if (ablate == 9) MCD_GEXP6(9, 0, 2); else MCD_GEXP6(0, 0, 2); }
-    else if (ov == 1) { if (ablate == 1) MCD_GEXP6(1, 1, 2); else if (ablate == 8) MCD_GEXP6(8, 1, 2); else if (ablate == 9) MCD_GEXP6(9, 1, 2); else MCD_GEXP6(0, 1, 2); }
-    else if (ablate == 1) MCD_GEXP6(1, 2, 2);
-    else if (ablate == 2) MCD_GEXP6(2, 2, 2);
-    else if (ablate == 8) MCD_GEXP6(8, 2, 2);
-    else if (ablate == 9) MCD_GEXP6(9, 2, 2);
-    else if (ablate == 24) MCD_GEXP6(24, 2, 2);
-    else if (ablate == 40) MCD_GEXP6(40, 2, 2);
-    else if (ablate == 72) MCD_GEXP6(72, 2, 2);
-    else if (ablate == 120) MCD_GEXP6(120, 2, 2);
-    else if (ablate == 128) MCD_GEXP6(128, 2, 2);
-    else if (ablate == 256) MCD_GEXP6(256, 2, 2);
-    else if (ablate == 264) MCD_GEXP6(264, 2, 2);
-    else if (ablate == 512) MCD_GEXP6(512, 2, 2);
-    else if (ablate == 1024) MCD_GEXP6(1024, 2, 2);
-    else if (ablate == 1792) MCD_GEXP6(1792, 2, 2);
-    else if (ablate == 2048) MCD_GEXP6(2048, 2, 2);
-    else if (ablate == 4096) MCD_GEXP6(4096, 2, 2);
-    else if (ablate == 2049) MCD_GEXP6(2049, 2, 2);
-    else if (mcd_dev_knob("MCD_GEMM_EXP_PLACE", G6_PLACE_PRODUCT) != G6_PLACE_PRODUCT) {
-        // where a plain k-step's 24 memory instructions sit among its 64 MFMAs (g6_op_after: 0 / 1 / 2) + 16 x the walk of the
-        // MFMAs over the 8 x 8 block grid (g6_walk_mi / g6_walk_nj: 0 row-major, 1 serpentine, 2 quads, 3 column-major, 4 column serpentine)
-        const int pl_ = mcd_dev_knob("MCD_GEMM_EXP_PLACE", G6_PLACE_PRODUCT);
-        static bool attrp[MCD_MAX_DEVICES][8];
-#define MCD_GEXP6P(P, SLOT)                                                                                              \
-    do {                                                                                                                 \
-        if (!attrp[dev][SLOT]) {                                                                                         \
-            MCD_REQUIRE(hipFuncSetAttribute((const void*)gemm_nt_bf16_exp_v6_kernel<0, P, 2, 2>,                         \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, G6_LDS) == hipSuccess,           \
-                        MCD_E_LAUNCH, "mcd_embed_gemm_exp: cannot reserve the LDS ring");                                \
-            attrp[dev][SLOT] = true;                                                                                     \
-        }                                                                                                                \
-        hipLaunchKernelGGL((gemm_nt_bf16_exp_v6_kernel<0, P, 2, 2>), dim3(pgrid), dim3(256), G6_LDS, st, a_bf, b_bf, Kp, C, N, \
-                           E, ldE, part, ldpart, s1, (int)mcd_cdiv(C, 256), (int)mcd_cdiv(N, 256), stagger);             \
-        ++launches;                                                                                                      \
-    } while (0)
-        for (int rep_ = 0; rep_ < (g_gexp_time > 1 ? g_gexp_time : 1); ++rep_) {
-            if (pl_ == 0) MCD_GEXP6P(0, 0); else if (pl_ == 2) MCD_GEXP6P(2, 1); else if (pl_ == 1) MCD_GEXP6P(1, 2);
-            else if (pl_ == 17) MCD_GEXP6P(17, 3); else if (pl_ == 33) MCD_GEXP6P(33, 4); else if (pl_ == 49) MCD_GEXP6P(49, 5);
-            else if (pl_ == 65) MCD_GEXP6P(65, 6);
-            else MCD_REQUIRE(false, MCD_E_UNSUPPORTED, "mcd_embed_gemm_exp: MCD_GEMM_EXP_PLACE is one of 0, 1, 2, 17, 33, 49, 65");
-        }
-#undef MCD_GEXP6P
+    for (int rep_ = 0; rep_ < (g_gexp_time > 1 ? g_gexp_time : 1); ++rep_) {   // (timing: the same launch, back to back)
+        hipLaunchKernelGGL(gemm_nt_bf16_exp_v6_kernel, dim3(pgrid), dim3(256), G6_LDS, st, a_bf, b_bf, Kp, C, N, E, ldE, part,
+                           ldpart, s1, (int)mcd_cdiv(C, 256), (int)mcd_cdiv(N, 256), stagger);
+        ++launches;
     }
-    else if (ax == 0) MCD_GEXP6(0, 2, 0);
-    else if (ax == 1) MCD_GEXP6(0, 2, 1);
-    else if (ax == 16) MCD_GEXP6(0, 2, 16);
-    else
-#endif
-    for (int rep_ = 0; rep_ < (g_gexp_time > 1 ? g_gexp_time : 1); ++rep_) MCD_GEXP6(0, 2, 2);   // (timing: the same launch, back to back)
     gexp_time_mark(dev, 1, st, launches);
-#undef MCD_GEXP6
-#ifdef MCD_DEV_KNOBS
-#undef MCD_GEXP7
-#endif
     MCD_LAUNCH_CHECK("gemm_nt_bf16_exp_v6_kernel");
     hipLaunchKernelGGL(rowsum_finish_kernel, dim3((unsigned)mcd_cdiv(N, 64)), dim3(256), 0, st, part, ldpart,
                        2 * (int)mcd_cdiv(C, 256), N, rinv);

@@ -1,5 +1,5 @@
-// k_gexp_v6.inc -- K1s, round 5: included by k_gemm.hip inside its anonymous namespace (behind k_gexp_v4.inc, whose helpers,
-// ring constants and operand image it shares).
+// k_gexp_v6.inc -- K1s, round 5: included by k_gemm.hip inside its anonymous namespace, which provides the tile walk (TileWalkR),
+// pack_bf16, the vector types and the fragment-major operand image (frag_major_off).
 //   replaces  image_features @ text_features.T  (concept_vit/utils.py:594)  fused with  softmax(a * clip_feats, dim=1)'s
 //   numerator (concept_vit/similarity.py:54), stress chain only (bf16, no parity claim).
 //
@@ -16,7 +16,7 @@
 //     over the 4 pieces of an image block, leaves the sum over the wave's 128 concepts in every row of a 16 x 16 block: 32 MFMAs
 //     (3 % of the tile's 1 024) replace 128 v_pk_add_f32 + 16 cross-lane shuffles, and the sum is the sum of the bf16 values that
 //     are stored (S = E * rinv then sums to 1 over what K4s reads).
-//   * OVERLAP (template parameter): the epilogue of tile i runs INSIDE the first two k-steps of tile i + 1.  A k-step's MFMAs
+//   * the epilogue of tile i runs INSIDE the first two k-steps of tile i + 1.  A k-step's MFMAs
 //     are dealt by image block (column-major): behind the epilogue of column nj come the 16 MFMAs of column nj -- k-steps 0 and
 //     1, whose fragments are both register sets -- so the vector work of one column rides the matrix work of the previous one
 //     (a v_mfma_f32_16x16x32_bf16 holds the vector issue for 8 of its 16 cycles: MI355X_MICROARCH.md, cycle constants).
@@ -24,9 +24,14 @@
 //     (G6_DMA_ASM below) -- every instruction beside an MFMA is an issue slot of the one wave that feeds the matrix pipe AND the
 //     DMA path, and the K loop of a 256 x 256 tile waits for that path (profiles/r05_gexp_v6.txt (k), (o)).
 //
+// (Rounds 4-5 carried this kernel's timing ablations, other placements and walks of a k-step, other cache policies of the E stores,
+// the epilogue behind its own tile or inside ONE k-step, and a two-accumulator-set form, scripts/archive/k_gexp_v7.inc, as template parameters and a
+// second kernel.  All measured, none faster: profiles/r05_gexp_v6.txt, r04_gexp_place.txt, r05_mfma_order.txt, r05_store_exp.txt.
+// They were retired; scripts/README.md's archive row names the commit that builds them.)
+//
 // Registers (per lane):  v0..v59 compiler | v60..v63 constant block | v[64 + 4 (6 mi + nj)] block (mi, nj < 6) | a[4 (2 mi + nj - 6)] block (mi, nj >= 6)
 //   a[64 + 64 s + 4 i] A fragment i of set s | a[96 + 64 s + 4 j] B fragment j of set s | a196..a199 constant block (C of a tile's first MFMAs on
-//   the AGPR blocks) | a204..a207 the row-sum block (a208..a211: the second one of k_gexp_v7.inc) | a[212 + 4 nj] selector fragment of image block nj.
+//   the AGPR blocks) | a204..a207 the row-sum block | a[212 + 4 nj] selector fragment of image block nj.
 #ifndef MCD_K_GEXP_V6_INC
 #define MCD_K_GEXP_V6_INC
 
@@ -37,7 +42,6 @@ constexpr int G6_SLOT = 32768;       // one k-step of the ring: A pieces 0..15 |
 constexpr int G6_RING = 4 * G6_SLOT;
 constexpr int G6_LT = 8192;          // per-wave transposition buffers: 2 x (16 images x 256 B)
 constexpr int G6_LDS = G6_RING + 4 * G6_LT;
-constexpr bool G6_ASMDMA = true;    // the plain k-steps' DMA pieces as asm statements with the M0 write one MFMA ahead
 constexpr int G6_IMM = 1;           // 1: a k-step's K-tile offset rides the DMA instruction's immediate field (0: in the scalar offset)
 
 template <int I> using g6_ic = std::integral_constant<int, I>;
@@ -53,43 +57,16 @@ __device__ __forceinline__ float g6_acc() {
     return x;
 }
 
-// Where a k-step's 24 memory instructions sit in its stream of 64 MFMAs (k = 8 mi + nj): the code of the operation issued
-// behind MFMA k -- 0 none, 1 + i DMA piece i, 9 + i A fragment i, 17 + i B fragment i of the next k-step.
-//   PLACE 0: row i carries piece i, A i, B i (behind its MFMAs 1, 3, 5).
-//   PLACE 1: the 16 fragment reads in rows 0-3 (behind MFMAs 1, 3, 5, 7), the 8 pieces in rows 4-7 (behind MFMAs 1 and 5): the
-//            last read is 32 MFMAs old at the sync point's lgkmcnt(0) instead of 2 (the product; profiles/r04_gexp_place.txt).
-//   PLACE 2: pieces in rows 0-1, reads in rows 2-5, rows 6-7 bare.
-template <int PLACE>
+// Where a k-step's 24 memory instructions sit in its stream of 64 MFMAs (k = 8 mi + nj, row-major over the wave tile's 8 x 8 block
+// grid, block (mi, nj) = A fragment mi x B fragment nj): the code of the operation issued behind MFMA k -- 0 none, 1 + i DMA piece i,
+// 9 + i A fragment i, 17 + i B fragment i of the next k-step.  The 16 fragment reads in rows 0-3 (behind MFMAs 1, 3, 5, 7), the 8
+// pieces in rows 4-7 (behind MFMAs 1 and 5): the last read is 32 MFMAs old at the sync point's lgkmcnt(0) (profiles/r04_gexp_place.txt;
+// the other placements and the other walks of the grid that were measured: profiles/r05_mfma_order.txt, r05_gexp_v6.txt (g)).
 constexpr int g6_op_after(int k) {
     const int row = k >> 3, c = k & 7;
-    if (PLACE == 0) return c == 1 ? 1 + row : c == 3 ? 9 + row : c == 5 ? 17 + row : 0;
-    if (PLACE == 1) {
-        if (row < 4) return c == 1 ? 9 + 2 * row : c == 3 ? 17 + 2 * row : c == 5 ? 10 + 2 * row : c == 7 ? 18 + 2 * row : 0;
-        return c == 1 ? 1 + 2 * (row - 4) : c == 5 ? 2 + 2 * (row - 4) : 0;
-    }
-    if (row < 2) return (c & 1) ? 1 + 4 * row + (c >> 1) : 0;
-    if (row < 6) return c == 1 ? 9 + 2 * (row - 2) : c == 3 ? 17 + 2 * (row - 2) : c == 5 ? 10 + 2 * (row - 2) : c == 7 ? 18 + 2 * (row - 2) : 0;
-    return 0;
+    if (row < 4) return c == 1 ? 9 + 2 * row : c == 3 ? 17 + 2 * row : c == 5 ? 10 + 2 * row : c == 7 ? 18 + 2 * row : 0;
+    return c == 1 ? 1 + 2 * (row - 4) : c == 5 ? 2 + 2 * (row - 4) : 0;
 }
-
-
-// The WALK of a plain k-step's 64 MFMAs over the wave tile's 8 x 8 block grid (block (mi, nj) = A fragment mi x B fragment nj), the
-// template parameter's bits 4 and up.  The product's results do not depend on it (every block is touched once per k-step); what the
-// chip SUSTAINS does: the bare MFMA loop on K1s' register picture runs at 1.80-1.87 PFLOP/s row-major (A held for eight MFMAs, B
-// changing at every one), 2.00 serpentine, 2.04 in 2 x 2 quads, 2.11 with the same two operands throughout -- the same 16.4 cycles per
-// MFMA at 1.76-1.83 / 1.95 / 2.00 / 2.07 GHz (scripts/micro/mfma_order.hip, profiles/r05_mfma_order.txt): operand fetches that
-// repeat the previous MFMA's cost less power, and the clock is what this kernel is short of (profiles/r05_gexp_v6.txt (g)).
-//   0 row-major (k = 8 mi + nj; rounds 2-5)   1 serpentine (odd rows backwards: one operand changes per step)
-//   2 2 x 2 quads in Z-order                  3 column-major   4 column-major serpentine
-template <int WALK>
-constexpr int g6_walk_mi(int k) {
-    return WALK == 2 ? ((k >> 4) & 3) * 2 + ((k >> 1) & 1) : WALK == 3 ? (k & 7) : WALK == 4 ? (((k >> 3) & 1) ? 7 - (k & 7) : (k & 7)) : k >> 3;
-}
-template <int WALK>
-constexpr int g6_walk_nj(int k) {
-    return WALK == 1 ? (((k >> 3) & 1) ? 7 - (k & 7) : (k & 7)) : WALK == 2 ? ((k >> 2) & 3) * 2 + (k & 1) : (WALK == 3 || WALK == 4) ? k >> 3 : (k & 7);
-}
-constexpr int G6_PLACE_PRODUCT = 1;      // placement 1, walk 0 (dev knob MCD_GEMM_EXP_PLACE = placement + 16 x walk)
 constexpr int g6_acc_reg(int mi, int nj) { return nj < 6 ? 64 + 4 * (6 * mi + nj) : 4 * (2 * mi + nj - 6); }
 constexpr int G6_FRAG0 = 64, G6_CB0 = 196, G6_RS0 = 204, G6_SEL0 = 212;
 constexpr int G6_NVGPR = 60, G6_VCB0 = 60;     // the compiler's registers end at v59; v60..v63: the constant block of the VGPR-resident accumulators
@@ -130,9 +107,8 @@ __device__ __forceinline__ void g6_read(unsigned addr) {
 //   2. the 16-byte piece into the transposition buffer;
 //   3. the row-sum MFMA on the piece (C = 0 for the column's first); at least two instructions lie between the piece's last
 //      write and this read.
-template <int P, int NJ, bool NOEXP = false>
+template <int P, int NJ>
 __device__ __forceinline__ void g6_epi_exp() {
-    if constexpr (NOEXP) return;
     constexpr int b0 = g6_acc_reg(2 * P, NJ), b1 = g6_acc_reg(2 * P + 1, NJ);
     asm volatile(
         "v_exp_f32 v%c0, v%c0\n\tv_exp_f32 v%c1, v%c1\n\tv_exp_f32 v%c2, v%c2\n\tv_exp_f32 v%c3, v%c3\n\t"
@@ -144,13 +120,8 @@ __device__ __forceinline__ void g6_epi_exp() {
 // the same with MFMAs of the NEXT tile's first two k-steps between the exponentials (the overlapped boundary phase): blocks
 // (MI0, NJ0), (MI0 + 1, NJ0) of k-step 0 (register set 0, C = the constant block) and, when NJ1 >= 0, blocks (MI0, NJ1),
 // (MI0 + 1, NJ1) of k-step 1 (set 1, C = the block) -- columns whose epilogue is done, NJ1 one behind NJ0.  All VGPR-resident.
-template <int P, int NJ, int MI0, int NJ0, int NJ1, bool NOEXP = false>
+template <int P, int NJ, int MI0, int NJ0, int NJ1>
 __device__ __forceinline__ void g6_epi_exp_mm() {
-    if constexpr (NOEXP) {     // (timing only: the MFMAs without the exponentials and packs)
-        g6_mfma<MI0, NJ0, 0, true>(); g6_mfma<MI0 + 1, NJ0, 0, true>();
-        if constexpr (NJ1 >= 0) { g6_mfma<MI0, NJ1 < 0 ? 0 : NJ1, 1, false>(); g6_mfma<MI0 + 1, NJ1 < 0 ? 0 : NJ1, 1, false>(); }
-        return;
-    }
     static_assert(NJ0 < 6 && NJ1 < 6, "VGPR-resident blocks only");
     constexpr int b0 = g6_acc_reg(2 * P, NJ), b1 = g6_acc_reg(2 * P + 1, NJ);
     constexpr int d0 = g6_acc_reg(MI0, NJ0), d1 = g6_acc_reg(MI0 + 1, NJ0), fa0 = G6_FRAG0 + 4 * MI0, fa1 = fa0 + 4, fb = G6_FRAG0 + 32 + 4 * NJ0;
@@ -235,13 +206,6 @@ __device__ __forceinline__ void g6_claim_registers() {
     asm volatile("" ::: "a0", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "a9", "a10", "a11", "a12", "a13", "a14", "a15", "a16", "a17", "a18", "a19", "a20", "a21", "a22", "a23", "a24", "a25", "a26", "a27", "a28", "a29", "a30", "a31", "a32", "a33", "a34", "a35", "a36", "a37", "a38", "a39", "a40", "a41", "a42", "a43", "a44", "a45", "a46", "a47", "a48", "a49", "a50", "a51", "a52", "a53", "a54", "a55", "a56", "a57", "a58", "a59", "a60", "a61", "a62", "a63", "a64", "a65", "a66", "a67", "a68", "a69", "a70", "a71", "a72", "a73", "a74", "a75", "a76", "a77", "a78", "a79", "a80", "a81", "a82", "a83", "a84", "a85", "a86", "a87", "a88", "a89", "a90", "a91", "a92", "a93", "a94", "a95", "a96", "a97", "a98", "a99", "a100", "a101", "a102", "a103", "a104", "a105", "a106", "a107", "a108", "a109", "a110", "a111", "a112", "a113", "a114", "a115", "a116", "a117", "a118", "a119", "a120", "a121", "a122", "a123", "a124", "a125", "a126", "a127", "a128", "a129", "a130", "a131", "a132", "a133", "a134", "a135", "a136", "a137", "a138", "a139", "a140", "a141", "a142", "a143", "a144", "a145", "a146", "a147", "a148", "a149", "a150", "a151", "a152", "a153", "a154", "a155", "a156", "a157", "a158", "a159", "a160", "a161", "a162", "a163", "a164", "a165", "a166", "a167", "a168", "a169", "a170", "a171", "a172", "a173", "a174", "a175", "a176", "a177", "a178", "a179", "a180", "a181", "a182", "a183", "a184", "a185", "a186", "a187", "a188", "a189", "a190", "a191", "a192", "a193", "a194", "a195", "a196", "a197", "a198", "a199", "a200", "a201", "a202", "a203", "a204", "a205", "a206", "a207", "a208", "a209", "a210", "a211", "a212", "a213", "a214", "a215", "a216", "a217", "a218", "a219", "a220", "a221", "a222", "a223", "a224", "a225", "a226", "a227", "a228", "a229", "a230", "a231", "a232", "a233", "a234", "a235", "a236", "a237", "a238", "a239", "a240", "a241", "a242", "a243", "a244", "a245", "a246", "a247", "a248", "a249", "a250", "a251", "a252", "a253", "a254", "a255");
 }
 
-// ABLATE: 0 product, 1 no E stores, 2 every tile's stores into one L2-resident window, 4 K loop only (no epilogue at all),
-// 8 s_memtime stamps (+1: without the stores; + 16 no LDS transposition, + 32 no exponentials / packs, + 64 no row-sum MFMAs:
-// what each part of the boundary phase costs, profiles/r05_gexp_v6.txt (i)); 128 / 256: the plain k-steps without every other /
-// without any workgroup barrier, 512 / 1024: without their DMA pieces / without their fragment reads (what each costs the K loop, (k)).
-// OVERLAP: 1 / 2 = the epilogue of tile i inside the first k-step / the first two k-steps of tile i + 1 (see the header); 0: the
-// epilogue behind its own tile.
-template <int ABLATE, int PLACE, int OVERLAP, int STAUX = 2 /* cache-policy bits of the E stores: 2 = nt (profiles/r05_gexp_v6.txt); 0 / 1 / 16: timing experiments */>
 __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) void gemm_nt_bf16_exp_v6_kernel(
     const unsigned short* __restrict__ A /* concepts, fragment-major, paired, pre-scaled by a log2(e) */,
     const unsigned short* __restrict__ B /* images, fragment-major */, int64_t Kp, int64_t Mc, int64_t Ni,
@@ -287,9 +251,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) 
 #define G6_BLK(nrb_, b_) ((((b_) < (nrb_)) ? (b_) : (nrb_) - 1) * nt * 1024)
 #define G6_SET_TILE(tm_, tn_)                                                        \
     do {                                                                             \
-        /* (ABLATE 2048, timing only: every tile reads the XCD's FIRST concept tile and image tile 0 -- the operand stream */ \
-        /* without L2 misses; 4096: the concept tile as in the product, image tile 0) */ \
-        const int ba_ = ((ABLATE & 2048) ? W.xcd : (tm_)) * 16 + 4 * wave, bb_ = ((ABLATE & (2048 | 4096)) ? 0 : (tn_)) * 16 + 4 * wave; \
+        const int ba_ = (tm_) * 16 + 4 * wave, bb_ = (tn_) * 16 + 4 * wave;         \
         oa0 = G6_BLK(nrbA, ba_); oa1 = G6_BLK(nrbA, ba_ + 1); oa2 = G6_BLK(nrbA, ba_ + 2); oa3 = G6_BLK(nrbA, ba_ + 3); \
         ob0 = G6_BLK(nrbB, bb_); ob1 = G6_BLK(nrbB, bb_ + 1); ob2 = G6_BLK(nrbB, bb_ + 2); ob3 = G6_BLK(nrbB, bb_ + 3); \
     } while (0)
@@ -368,36 +330,23 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) 
     } while (0)
     G6_WALK_NEXT();
 
-    unsigned long long* const stamps = reinterpret_cast<unsigned long long*>(part) + wave * 256;
-    int tile_no = 0;
-#define G6_STAMP(i_)                                                                                                    \
-    do {                                                                                                                \
-        if constexpr ((ABLATE & 8) != 0) {                                                                              \
-            if (blockIdx.x == 0 && lane == 0 && tile_no < 16) stamps[tile_no * 16 + (i_)] = __builtin_amdgcn_s_memtime(); \
-        }                                                                                                               \
-    } while (0)
-    constexpr int G6_NST = (ABLATE & 5) ? 0 : 32;      // E stores a wave issues per epilogue
-    bool after_epi = false;                            // an epilogue's stores precede (or ride) this tile's first k-steps
+    constexpr int G6_NST = 32;                         // E stores a wave issues per epilogue
+    bool pending = false;                              // the previous tile's sums wait in the accumulators: its epilogue, stores included, rides this tile's first k-steps
 
     // ---- the sync point in front of the k-step in slot U: own pieces of k-step g+1 landed (the 16 pieces of g+2 and g+3 stay in
     // flight -- and, in a tile's first three k-steps, the 32 stores of the previous tile's epilogue, which are YOUNGER than
-    // those pieces: vmcnt is in order.  In the overlapped forms the stores ride k-step 0 (and 1): nothing extra in front of
+    // those pieces: vmcnt is in order.  The stores ride k-steps 0 and 1: nothing extra in front of
     // k-step 0, the same 32 in front of k-steps 1 and 2, and 29 in front of k-step 3, which waits for k-step 4's pieces: they
     // are issued one per step in steps 0-7 of the phase, the last one behind the stores of steps 5, 6 and 7)
-#define G6_SYNC(U_, R0_) G6_SYNC_(U_, R0_, false)
-#define G6_SYNC_(U_, R0_, KS_)                                                                                              \
+#define G6_SYNC(U_, R0_)                                                                                                    \
     do {                                                                                                                     \
-        if constexpr (R0_) G6_STAMP(1 + 3 * (U_));                                                                           \
-        if ((R0_) && (OVERLAP ? (U_) >= 1 : (U_) < 3) && after_epi)                                                          \
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(16 + ((OVERLAP && (U_) == 3 && G6_NST) ? G6_NST - 3 : G6_NST)) : "memory"); \
+        if ((R0_) && (U_) >= 1 && pending)                                                                                   \
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(16 + ((U_) == 3 ? G6_NST - 3 : G6_NST)) : "memory");                    \
         else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");                                                               \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  /* own reads of k-step g done: slot U can be refilled */         \
-        if constexpr (R0_) G6_STAMP(2 + 3 * (U_));                                                                           \
         __builtin_amdgcn_sched_barrier(0);                                                                                   \
-        /* (ABLATE 128 / 256, timing only: the plain k-steps without every other / without any workgroup barrier) */        \
-        if constexpr (!((KS_) && (((ABLATE & 256) != 0) || (((ABLATE & 128) != 0) && ((U_) & 1))))) __builtin_amdgcn_s_barrier(); \
+        __builtin_amdgcn_s_barrier();                                                                                        \
         asm volatile("" ::: "memory");                                                                                       \
-        if constexpr (R0_) G6_STAMP(3 + 3 * (U_));                                                                           \
         __builtin_amdgcn_sched_barrier(0);                                                                                   \
     } while (0)
     // the memory operation behind MFMA position k of the k-step in slot U (g6_op_after: 1 + i DMA piece i of k-step g + 4 into
@@ -405,28 +354,26 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) 
 #define G6_OP(U_, op_, kt1024_)                                                                                              \
     do {                                                                                                                     \
         constexpr int nxt_ = ((U_) & 1) ^ 1, SN_ = ((U_) + 1) & 3;                                                           \
-        if constexpr ((op_) != 0 && !(((ABLATE & 512) != 0) && (op_) <= 8) && !(((ABLATE & 1024) != 0) && (op_) > 8)) {         \
+        if constexpr ((op_) != 0) {                                                                                          \
             __builtin_amdgcn_sched_barrier(0);                                                                               \
-            if constexpr ((op_) <= 8) { if constexpr (G6_ASMDMA) G6_DMA_ASM(U_, (op_) - 1, kt1024_); else G6_DMA(U_, (op_) - 1, kt1024_); } \
+            if constexpr ((op_) <= 8) G6_DMA_ASM(U_, (op_) - 1, kt1024_);                                                    \
             else if constexpr ((op_) <= 16) G6_RDA(nxt_, SN_, (op_) - 9);                                                    \
             else G6_RDB(nxt_, SN_, (op_) - 17);                                                                              \
             __builtin_amdgcn_sched_barrier(0);                                                                               \
         }                                                                                                                    \
     } while (0)
-    // ---- one k-step, row-major (v4's order and placement of the 24 memory operations)
+    // ---- one k-step: 64 MFMAs row-major, the 24 memory operations where g6_op_after puts them
 #define G6_KSTEP(U_, FIRST_, R0_, kt1024_)                                                                                   \
     do {                                                                                                                     \
         int wb_ = wave4096;                                                                                                  \
         asm volatile("" : "+s"(wb_));                                                                                        \
-        [[maybe_unused]] const int wbl_ = (int)lds0 + wb_;                                                                   \
-        G6_SYNC_(U_, R0_, true);                                                                                             \
+        const int wbl_ = (int)lds0 + wb_;                                                                                    \
+        G6_SYNC(U_, R0_);                                                                                                    \
         g6_for<64>([&](auto k_c) __attribute__((always_inline)) {                                                            \
-            constexpr int k_ = decltype(k_c)::value, mi_ = g6_walk_mi<(PLACE >> 4)>(k_), nj_ = g6_walk_nj<(PLACE >> 4)>(k_); \
-            constexpr int op_ = g6_op_after<(PLACE & 15)>(k_);                                                               \
-            constexpr int opn_ = k_ < 63 ? g6_op_after<(PLACE & 15)>(k_ + 1 < 64 ? k_ + 1 : 0) : 0;                          \
-            g6_mfma<mi_, nj_, (U_) & 1, (FIRST_)>();                                                                         \
-            if constexpr (G6_ASMDMA && (opn_ == 1 || opn_ == 5) && !((ABLATE & 512) != 0)) {                                 \
-                static_assert(!(G6_ASMDMA && (opn_ == 1 || opn_ == 5)) || op_ == 0, "the gap in front of a group's first piece is empty"); \
+            constexpr int k_ = decltype(k_c)::value, op_ = g6_op_after(k_), opn_ = k_ < 63 ? g6_op_after(k_ + 1) : 0;        \
+            g6_mfma<(k_ >> 3), (k_ & 7), (U_) & 1, (FIRST_)>();                                                              \
+            if constexpr (opn_ == 1 || opn_ == 5) {                                                                          \
+                static_assert(op_ == 0, "the gap in front of a group's first piece is empty");                               \
                 __builtin_amdgcn_sched_barrier(0);                                                                           \
                 G6_DMA_M0(U_, (opn_ - 1) >> 2);                                                                              \
                 __builtin_amdgcn_sched_barrier(0);                                                                           \
@@ -435,7 +382,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) 
         });                                                                                                                  \
         __builtin_amdgcn_sched_barrier(0);                                                                                   \
     } while (0)
-    // the tile whose sums are in the accumulators (in the overlapped forms its epilogue runs at the top of the NEXT tile's K loop)
+    // the tile whose sums are in the accumulators (its epilogue runs at the top of the NEXT tile's K loop)
     int ptm = 0, ptn = 0;
     // ---- the epilogue of tile (ptm, ptn).
     // Block (2p + h, nj), register r: concept = row0 + wr*128 + 32 p + 8 fq + 4 h + r, image = col0 + wc*128 + 16 nj + fr.
@@ -445,19 +392,13 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) 
     //   E  row-sum MFMA of the piece
     // Every wait for the LDS (B's, for the slice) sits a whole group behind the LDS instructions it waits for (C, D of the
     // previous step): with store and read right behind the piece's write, as in v4, each group exposed an LDS round trip.
-    // K0 (the overlapped boundary phase): this IS the next tile's k-step in slot 0.  Behind its sync point come the k-step's 8
+    // RIDE (the overlapped boundary phase; false behind the walk's last tile): this IS the next tile's k-steps in slots 0 and 1.  Behind its sync point come the k-step's 8
     // DMA pieces (k-step 4 into slot 0; in front of every store: the vmcnt counts of the next sync points rely on it), the 16
     // fragment reads of k-step 1 (two per step, steps 0-7) and, in the steps of column it + 1, the 8 MFMAs of column it, which
     // overwrite blocks whose pieces have left.
     // EDGE: the tile has concepts past the last one (or past the row pitch): their bf16 values are cleared in the piece.
-#define G6_STORE_SLICE(w_, col_, p_)                                                                                         \
-    do {                                                                                                                     \
-        if constexpr (ABLATE & 1) {                                                                                          \
-            asm volatile("" ::"v"(w_));                                                                                      \
-        } else {                                                                                                             \
-            __builtin_amdgcn_raw_buffer_store_b128(w_, rs_e, lane_off2 + (unsigned)((((col_) * 16 + 4 * (p_)) * (int)ldE) * 2), 0, STAUX); \
-        }                                                                                                                    \
-    } while (0)
+#define G6_STORE_SLICE(w_, col_, p_) /* nontemporal (aux 2): profiles/r05_gexp_v6.txt, r05_store_exp.txt */ \
+    __builtin_amdgcn_raw_buffer_store_b128(w_, rs_e, lane_off2 + (unsigned)((((col_) * 16 + 4 * (p_)) * (int)ldE) * 2), 0, 2)
 #define G6_LDS_U32X4(a_) (*(__attribute__((address_space(3))) u32x4*)(uintptr_t)(a_))
 #define G6_READ_SLICE(col_, p_) G6_LDS_U32X4(((p_) == 0 ? ra0 : (p_) == 1 ? ra1 : (p_) == 2 ? ra2 : ra3) + ((col_) & 1) * 4096)
     // lane-dependent constants of the epilogue, computed once per launch (round 5, late: they are live across the K loop, which
@@ -474,9 +415,9 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) 
              ra2 = tbr + (8u + rrow) * 256 + ((rchunk ^ (8u + rrow)) << 4), ra3 = tbr + (12u + rrow) * 256 + ((rchunk ^ (12u + rrow)) << 4);
     asm volatile("" : "+v"(wa0), "+v"(wa1), "+v"(wa2), "+v"(wa3), "+v"(ra0), "+v"(ra1), "+v"(ra2), "+v"(ra3), "+v"(lane_base2));
     const unsigned lane4 = (unsigned)lane * 4u;
-    auto epilogue = [&](auto k0_c, auto edge_c, [[maybe_unused]] int kt1024) __attribute__((always_inline)) {
-        constexpr int KN = decltype(k0_c)::value;      // k-steps of the next tile that ride this epilogue: 0, 1 or 2
-        constexpr bool K0 = KN >= 1, K1 = KN >= 2, EDGE = decltype(edge_c)::value;
+    auto epilogue = [&](auto ride_c, auto edge_c, [[maybe_unused]] int kt1024) __attribute__((always_inline)) {
+        constexpr bool RIDE = decltype(ride_c)::value;      // the next tile's first two k-steps ride this epilogue
+        constexpr bool EDGE = decltype(edge_c)::value;
         [[maybe_unused]] int wb_ = wave4096;
         asm volatile("" : "+s"(wb_));
         [[maybe_unused]] const int wbl_ = (int)lds0 + wb_;
@@ -486,10 +427,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) 
         // piece, stalled the MFMA stream for as long as they had cost here: profiles/r05_gexp_v6.txt (i).)
         const int c0_ = ptm * 256 + wr * 128, i0_ = ptn * 256 + wc * 128;      // first concept / image of this wave's 128 x 128
         const int rows_ = (int)Ni - i0_ < 128 ? ((int)Ni - i0_ > 0 ? (int)Ni - i0_ : 0) : 128;   // image rows left from there
-        // (ABLATE 2, timing only: every tile of a workgroup goes to the workgroup's FIRST window -- the same instructions; what of
-        // the stores' cost is the CU's store path, what is HBM / fabric)
-        const int64_t e_first = (ABLATE & 2) ? ((int64_t)(blockIdx.x >> 3) * 256 + wc * 128) * ldE + (int64_t)(blockIdx.x & 7) * 256 + wr * 128
-                                             : (int64_t)((uint64_t)(uint32_t)i0_ * (uint32_t)(int)ldE) + c0_;
+        const int64_t e_first = (int64_t)((uint64_t)(uint32_t)i0_ * (uint32_t)(int)ldE) + c0_;
         // E stores go through a buffer descriptor based at this wave's first element of the tile and ending with the last real image's
         // row -- offsets r * ldE * 2 + c * 2, r < rows_, c < ldE - c0_ (the hardware drops what lies past it); a lane whose 8 concepts
         // lie outside the row pitch gets an offset past any range
@@ -505,7 +443,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) 
         // real concepts of this lane's piece p: eclim - 32 p (this lane's first concept of the piece is wave-relative 32 p + 8 fq)
         [[maybe_unused]] int eclim = 0;
         if constexpr (EDGE) eclim = p_crem - 8 * (int)efq;
-        if constexpr (K0) {
+        if constexpr (RIDE) {
             G6_SYNC(0, true);
         } else {
             asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // the last MFMAs' results
@@ -516,17 +454,14 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) 
             [[maybe_unused]] u32x4 v;
             [[maybe_unused]] unsigned m0 = 0, m1 = 0, m2 = 0, m3 = 0;
             // (k-step 1's fragments, read in steps 0-7 by statements the compiler does not count, are used from here on)
-            if constexpr (K1 && S == 8) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if constexpr (RIDE && S == 8) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             // k-step 1's sync point, inside the phase: every wave has its fragments of k-step 1 (slot 1 may be refilled) and its
             // pieces of k-step 2 have landed -- in flight behind them: k-step 3's 8 pieces, k-step 4's 8 (steps 0-7), 7 stores (steps 5-11)
-            if constexpr (K1 && S == 12) {
-                G6_STAMP(4);
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(16 + (G6_NST ? 7 : 0)) : "memory");
-                G6_STAMP(5);
+            if constexpr (RIDE && S == 12) {
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(16 + 7) : "memory");
                 __builtin_amdgcn_sched_barrier(0);
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
-                G6_STAMP(6);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if constexpr (EDGE) {
@@ -537,16 +472,16 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) 
                 m3 = n >= 8 ? 0xffffffffu : n == 7 ? 0xffffu : 0u;
             }
             if constexpr (IT < 6) {
-                if constexpr (K0 && IT >= 1) g6_epi_exp_mm<p, IT, 2 * p, IT - 1, (K1 && IT >= 2) ? IT - 2 : -1, (ABLATE & 32) != 0>(); else g6_epi_exp<p, IT, (ABLATE & 32) != 0>();
+                if constexpr (RIDE && IT >= 1) g6_epi_exp_mm<p, IT, 2 * p, IT - 1, IT >= 2 ? IT - 2 : -1>(); else g6_epi_exp<p, IT>();
                 if constexpr (EDGE) g6_epi_mask<p, IT>(m0, m1, m2, m3);
             } else {
                 constexpr int r0 = g6_acc_reg(2 * p, IT), r1 = g6_acc_reg(2 * p + 1, IT);
                 const float e0 = __builtin_amdgcn_exp2f(g6_acc<r0 + 0>()), e1 = __builtin_amdgcn_exp2f(g6_acc<r0 + 1>());
                 const float e2 = __builtin_amdgcn_exp2f(g6_acc<r0 + 2>()), e3 = __builtin_amdgcn_exp2f(g6_acc<r0 + 3>());
-                if constexpr (K0) { __builtin_amdgcn_sched_barrier(0); g6_mfma_k0<2 * p, IT - 1>(); if constexpr (K1) g6_mfma_k1<2 * p, IT - 2>(); __builtin_amdgcn_sched_barrier(0); }
+                if constexpr (RIDE) { __builtin_amdgcn_sched_barrier(0); g6_mfma_k0<2 * p, IT - 1>(); g6_mfma_k1<2 * p, IT - 2>(); __builtin_amdgcn_sched_barrier(0); }
                 const float e4 = __builtin_amdgcn_exp2f(g6_acc<r1 + 0>()), e5 = __builtin_amdgcn_exp2f(g6_acc<r1 + 1>());
                 const float e6 = __builtin_amdgcn_exp2f(g6_acc<r1 + 2>()), e7 = __builtin_amdgcn_exp2f(g6_acc<r1 + 3>());
-                if constexpr (K0) { __builtin_amdgcn_sched_barrier(0); g6_mfma_k0<2 * p + 1, IT - 1>(); if constexpr (K1) g6_mfma_k1<2 * p + 1, IT - 2>(); __builtin_amdgcn_sched_barrier(0); }
+                if constexpr (RIDE) { __builtin_amdgcn_sched_barrier(0); g6_mfma_k0<2 * p + 1, IT - 1>(); g6_mfma_k1<2 * p + 1, IT - 2>(); __builtin_amdgcn_sched_barrier(0); }
                 v = u32x4{pack_bf16(e0, e1), pack_bf16(e2, e3), pack_bf16(e4, e5), pack_bf16(e6, e7)};
                 if constexpr (EDGE) v &= u32x4{m0, m1, m2, m3};
             }
@@ -554,31 +489,27 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) 
             if constexpr (S >= 5) G6_STORE_SLICE(wq, ((S - 1) >> 2) - 1, (S - 1) & 3);
             __builtin_amdgcn_sched_barrier(0);
             // the LDS destination (M0) of the four DMA pieces whose first goes out further down in this step
-            if constexpr (G6_ASMDMA && K0 && (S == 0 || S == 4)) G6_DMA_M0(0, S >> 2);
-            if constexpr (G6_ASMDMA && K1 && (S == 12 || S == 20)) G6_DMA_M0(1, (S - 12) >> 3);
+            if constexpr (RIDE && (S == 0 || S == 4)) G6_DMA_M0(0, S >> 2);
+            if constexpr (RIDE && (S == 12 || S == 20)) G6_DMA_M0(1, (S - 12) >> 3);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (!(ABLATE & 16)) {          // (ABLATE 16, timing only: no transposition -- the stores send whatever wq holds)
-                if constexpr (IT < 6) {
-                    g6_epi_put<p, IT, (IT & 1) * 4096>(p == 0 ? wa0 : p == 1 ? wa1 : p == 2 ? wa2 : wa3);
-                } else {
-                    G6_LDS_U32X4((p == 0 ? wa0 : p == 1 ? wa1 : p == 2 ? wa2 : wa3) + (IT & 1) * 4096) = v;
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if constexpr (IT >= 1) wq = G6_READ_SLICE(IT - 1, p);
+            if constexpr (IT < 6) {
+                g6_epi_put<p, IT, (IT & 1) * 4096>(p == 0 ? wa0 : p == 1 ? wa1 : p == 2 ? wa2 : wa3);
             } else {
-                asm volatile("" : "+v"(wq));
+                G6_LDS_U32X4((p == 0 ? wa0 : p == 1 ? wa1 : p == 2 ? wa2 : wa3) + (IT & 1) * 4096) = v;
             }
-            if constexpr (K0 && S < 8) {              // fragments of k-step 1 (slot 1) into register set 1; piece S of k-step 4 -> slot 0
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (IT >= 1) wq = G6_READ_SLICE(IT - 1, p);
+            if constexpr (RIDE && S < 8) {              // fragments of k-step 1 (slot 1) into register set 1; piece S of k-step 4 -> slot 0
                 __builtin_amdgcn_sched_barrier(0);
                 G6_RDA(1, 1, S);
                 G6_RDB(1, 1, S);
-                if constexpr (G6_ASMDMA) G6_DMA_ASM(0, S, kt1024); else G6_DMA(0, S, kt1024);
+                G6_DMA_ASM(0, S, kt1024);
             }
-            if constexpr (K1 && S >= 12) {
+            if constexpr (RIDE && S >= 12) {
                 // behind k-step 1's sync point (step 12): the pieces of k-step 5 -> slot 1, one every other step; the B fragments of
                 // k-step 2 into the register-set-0 slots whose column has had its k-step-0 MFMAs (column j: steps 4 j + 4 .. 4 j + 7)
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (S % 2 == 0 && S <= 26) { if constexpr (G6_ASMDMA) G6_DMA_ASM(1, (S - 12) / 2, kt1024 + 1024); else G6_DMA(1, (S - 12) / 2, kt1024 + 1024); }
+                if constexpr (S % 2 == 0 && S <= 26) G6_DMA_ASM(1, (S - 12) / 2, kt1024 + 1024);
                 if constexpr (S == 12) G6_RDB(0, 2, 0);
                 if constexpr (S == 13) G6_RDB(0, 2, 1);
                 if constexpr (S == 16) G6_RDB(0, 2, 2);
@@ -587,15 +518,15 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) 
                 if constexpr (S == 28) G6_RDB(0, 2, 5);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (!(ABLATE & 64)) { if constexpr (IT < 6) g6_epi_sum<p, IT>(); else g6_rowsum<IT>(v); }   // (ABLATE 64, timing only: no row sums)
+            if constexpr (IT < 6) g6_epi_sum<p, IT>(); else g6_rowsum<IT>(v);
             __builtin_amdgcn_sched_barrier(0);
         });
         // the tail: the last slice of column 6, then column 7's four slices (read together: one exposed LDS round trip, under
-        // column 7's k-step-0 MFMAs in the overlapped forms)
+        // column 7's k-step-0 MFMAs when the next tile rides)
         G6_STORE_SLICE(wq, 6, 3);
         const u32x4 w0 = G6_READ_SLICE(7, 0), w1 = G6_READ_SLICE(7, 1), w2 = G6_READ_SLICE(7, 2), w3 = G6_READ_SLICE(7, 3);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (K0) {
+        if constexpr (RIDE) {
             g6_for<8>([&](auto m_c) __attribute__((always_inline)) { g6_mfma_k0<decltype(m_c)::value, 7>(); });
         } else {
             asm volatile("s_nop 7" ::: "memory");     // the last row-sum MFMA is a handful of instructions old
@@ -607,14 +538,14 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) 
         G6_STORE_SLICE(w3, 7, 3);
         // partial row sums of this wave's 128 concepts: lane (fq, fr) holds image 16 fq + fr in register 0 of the row-sum block
         // and image 16 (fq + 4) + fr in register 2; images past the last one fall outside the descriptor
-        if (!((ABLATE & 8) && blockIdx.x == 0)) {
+        {
             const __amdgpu_buffer_rsrc_t rs_p = __builtin_amdgcn_make_buffer_rsrc((void*)(part + ((int64_t)(ptm * 2 + wr) * ldpart + i0_)), 0, __builtin_amdgcn_readfirstlane(rows_ * 4), 0x00020000);
             const float r0 = g6_acc<G6_RS0>(), r2 = g6_acc<G6_RS0 + 2>();
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r0), rs_p, lane4, 0, 0);
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r2), rs_p, lane4 + 256u, 0, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (K1) {
+        if constexpr (RIDE) {
             // columns 6 and 7 of k-step 1 and, under them, the rest of k-step 2's fragments: its A side (every k-step-0 MFMA has
             // been issued: register set 0 is free) and B 6, B 7
             g6_for<16>([&](auto j_c) __attribute__((always_inline)) {
@@ -631,15 +562,11 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) 
     };
     using g6_true = std::integral_constant<bool, true>;
     using g6_false = std::integral_constant<bool, false>;
-    using g6_kn = std::integral_constant<int, OVERLAP>;       // k-steps riding the epilogue
-    using g6_k0 = std::integral_constant<int, 0>;
     // a tile needs the mask when this wave's 128 concepts reach past the last concept
 #define G6_EDGE() (ptm * 256 + wr * 128 + 128 > (int)Mc)
 
-    bool pending = false;                              // (overlapped form) the previous tile's sums wait in the accumulators
     for (;;) {
         int t4 = 0;
-        G6_STAMP(0);
 #define G6_KB(t4_) ((t4_) == nt4 - 1 ? 0 : ((t4_) + 1) * 4096)
 #define G6_TAIL_SWITCH()                                 \
     do {                                                 \
@@ -650,12 +577,12 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) 
         {
             G6_TAIL_SWITCH();
             const int kb = G6_KB(t4);
-            if (OVERLAP && pending) {
-                if (G6_EDGE()) epilogue(g6_kn{}, g6_true{}, kb); else epilogue(g6_kn{}, g6_false{}, kb);
+            if (pending) {                     // k-steps 0 and 1 ride the previous tile's epilogue
+                if (G6_EDGE()) epilogue(g6_true{}, g6_true{}, kb); else epilogue(g6_true{}, g6_false{}, kb);
             } else {
                 G6_KSTEP(0, true, true, kb);
             }
-            if (OVERLAP < 2 || !pending) G6_KSTEP(1, false, true, kb + 1024);
+            if (!pending) G6_KSTEP(1, false, true, kb + 1024);     // (a test of its own: inside the else above, hipcc lays the K loop out differently)
             G6_KSTEP(2, false, true, kb + 2048);
             G6_KSTEP(3, false, true, kb + 3072);
         }
@@ -667,26 +594,15 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) 
             G6_KSTEP(2, false, false, kb + 2048);
             G6_KSTEP(3, false, false, kb + 3072);
         }
-        G6_STAMP(13);
         ptm = tm;
         ptn = tn;
-        if constexpr (!(ABLATE & 4)) {
-            if constexpr (OVERLAP) {
-                pending = true;
-            } else {
-                for (int i = 0; i < wave; ++i) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // the waves' stores skewed (as v4)
-                if (G6_EDGE()) epilogue(g6_k0{}, g6_true{}, 0); else epilogue(g6_k0{}, g6_false{}, 0);
-            }
-            after_epi = true;
-        }
-        G6_STAMP(14);
-        ++tile_no;
+        pending = true;
         if (!has_next) break;
         tm = ntm;
         tn = ntn;
         G6_WALK_NEXT();
     }
-    if constexpr (OVERLAP != 0 && !(ABLATE & 4)) epilogue(g6_k0{}, g6_true{}, 0);   // (the masked form serves any tile)
+    epilogue(g6_false{}, g6_true{}, 0);   // the last tile's, with nothing riding it (the masked form serves any tile)
     // the refills past the last k-step are still in flight: they must land before this workgroup's LDS is handed to the next one
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #undef G6_WALK_NEXT
@@ -698,8 +614,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(G6_NVGPR))) 
 #undef G6_KSTEP
 #undef G6_OP
 #undef G6_SYNC
-#undef G6_SYNC_
-#undef G6_STAMP
 #undef G6_STAGE_ALL
 #undef G6_RDA
 #undef G6_RDB

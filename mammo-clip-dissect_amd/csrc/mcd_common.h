@@ -27,9 +27,10 @@ int mcd_fail(int code, const char* fmt, ...);
 
 static inline int64_t mcd_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// Development knobs: environment variables that pick kernel variants for scripts/ (and for one test that compares two of
-// them).  They exist in the DEV build only (`make dev`, -DMCD_DEV_KNOBS -> libmcd_hip_dev.so); the product library never
-// reads the environment.
+// Development knobs: environment variables that pick kernel variants of k_topk.hip and k_wpmi.hip for scripts/ (and for one
+// test that compares two of them).  They exist in the DEV build only (`make dev`, -DMCD_DEV_KNOBS -> libmcd_hip_dev.so); the
+// product library reads the environment in one place only: mcd_embed_gemm_exp (k_gemm.hip) refuses a set MCD_GEMM_EXP_ABLATE,
+// a retired knob, in both builds.
 #ifdef MCD_DEV_KNOBS
 static inline int mcd_dev_knob(const char* name, int def) { const char* v = getenv(name); return v ? atoi(v) : def; }
 static inline const char* mcd_dev_env(const char* name) { return getenv(name); }

@@ -39,7 +39,7 @@ def _kernel_body(text, needle):
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
 def test_k1s_keeps_the_compiler_out_of_the_named_registers(k1s_asm):
     name, body = _kernel_body(k1s_asm, "gemm_nt_bf16_exp_v6_kernel")
-    assert "ILi0ELi1ELi2ELi2E" in name                 # ABLATE 0, PLACE 1, two k-steps ride the epilogue, nt stores
+    assert "gemm_nt_bf16_exp_v6_kernelE" in name       # a plain kernel: no template arguments (the ablations were retired)
     in_asm, offenders, count = False, [], {}
     for ln in body.splitlines():
         s = ln.strip()
@@ -110,12 +110,26 @@ def test_k1s_is_the_only_exp_gemm_in_the_product(k1s_asm):
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
+def test_the_product_defines_exactly_the_kernels_it_can_launch(k1s_asm):
+    """Every kernel of the translation unit is one the dispatch of mcd_embed_gemm / mcd_embed_gemm_exp can reach: rounds 4-5's
+    variants (plain-store and single-pass forms of the 256 x 256 kernel, a plain-store persistent kernel) shipped unreachable."""
+    import collections
+    syms = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", k1s_asm, flags=re.M)
+    assert len(syms) == len(set(syms))
+    kinds = collections.Counter(re.search(r"N_1\d+(\w+?_kernel)", s).group(1) for s in syms)
+    assert kinds == {"split_bf16_kernel": 1, "rowsum_finish_kernel": 1, "gexp_zero_pad_kernel": 1, "gemm_nt_bf16_big_kernel": 1,
+                     "gemm_nt_bf16_persist_kernel": 1, "gemm_nt_f32_dma_kernel": 4, "gemm_nt_f32_kernel": 4,
+                     "gemm_nt_bf16_kernel": 4, "normalize_to_bf16_kernel": 3, "gemm_nt_bf16_exp_v6_kernel": 1}, kinds
+    assert len(syms) == 21
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
 def test_k1_fp32_issues_the_next_tiles_dma_between_the_mfmas(k1s_asm):
-    """K1 (gemm_nt_f32_dma_kernel, the product's SPREAD = 1 form): inside the K loop no two `buffer_load ... lds` follow each other
+    """K1 (gemm_nt_f32_dma_kernel): inside the K loop no two `buffer_load ... lds` follow each other
     without MFMAs between them -- eight of them back to back behind the barrier were ~1 200 idle cycles of the matrix pipe per K-tile for
     a workgroup alone on its CU (profiles/r05_k1_notes.txt) -- and the compiler has put no vmcnt wait of its own into the loop."""
     for kb in ("Lb1E", "Lb0E"):
-        names = sorted(set(re.findall(r"^(_Z\w*gemm_nt_f32_dma_kernelI%sLi32ELi1ELb1E\w*):" % kb, k1s_asm, flags=re.M)))      # SPREAD 1, buffer-store epilogue
+        names = sorted(set(re.findall(r"^(_Z\w*gemm_nt_f32_dma_kernelI%sLb1EE\w*):" % kb, k1s_asm, flags=re.M)))      # <KBLOCKS, BST = true>: the buffer-store epilogue
         assert len(names) == 1, names
         a = k1s_asm.index(names[0] + ":")
         body = k1s_asm[a:k1s_asm.index(".Lfunc_end", a)]
