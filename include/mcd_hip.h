@@ -464,6 +464,34 @@ int mcd_avgpool2_nhwc(const float* x, int64_t B, int64_t H, int64_t W, int64_t C
 int mcd_attnpool_tokens(const float* x, int64_t B, int64_t HW, int64_t C, const float* pos, float* tok,
                         mcd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * K22  probe-image preprocessing in one launch: src packed RGB uint8 [n, H, W, 3] (n images of ONE source size) ->
+ *      dst fp32 [n, 3, OH, OW], image i at dst + i * dst_img (dst_img >= 3*OH*OW elements; the gap is not written).
+ *      PIL's 8-bit two-pass resampler (Resample.c, PRECISION_BITS = 22) to RH x RW, a crop window of OH x OW at
+ *      (top, left) inside it, then one look-up per byte:
+ *        t[y][o] = clip8((2^21 + sum_j src[y][first_o + j] * coef_o[j]) >> 22)      horizontal, per channel
+ *        r[o][x] = clip8((2^21 + sum_j   t[first_o + j][x] * coef_o[j]) >> 22)      vertical, on the uint8 t
+ *        dst[i][c][y][x] = lut[c][ r[top + y][left + x][c] ]
+ *      int32 accumulation (|sum| <= 255 * sum|coef| + 2^21 < 2^31 for tables whose rows sum to 2^22), arithmetic
+ *      shift, clip8 clamps to 0..255: bit for bit Image.resize((RW, RH), BILINEAR | BICUBIC) on an RGB image.  No
+ *      floating-point operation runs on the device; lut [3][256] fp32 carries ToTensor / Normalize (the caller computes
+ *      v / 255, (. - mean) / std once per byte value).  Only the crop window is computed.
+ *      xtab [RW][2 + kx], ytab [RH][2 + ky] int32: row o = {first, count, coef[0 .. k)}, zero padded, count <= k, as
+ *      PIL's precompute_coeffs + normalize_coeffs_8bpc give them (first non-decreasing in o).  A NULL table skips that
+ *      pass and needs RW == W (RH == H).  Rows that name pixels outside the image are clamped into it (a wrong
+ *      picture, no access outside src).
+ *      Limits: H*W*3 and 3*OH*OW*4 under 2^31 and at most 128 coefficients per table row (bicubic up to ratio 31,
+ *      bilinear up to 63), else MCD_E_UNSUPPORTED and nothing is written.  lut, dst and the tables 4-byte aligned.
+ *      No aliasing: src, lut or a table overlapping dst is MCD_E_ARG.  n == 0 is MCD_OK.
+ * replaces  Resize(256) + CenterCrop(224) + ToTensor + Normalize   concept_vit/data_utils.py:95-100
+ *           CLIP's _transform (bicubic 224, crop, normalise)       concept_vit/clip/clip.py:79-86
+ *           Resize((1520, 912)) + ToTensor of the EMBED sets       concept_vit/data_utils.py:176-179
+ *           ToTensor + Normalize of imagenet_subsets               concept_vit/data_utils.py:111
+ * ------------------------------------------------------------------------------------------- */
+int mcd_image_preprocess(const uint8_t* src, int64_t n, int64_t H, int64_t W, const int32_t* xtab, int64_t kx, int64_t RW,
+                         const int32_t* ytab, int64_t ky, int64_t RH, int64_t top, int64_t left, int64_t OH, int64_t OW,
+                         const float* lut, float* dst, int64_t dst_img, mcd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,8 @@ SIGNATURES = {
     "mcd_conv3x3s2_nhwc": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _i64, _int, _p, _p]),
     "mcd_avgpool2_nhwc": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p]),
     "mcd_attnpool_tokens": (_int, [_p, _i64, _i64, _i64, _p, _p, _p]),
+    "mcd_image_preprocess": (_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _i64,
+                                    _p]),
 }
 
 MCD_E_ARG = -1

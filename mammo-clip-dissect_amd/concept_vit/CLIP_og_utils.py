@@ -18,7 +18,8 @@ def save_activations(clip_name, target_name, target_layers, d_probe,
                      concept_set, batch_size, device, pool_mode, save_dir):
     clip_model, tokenize = _clip_dissector(device, clip_name)
     target_model = clip_model if target_name == "clip" else data_utils.get_target_model(target_name, device)[0]
-    data = _u._probe_data(d_probe, device)
+    # reference :128-132: the dissector's copy of the probe set gets CLIP's transform, the target's copy its own
+    data = _u._probe_data(d_probe, device, "clip" if target_name == "clip" else data_utils.target_preset(target_name), "clip")
     words = _u._read_concepts(concept_set)
     t_name, c_name, x_name = get_save_names(clip_name=clip_name, target_name=target_name, target_layer='{}',
                                             d_probe=d_probe, concept_set=concept_set, pool_mode=pool_mode,

@@ -1518,12 +1518,239 @@ class DeviceSyntheticImages(torch.utils.data.Dataset):
             yield x[i:i + batch_size]
 
 
-def get_data(dataset_name, preprocess=None, device=None, lo=0, hi=None):
+# ------------------------------------------------------------------------------------------------------
+# file probe sets: the reference's image datasets (data_utils.py:102-311, data/Imagenet_custom_dataloader.py)
+# ------------------------------------------------------------------------------------------------------
+IMG_EXTENSIONS = (".jpg", ".jpeg", ".png", ".ppm", ".bmp", ".pgm", ".tif", ".tiff", ".webp")     # torchvision's
+
+
+def list_txt(txt_file):
+    """CustomImageDatasetFromTxt (Imagenet_custom_dataloader.py:17-22): one `path label` per line, in file order."""
+    samples = []
+    with open(txt_file, "r") as f:
+        for line in f:
+            img_path, label = line.strip().split(" ")
+            samples.append((img_path, int(label)))
+    return samples
+
+
+def list_folder(root):
+    """torchvision's ImageFolder: classes = the sorted sub-directory names, label = the class's index; inside a class
+    the directories in sorted order (os.walk, links followed), the files of each sorted by name, IMG_EXTENSIONS only
+    (case-insensitive)."""
+    classes = sorted(e.name for e in os.scandir(root) if e.is_dir())
+    if not classes:
+        raise FileNotFoundError("no class folders in %s" % root)
+    samples = []
+    for label, cls in enumerate(classes):
+        for d, _, names in sorted(os.walk(os.path.join(root, cls), followlinks=True)):
+            for name in sorted(names):
+                if name.lower().endswith(IMG_EXTENSIONS):
+                    samples.append((os.path.join(d, name), label))
+    return samples
+
+
+# EMBED_Dataset / EMBED_marker_Dataset (Imagenet_custom_dataloader.py:55, :88): label column -> its mapping
+CSV_LABELS = {"Implant_type": {"non-implant": 0, "implant": 1}, "Marker": {"No": 0, "Yes": 1}}
+
+
+def list_csv(root, csv_file, label_column="Implant_type"):
+    """EMBED_Dataset (label_column 'Implant_type') / EMBED_marker_Dataset ('Marker'): the CSV's rows in file order,
+    path = root / filename, label mapped as the reference maps it (a value outside the mapping is NaN, pandas' map)."""
+    import pandas as pd
+    data = pd.read_csv(csv_file)
+    if "filename" not in data.columns or label_column not in data.columns:
+        raise ValueError("CSV file must contain 'filename' and '%s' columns." % label_column)
+    labels = data[label_column].map(CSV_LABELS[label_column])
+    return [(os.path.join(root, name), label) for name, label in zip(data["filename"], labels)]
+
+
+def decode_rgb(path):
+    """Image.open(path).convert("RGB") as a uint8 [H, W, 3] array: what every dataset of the reference starts from."""
+    import numpy as np
+    from PIL import Image
+    with Image.open(path) as img:
+        return np.asarray(img.convert("RGB"), dtype=np.uint8)
+
+
+def host_preprocess(arr, pre):
+    """The host route, and the yardstick of K22: `pre` on one uint8 [H, W, 3] array with PIL itself (Image.resize,
+    Image.crop) and the three torch operations of ToTensor / Normalize -> fp32 [3, OH, OW] on the CPU."""
+    import numpy as np
+    from PIL import Image
+    plan = pre.plan(arr.shape[0], arr.shape[1])
+    img = Image.fromarray(np.ascontiguousarray(arr), "RGB")
+    if (plan.RH, plan.RW) != (plan.H, plan.W):
+        img = img.resize((plan.RW, plan.RH), {"bilinear": Image.BILINEAR, "bicubic": Image.BICUBIC}[pre.filter])
+    if (plan.OH, plan.OW) != (plan.RH, plan.RW):
+        img = img.crop((plan.left, plan.top, plan.left + plan.OW, plan.top + plan.OH))
+    t = torch.from_numpy(np.array(img, dtype=np.uint8)).permute(2, 0, 1).contiguous().to(torch.float32).div(255)
+    if pre.mean is not None:
+        t = t.sub(torch.as_tensor(pre.mean, dtype=torch.float32)[:, None, None]).div(
+            torch.as_tensor(pre.std, dtype=torch.float32)[:, None, None])
+    return t
+
+
+class ImageFileProbe(torch.utils.data.Dataset):
+    """A probe set of image files.  samples: [(path, label)] in the reference's order (list_txt / list_folder /
+    list_csv); the row order is the `images` column of the drivers' CSV.  preprocess: the target's transform (a preset
+    name or a core.Preprocess); clip_preprocess: the dissector's when it differs -- every item / batch is then the pair
+    (target view, dissector view) made from ONE decoded image.  decode: path -> uint8 [H, W, 3] (default decode_rgb).
+    lo / hi: this rank's shard of the sample list.
+
+    Host route (device None): dataset[i] -> (tensor, label), PIL + torch (host_preprocess).
+    Device route (a CUDA device): device_batches(batch_size) decodes on a thread pool one batch ahead, uploads the
+    uint8 pixels through pinned memory and runs K22 (core.image_preprocess) once per run of consecutive same-size
+    images, straight into the batch tensor(s)."""
+
+    def __init__(self, samples, preprocess, clip_preprocess=None, decode=None, lo=0, hi=None, device=None):
+        samples = list(samples)
+        self.n_total = len(samples)
+        self.lo, self.hi = int(lo), int(self.n_total if hi is None else hi)
+        self.samples = samples[self.lo:self.hi]
+        self.preprocess = core.get_preprocess(preprocess)
+        clip = None if clip_preprocess is None else core.get_preprocess(clip_preprocess)
+        self.clip_preprocess = None if clip == self.preprocess else clip
+        self.decode = decode_rgb if decode is None else decode
+        self.device = None if device is None or torch.device(device).type != "cuda" else torch.device(device)
+
+    @property
+    def views(self):
+        return [self.preprocess] + ([] if self.clip_preprocess is None else [self.clip_preprocess])
+
+    def __len__(self):
+        return len(self.samples)
+
+    def __getitem__(self, i):
+        path, label = self.samples[i]
+        arr = self.decode(path)
+        out = [host_preprocess(arr, p) for p in self.views]
+        return (out[0] if len(out) == 1 else tuple(out)), label
+
+    def sample(self):
+        """The first image's target view as a [1, 3, OH, OW] batch on the device (the layer-width probe)."""
+        batches = self._batches(1, 1)
+        try:
+            return next(batches)[0]
+        finally:
+            batches.close()
+
+    def device_batches(self, batch_size):
+        """Batches [B, 3, OH, OW] on the device, in sample order; with two views, pairs (target, dissector) of them."""
+        if self.device is None:
+            raise RuntimeError("ImageFileProbe.device_batches: the probe set was built without a CUDA device")
+        for out in self._batches(batch_size, len(self)):
+            yield out[0] if len(out) == 1 else tuple(out)
+
+    def _batches(self, batch_size, n):
+        from concurrent.futures import ThreadPoolExecutor
+        spans = [(i, min(i + batch_size, n)) for i in range(0, n, batch_size)]
+        with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+            def submit(span):
+                return [pool.submit(self.decode, self.samples[i][0]) for i in range(*span)]
+            ahead = submit(spans[0]) if spans else None
+            for k in range(len(spans)):
+                arrays = [f.result() for f in ahead]
+                ahead = submit(spans[k + 1]) if k + 1 < len(spans) else None     # decoded while the GPU works on batch k
+                yield self._to_device(arrays)
+
+    def _to_device(self, arrays):
+        """One batch: uint8 [H, W, 3] arrays -> a [B, 3, OH, OW] device tensor per view."""
+        plans = [[p.plan(a.shape[0], a.shape[1]) for a in arrays] for p in self.views]
+        outs = []
+        for p, pl in zip(self.views, plans):
+            sizes = {(q.OH, q.OW) for q in pl}
+            if len(sizes) != 1:
+                raise ValueError("ImageFileProbe: %r gives images of different sizes in one batch: %s" % (p, sorted(sizes)))
+            outs.append(torch.empty((len(arrays), 3) + sizes.pop(), dtype=torch.float32, device=self.device))
+        i = 0
+        while i < len(arrays):
+            j = i + 1
+            while j < len(arrays) and arrays[j].shape == arrays[i].shape:
+                j += 1
+            if all(pl[i].device_ok for pl in plans):
+                H, W = arrays[i].shape[:2]
+                pinned = torch.empty((j - i, H, W, 3), dtype=torch.uint8, pin_memory=True)
+                staged = pinned.numpy()
+                for r in range(i, j):
+                    staged[r - i] = arrays[r]
+                src = pinned.to(self.device, non_blocking=True)            # ONE upload feeds every view
+                for p, out in zip(self.views, outs):
+                    core.image_preprocess(src, p, out=out[i:j])
+            else:      # past K22's limits (core.ImagePlan.device_ok): this run is made on the host and uploaded
+                for p, out in zip(self.views, outs):
+                    out[i:j].copy_(torch.stack([host_preprocess(a, p) for a in arrays[i:j]]))
+            i = j
+        return outs
+
+
+# name -> how the reference's get_data builds the set (data_utils.py:106-113, :169-251, :304-309) and the transform it
+# gets when the caller passes none.  Paths are not part of the package: register_dataset, or a JSON file named by
+# MCD_DATASETS ({name: {"path": ..} | {"root": .., "csv": ..}}).
+DATASET_KINDS = {"imagenet_subsets": ("txt", "tensor"), "imagenet_val": ("folder", "imagenet"),
+                 "broden": ("folder", "imagenet"), "imagenet_broden": ("concat", "imagenet"),
+                 "embed_png": ("csv:Implant_type", "embed"), "embed_marker_84": ("csv:Marker", "embed"),
+                 "embed_implant": ("csv:Implant_type", "embed"), "embed_marker_only": ("csv:Marker", "embed"),
+                 "embed_non_implant": ("csv:Implant_type", "embed"), "embed_non_implant_100": ("csv:Implant_type", "embed")}
+CONCAT_PARTS = {"imagenet_broden": ("imagenet_val", "broden")}
+DATASET_ROOTS = {}
+
+
+def register_dataset(name, path=None, root=None, csv=None, kind=None, default_preprocess=None):
+    """Where a probe set lives: `path` (the text file of a 'txt' set, the class-folder tree of a 'folder' set) or
+    `root` + `csv` (a 'csv:<label column>' set).  kind / default_preprocess: for a name the reference does not have."""
+    if name not in DATASET_KINDS:
+        if kind is None:
+            raise ValueError("register_dataset: %r is not one of the reference's probe sets; give its kind "
+                             "('txt', 'folder', 'csv:Implant_type' or 'csv:Marker')" % (name,))
+        DATASET_KINDS[name] = (kind, default_preprocess or "imagenet")
+    DATASET_ROOTS[name] = {"path": path, "root": root, "csv": csv}
+
+
+def _registered(name):
+    entry = DATASET_ROOTS.get(name)
+    table = os.environ.get("MCD_DATASETS")
+    if entry is None and table:
+        import json
+        with open(table) as f:
+            entry = json.load(f).get(name)
+    return entry
+
+
+def _list_samples(name):
+    kind = DATASET_KINDS[name][0]
+    if kind == "concat":
+        return [s for part in CONCAT_PARTS[name] for s in _list_samples(part)]
+    entry = _registered(name)
+    if entry is None:
+        raise ValueError("dataset %r has no path: register_dataset(%r, ...) or name a JSON table in MCD_DATASETS"
+                         % (name, name))
+    paths = [entry.get("root"), entry.get("csv")] if kind.startswith("csv:") else [entry.get("path")]
+    for p in paths:
+        if p is None or not os.path.exists(p):
+            raise FileNotFoundError("dataset %r: %s does not exist" % (name, p))
+    if kind == "txt":
+        return list_txt(paths[0])
+    if kind == "folder":
+        return list_folder(paths[0])
+    return list_csv(paths[0], paths[1], kind[len("csv:"):])
+
+
+def target_preset(target_name):
+    """The transform the reference's get_target_model hands back with a target (data_utils.py:38-93): none for the
+    Mammo-CLIP models, the ImageNet one for everything else."""
+    return None if target_name.startswith("breastclip") else "imagenet"
+
+
+def get_data(dataset_name, preprocess=None, device=None, lo=0, hi=None, clip_preprocess=None):
     """'synthetic_<N>', 'synthetic_<N>_<size>' (e.g. synthetic_10000_224) or 'synthetic_<N>_<H>x<W>' (H rows, W columns,
-    e.g. synthetic_64_1520x912).  Real datasets are not in the
-    container (reference data_utils.py:102-311 reads VinDr/CSAW/EMBED/ImageNet paths).  With a CUDA `device` the
-    probe set is generated on the device and stays resident there (DeviceSyntheticImages); lo/hi select a rank's
-    shard of it."""
+    e.g. synthetic_64_1520x912): with a CUDA `device` the probe set is generated on the device and stays resident there
+    (DeviceSyntheticImages); lo/hi select a rank's shard of it.
+    The reference's file sets (DATASET_KINDS: imagenet_subsets, imagenet_val, broden, imagenet_broden, embed_*) once
+    their paths are registered: an ImageFileProbe over images lo..hi-1.  preprocess / clip_preprocess: a preset name, a
+    core.Preprocess or None (preprocess: the set's own default, 'tensor', 'imagenet' or 'embed' as in the reference;
+    clip_preprocess: no second view; 'default' there names the set's own default).  With a CUDA `device` the set
+    preprocesses on the GPU (K22)."""
     if dataset_name.startswith("synthetic"):
         parts = dataset_name.split("_")
         n = int(parts[1]) if len(parts) > 1 else 256
@@ -1536,4 +1763,11 @@ def get_data(dataset_name, preprocess=None, device=None, lo=0, hi=None):
         if lo != 0 or (hi is not None and hi != n):
             return torch.utils.data.Subset(ds, range(lo, n if hi is None else hi))
         return ds
-    raise ValueError("dataset %r is not available offline; use synthetic_<N>[_<size> | _<H>x<W>]" % (dataset_name,))
+    if dataset_name in DATASET_KINDS:
+        default = DATASET_KINDS[dataset_name][1]
+        if isinstance(clip_preprocess, str) and clip_preprocess == "default":
+            clip_preprocess = default
+        return ImageFileProbe(_list_samples(dataset_name), default if preprocess is None else preprocess,
+                              clip_preprocess, lo=lo, hi=hi, device=device)
+    raise ValueError("dataset %r is not available offline; use synthetic_<N>[_<size> | _<H>x<W>] or one of %s"
+                     % (dataset_name, ", ".join(sorted(DATASET_KINDS))))

@@ -52,7 +52,8 @@ def save_activations(clip_name, target_name, target_layers, d_probe,
     else:
         target_model, _ = data_utils.get_target_model(target_name, device, ckpt=breast_clip_ckh)
         encode_target = target_model.encode_image         # reference :93
-    data = _u._probe_data(d_probe, device)
+    # reference :410-430: the dissector gets the set's own transform (clip_preprocess = None), the target its own
+    data = _u._probe_data(d_probe, device, data_utils.target_preset(target_name), "default")
     words = _u._read_concepts(concept_set)
     t_name, c_name, x_name = get_save_names(clip_name=clip_name, target_name=target_name, target_layer='{}',
                                             d_probe=d_probe, concept_set=concept_set, pool_mode=pool_mode,

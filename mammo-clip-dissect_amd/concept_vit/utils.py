@@ -248,13 +248,13 @@ def extract_and_save(clip_model, target_model, encode_target, target_layers, dat
         if E_txt is None:
             E_txt = _load_feats(text_save_name, device)
         N = len(dataset)
-        on_device = hasattr(dataset, "device_batches")
+        on_device = hasattr(dataset, "device_batches") and getattr(dataset, "device", None) is not None
         if on_device:
             batches = dataset.device_batches(batch_size)
-            first = dataset.images()[:1] if N > 0 else None
+            first = (dataset.sample() if hasattr(dataset, "sample") else dataset.images()[:1]) if N > 0 else None
         else:
             batches = DataLoader(dataset, batch_size=batch_size, shuffle=False, num_workers=0)
-            first = dataset[0][0].unsqueeze(0).to(device) if N > 0 else None
+            first = _views(dataset[0][0])[0].unsqueeze(0).to(device) if N > 0 else None
         if first is None:   # a rank without images still needs the layer widths
             first = torch.zeros((1, 3, 224, 224), dtype=torch.float32, device=device)
         layers = [resolve_layer(target_model, l) for l in target_layers]
@@ -266,14 +266,19 @@ def extract_and_save(clip_model, target_model, encode_target, target_layers, dat
         handles = [m.register_forward_hook(dis.hook(i)) for i, m in enumerate(layers)] if need_target else []
         try:
             for batch in batches:
-                if on_device:
-                    images = batch
-                else:
-                    images = (batch[0] if isinstance(batch, (list, tuple)) else batch["images"]).to(device)
+                if not on_device:
+                    batch = batch[0] if isinstance(batch, (list, tuple)) else batch["images"]
+                # one view, or the pair (target view, dissector view) of a probe set with two transforms
+                target_view, clip_view = _views(batch)
+                images = target_view.to(device)
+                clip_images = images if clip_view is target_view else clip_view.to(device)
                 if need_target:
                     out = encode_target(images)                    # hooks fire (reference :174-181)
                 if need_clip:
-                    f = out if (same and need_target) else clip_model.encode_image(images)   # one pass when same
+                    if same and need_target and clip_images is images:
+                        f = out                                    # one pass when the target is the dissector
+                    else:
+                        f = clip_model.encode_image(clip_images)
                     if getattr(clip_model, "projection", False):
                         f = clip_model.image_projection(f)
                     dis.add_image_features(f.float())
@@ -299,16 +304,26 @@ def extract_and_save(clip_model, target_model, encode_target, target_layers, dat
         return Extraction(dis, E_txt, target_layers, writer)
 
 
-def _probe_data(d_probe, device):
-    """D_probe for the extraction loop: generated on the device and resident there when `device` is a GPU (this rank's
-    shard of it in a multi-rank run); MCD_PROBE_ON_HOST=1 keeps the host dataset + DataLoader path."""
+def _views(batch):
+    """(target view, dissector view) of a batch or an item: a probe set with two transforms yields pairs, every other
+    one a single tensor that serves both."""
+    if isinstance(batch, (list, tuple)):
+        target, clip = batch
+        return target, clip
+    return batch, batch
+
+
+def _probe_data(d_probe, device, preprocess=None, clip_preprocess=None):
+    """D_probe for the extraction loop: generated (synthetic sets) or preprocessed (file sets, K22) on the device when
+    `device` is a GPU (this rank's shard of it in a multi-rank run); MCD_PROBE_ON_HOST=1 keeps the host dataset +
+    DataLoader path.  preprocess / clip_preprocess: the target's and the dissector's transform of a file set
+    (data_utils.get_data); synthetic sets ignore them."""
     from ..pipeline import shard_bounds
     world, rank = _dist_info()
     n = len(data_utils.get_data(d_probe, None))
     lo, hi = shard_bounds(n, world, rank)
-    if os.environ.get("MCD_PROBE_ON_HOST", "0") == "1":
-        return data_utils.get_data(d_probe, None, None, lo, hi)
-    return data_utils.get_data(d_probe, None, device, lo, hi)
+    on_host = os.environ.get("MCD_PROBE_ON_HOST", "0") == "1"
+    return data_utils.get_data(d_probe, preprocess, None if on_host else device, lo, hi, clip_preprocess=clip_preprocess)
 
 
 def build_mammo_models(target_name, device, breast_clip_ckh=None, fine_tuned_ckh=None, args=None):
@@ -339,7 +354,8 @@ def save_activations(clip_name, target_name, target_layers, d_probe,
         clip_model, target_model, data = prebuilt["clip_model"], prebuilt["target_model"], prebuilt["data"]
     else:
         clip_model, target_model = build_mammo_models(target_name, device, breast_clip_ckh, fine_tuned_ckh, args)
-        data = _probe_data(d_probe, device)
+        # reference :472-490: the dissector gets the set's own transform (clip_preprocess = None), the target its own
+        data = _probe_data(d_probe, device, data_utils.target_preset(target_name), "default")
     words = _read_concepts(concept_set)
     t_name, c_name, x_name = get_save_names(clip_name=clip_name, target_name=target_name, target_layer='{}',
                                             d_probe=d_probe, concept_set=concept_set, pool_mode=pool_mode,

@@ -890,3 +890,212 @@ def hook_pool(x, mode, dst, row0, col0, neuron_major):
         return Cout
     check(L.mcd_hook_pool(x.data_ptr(), B, Cout, HW, m, dst.data_ptr(), int(row0), int(col0), sn, su, _stream()))
     return Cout
+
+
+# ---- K22: probe-image preprocessing (csrc/k_image.hip) ----------------------------------------------
+IMAGE_MAX_TAPS = 128       # coefficients per table row mcd_image_preprocess takes (kMaxTaps)
+_PRECISION_BITS = 22       # PIL Resample.c, 8 bits per channel
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
+
+
+def _bilinear(x):
+    x = -x if x < 0.0 else x
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+def _bicubic(x):
+    a = -0.5
+    x = -x if x < 0.0 else x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+FILTERS = {"bilinear": (_bilinear, 1.0), "bicubic": (_bicubic, 2.0)}
+
+
+@functools.lru_cache(maxsize=None)
+def resample_table(in_size, out_size, filter):
+    """PIL's precompute_coeffs + normalize_coeffs_8bpc (Resample.c) for one axis, in doubles: an int32 CPU tensor
+    [out_size, 2 + k], row o = {first, count, coef[0 .. k)} zero padded, k = the widest row.  The horizontal and the
+    vertical pass of Image.resize read the same kind of table.  Cached: treat the tensor as read-only."""
+    fn, support = FILTERS[filter]
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError("resample_table: sizes must be positive, got %d -> %d" % (in_size, out_size))
+    scale = filterscale = in_size / out_size
+    if filterscale < 1.0:
+        filterscale = 1.0
+    support = support * filterscale
+    ss = 1.0 / filterscale
+    rows = []
+    for o in range(out_size):
+        center = (o + 0.5) * scale
+        first = max(int(center - support + 0.5), 0)
+        last = min(int(center + support + 0.5), in_size)
+        w = [fn((j + first - center + 0.5) * ss) for j in range(last - first)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        half = 0.5
+        rows.append((first, [int(v * (1 << _PRECISION_BITS) - half) if v < 0 else int(v * (1 << _PRECISION_BITS) + half)
+                             for v in w]))
+    k = max(len(c) for _, c in rows)
+    t = torch.zeros((out_size, 2 + k), dtype=torch.int32)
+    for o, (first, c) in enumerate(rows):
+        t[o, 0], t[o, 1] = first, len(c)
+        if c:
+            t[o, 2:2 + len(c)] = torch.tensor(c, dtype=torch.int32)
+    return t
+
+
+class ImagePlan:
+    """What Preprocess.plan(H, W) gives: the resized size RH x RW, the crop window (top, left, OH, OW) inside it and
+    the two pass tables (None where the axis keeps its size: PIL skips that pass)."""
+
+    def __init__(self, H, W, RH, RW, top, left, OH, OW, filter):
+        self.H, self.W, self.RH, self.RW, self.top, self.left, self.OH, self.OW = H, W, RH, RW, top, left, OH, OW
+        self.xtab = resample_table(W, RW, filter) if RW != W else None
+        self.ytab = resample_table(H, RH, filter) if RH != H else None
+
+    @property
+    def taps(self):
+        """(kx, ky): coefficients per row of the two tables (0 for a skipped pass)."""
+        return tuple(0 if t is None else t.shape[1] - 2 for t in (self.xtab, self.ytab))
+
+    @property
+    def device_ok(self):
+        """K22 takes this plan (IMAGE_MAX_TAPS, one image under 2^31 bytes); otherwise the caller keeps the host route."""
+        return max(self.taps) <= IMAGE_MAX_TAPS and self.H * self.W * 3 < 2 ** 31 and 12 * self.OH * self.OW < 2 ** 31
+
+
+class Preprocess:
+    """Resize -> CenterCrop -> ToTensor -> Normalize on an RGB PIL image, as a spec.  filter: 'bilinear' | 'bicubic';
+    resize: None, an int (shorter side, torchvision's Resize(int)) or (h, w); crop: None, an int or (h, w) (CenterCrop);
+    mean / std: per channel, or None for ToTensor alone."""
+
+    def __init__(self, filter="bilinear", resize=None, crop=None, mean=None, std=None):
+        if filter not in FILTERS:
+            raise ValueError("Preprocess: filter must be one of %s, got %r" % (sorted(FILTERS), filter))
+        if (mean is None) != (std is None):
+            raise ValueError("Preprocess: mean and std come together")
+        self.filter = filter
+        self.resize = None if resize is None else (int(resize) if isinstance(resize, int) else tuple(int(v) for v in resize))
+        self.crop = None if crop is None else ((int(crop), int(crop)) if isinstance(crop, int) else tuple(int(v) for v in crop))
+        self.mean = None if mean is None else tuple(float(v) for v in mean)
+        self.std = None if std is None else tuple(float(v) for v in std)
+        self._lut = None
+
+    def _key(self):
+        return (self.filter, self.resize, self.crop, self.mean, self.std)
+
+    def __eq__(self, other):
+        return isinstance(other, Preprocess) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "Preprocess(filter=%r, resize=%r, crop=%r, mean=%r, std=%r)" % self._key()
+
+    def plan(self, H, W):
+        """ImagePlan for an H x W source: torchvision's sizes -- Resize(int s): the shorter side -> s, the longer ->
+        int(s * long / short); CenterCrop: top = int(round((RH - ch) / 2.0)), Python's round (4.5 -> 4, 5.5 -> 6).  A crop
+        larger than the resized image is a ValueError (torchvision would pad)."""
+        H, W = int(H), int(W)
+        if self.resize is None:
+            RH, RW = H, W
+        elif isinstance(self.resize, int):
+            short, long = (W, H) if W <= H else (H, W)
+            new_short, new_long = self.resize, int(self.resize * long / short)
+            RW, RH = (new_short, new_long) if W <= H else (new_long, new_short)
+        else:
+            RH, RW = self.resize
+        if self.crop is None:
+            top, left, OH, OW = 0, 0, RH, RW
+        else:
+            OH, OW = self.crop
+            if OH > RH or OW > RW:
+                raise ValueError("Preprocess: a %d x %d crop of a %d x %d image (resized from %d x %d)"
+                                 % (OH, OW, RH, RW, H, W))
+            top, left = int(round((RH - OH) / 2.0)), int(round((RW - OW) / 2.0))
+        return ImagePlan(H, W, RH, RW, top, left, OH, OW, self.filter)
+
+    def lut(self):
+        """[3, 256] fp32 on the CPU: channel c's value for byte v, computed with the torch operations ToTensor and
+        Normalize run: v.to(float32).div(255), then .sub(mean32).div(std32)."""
+        if self._lut is None:
+            t = torch.arange(256, dtype=torch.uint8).to(torch.float32).div(255).repeat(3, 1)
+            if self.mean is not None:
+                mean = torch.as_tensor(self.mean, dtype=torch.float32)
+                std = torch.as_tensor(self.std, dtype=torch.float32)
+                t = t.sub(mean[:, None]).div(std[:, None])
+            self._lut = t.contiguous()
+        return self._lut
+
+
+# the transforms the reference builds (file:line of the reference)
+PRESETS = {
+    "imagenet": Preprocess("bilinear", 256, 224, IMAGENET_MEAN, IMAGENET_STD),      # concept_vit/data_utils.py:95-100
+    "clip": Preprocess("bicubic", 224, 224, CLIP_MEAN, CLIP_STD),                   # concept_vit/clip/clip.py:79-86
+    "embed": Preprocess("bilinear", (1520, 912)),                                   # concept_vit/data_utils.py:176-179
+    "tensor": Preprocess("bilinear", None, None, IMAGENET_MEAN, IMAGENET_STD),      # concept_vit/data_utils.py:111
+}
+
+
+def get_preprocess(p):
+    """A preset name or a Preprocess -> the Preprocess."""
+    if isinstance(p, Preprocess):
+        return p
+    if p not in PRESETS:
+        raise ValueError("unknown preprocess %r (presets: %s)" % (p, ", ".join(sorted(PRESETS))))
+    return PRESETS[p]
+
+
+_image_consts = {}
+
+
+def _device_const(key, device, make):
+    """A small CPU tensor (a pass table, a look-up table) uploaded once per device."""
+    k = (key, str(device))
+    if k not in _image_consts:
+        _image_consts[k] = make().to(device)
+    return _image_consts[k]
+
+
+@_on_device
+def image_preprocess(src_u8, preprocess, out=None):
+    """K22: packed RGB uint8 images [n, H, W, 3] of one source size on the GPU -> fp32 [n, 3, OH, OW], the bits of
+    `preprocess` (a preset name or a Preprocess) run with PIL + torch on every image.  out: where to write, e.g. a
+    slice of a batch tensor: fp32 [n, 3, OH, OW] with each image contiguous (stride(0) >= 3*OH*OW).  A plan past the
+    kernel's limits (ImagePlan.device_ok) raises McdError(MCD_E_UNSUPPORTED)."""
+    _need_gpu(src_u8, out)
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 4 or src_u8.shape[3] != 3 or not src_u8.is_contiguous():
+        raise TypeError("image_preprocess: src must be a contiguous uint8 [n, H, W, 3] tensor")
+    pre = get_preprocess(preprocess)
+    n, H, W = src_u8.shape[:3]
+    plan = pre.plan(H, W)
+    shape = (n, 3, plan.OH, plan.OW)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=src_u8.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != shape or (n > 0 and not out[0].is_contiguous()) \
+            or (n > 1 and out.stride(0) < 3 * plan.OH * plan.OW):
+        raise ValueError("image_preprocess: out must be float32 %s with contiguous images" % (shape,))
+    if n == 0:
+        return out
+    dev = src_u8.device
+    xtab = None if plan.xtab is None else _device_const(("tab", W, plan.RW, pre.filter), dev, lambda: plan.xtab)
+    ytab = None if plan.ytab is None else _device_const(("tab", H, plan.RH, pre.filter), dev, lambda: plan.ytab)
+    lut = _device_const(("lut", pre.mean, pre.std), dev, pre.lut)
+    kx, ky = plan.taps
+    L = _lib.load()
+    check(L.mcd_image_preprocess(src_u8.data_ptr(), n, H, W, None if xtab is None else xtab.data_ptr(), kx, plan.RW,
+                                 None if ytab is None else ytab.data_ptr(), ky, plan.RH, plan.top, plan.left, plan.OH,
+                                 plan.OW, lut.data_ptr(), out.data_ptr(), out.stride(0) if n > 1 else 3 * plan.OH * plan.OW,
+                                 _stream()))
+    return out
