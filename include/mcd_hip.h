@@ -492,6 +492,43 @@ int mcd_image_preprocess(const uint8_t* src, int64_t n, int64_t H, int64_t W, co
                          const int32_t* ytab, int64_t ky, int64_t RH, int64_t top, int64_t left, int64_t OH, int64_t OW,
                          const float* lut, float* dst, int64_t dst_img, mcd_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * K23  per-image min-max normalisation, the transform of the mammogram probe sets: src uint8, n images of ONE size packed
+ *      back to back, channels == 3: [n, H, W, 3] (what .convert('RGB') gives), channels == 1: [n, H, W] (a mode-L PNG,
+ *      which .convert('RGB') only replicates) -> dst fp32 [n, 3, H, W], image i at dst + i * dst_img (dst_img >= 3*H*W
+ *      elements; the gap is not written).  With channels == 1 the three planes are identical.
+ *        MCD_IMG_MINMAX  mn, mx = the smallest and the largest byte of image i over ALL of its channels,
+ *                        out = ((f32(v) - f32(mn)) / f32(mx - mn) - mean) / std
+ *                        four IEEE fp32 operations, each rounded once, both divisions real divisions; mx == mn gives
+ *                        NaN in the whole image (0 / 0), which is the reference's result
+ *        MCD_IMG_RAW     out = f32(v); mean and std are ignored, ws may be NULL
+ *      Two launches, no atomics, no memset: (a) grid (chunks, n), a workgroup reduces one chunk of
+ *      MCD_IMAGE_MINMAX_CHUNK bytes of image i (doubled until an image has at most 256 chunks) to an int32 (min, max)
+ *      pair in ws[i][chunk], 16-byte loads on the aligned body, bytes at the chunk's head and tail, nothing outside the
+ *      image is read; (b) grid (tiles, n), every workgroup folds its image's pairs, builds the 256-entry fp32 table in
+ *      LDS (thread v computes entry v) and streams its tile through it.  Wide path (dword loads of 4 pixels, one 16-byte
+ *      store per plane): H*W % 16 == 0, dst_img % 4 == 0, dst 16-byte and src 4-byte aligned; every other shape takes
+ *      scalar accesses.  min and max are integers: an image's bits depend neither on its batch nor on its place in it.
+ *      The workspace function gives the bytes ws needs (0 for a shape the entry refuses).
+ *      MCD_E_ARG: NULL src or dst, channels not 1 or 3, an unknown mode, H or W < 1, n < 0, dst_img < 3*H*W, dst not 4-byte or ws
+ *      not 8-byte aligned, src or ws overlapping dst, MCD_IMG_MINMAX with ws == NULL.  MCD_E_WORKSPACE: ws_bytes too small.
+ *      MCD_E_UNSUPPORTED: n > 65535, one image's source or output of 2^31 bytes or more.  n == 0 is MCD_OK.  On any
+ *      error nothing is written.  No environment variable is read.
+ * replaces  img.astype('float32'); img -= img.min(); img /= img.max(); (img - mean) / std
+ *                                                 data/dataset/image_classification_zs.py:57-96 (:81-84)
+ *           the vindr / vindr_alt loaders          concept_vit/data_utils.py:114-158, data/datamodule.py:53-98,
+ *                                                 data/data_utils.py:25-67 (load_transform: None at 1520 x 912)
+ *           images.permute(0, 3, 1, 2)            concept_vit/utils.py:176
+ *           np.array(Image.open(path), dtype=np.float32), repeat to 3 channels, ToTensor (csaw, csaw_all_splits)
+ *                                                 data/dataset/CSAW_dataset.py:41-68, concept_vit/data_utils.py:254-298
+ * ------------------------------------------------------------------------------------------- */
+#define MCD_IMG_MINMAX 0
+#define MCD_IMG_RAW 1
+#define MCD_IMAGE_MINMAX_CHUNK 16384
+size_t mcd_image_minmax_workspace(int64_t n, int64_t H, int64_t W, int64_t channels);
+int mcd_image_minmax_normalize(const uint8_t* src, int64_t n, int64_t H, int64_t W, int64_t channels, int mode, float mean,
+                               float std, float* dst, int64_t dst_img, void* ws, size_t ws_bytes, mcd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

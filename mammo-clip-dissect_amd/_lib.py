@@ -56,10 +56,13 @@ SIGNATURES = {
     "mcd_attnpool_tokens": (_int, [_p, _i64, _i64, _i64, _p, _p, _p]),
     "mcd_image_preprocess": (_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _i64,
                                     _p]),
+    "mcd_image_minmax_workspace": (_sz, [_i64, _i64, _i64, _i64]),
+    "mcd_image_minmax_normalize": (_int, [_p, _i64, _i64, _i64, _i64, _int, _f, _f, _p, _i64, _p, _sz, _p]),
 }
 
 MCD_E_ARG = -1
 MCD_E_RANGE = -2
+MCD_E_WORKSPACE = -3
 MCD_E_UNSUPPORTED = -5
 
 _lib = None

@@ -1573,11 +1573,99 @@ def decode_rgb(path):
         return np.asarray(img.convert("RGB"), dtype=np.uint8)
 
 
-def host_preprocess(arr, pre):
-    """The host route, and the yardstick of K22: `pre` on one uint8 [H, W, 3] array with PIL itself (Image.resize,
-    Image.crop) and the three torch operations of ToTensor / Normalize -> fp32 [3, OH, OW] on the CPU."""
+# the mammogram sets: reference concept_vit/data_utils.py:114-158 (vindr, vindr_alt) and :254-298 (csaw, csaw_all_splits)
+VINDR_IMG_DIR = "VinDR_MammoCLIP/images_png"
+VINDR_CSV = "VinDR-data/vindr_detection_v1_folds.csv"
+VINDR_DTYPES = {"patient_id": str, "image_id": str, "laterality": str, "view": str, "text1": str, "text_aug": str,
+                "fold": int}                                                       # data/datamodule.py:31-39
+
+
+def list_vindr(data_dir, img_dir=VINDR_IMG_DIR, csv=VINDR_CSV):
+    """DataModule.valid_dataloader() of the vindr set (data/datamodule.py:53-98): the CSV data_dir / csv read with the
+    reference's dtype table (patient_id stays a string: '007' is not 7), NaN -> 0, the rows with split == 'test' in file
+    order.  path = data_dir / img_dir / patient_id / image_id, '.png' appended when the name does not end in it
+    (image_classification_zs.py:51-63); the label is the row's Mass (the drivers ignore labels)."""
+    import pandas as pd
+    df = pd.read_csv(os.path.join(data_dir, csv), dtype=VINDR_DTYPES).fillna(0)
+    df = df[df["split"] == "test"]
+    samples = []
+    for patient_id, image_id, mass in zip(df["patient_id"], df["image_id"], df["Mass"]):
+        path = os.path.join(data_dir, img_dir, str(patient_id), image_id)
+        samples.append((path if path.endswith(".png") else path + ".png", int(mass)))
+    return samples
+
+
+def list_csaw(root, csv, images, split="test"):
+    """CSAWDataset (split 'test' for csaw) / CSAWDataset_all_splits (split None: every row), CSAW_dataset.py:32-48: the
+    CSV root / csv in file order, path = images / anon_filename without its last four characters ('.dcm') + '.png',
+    label = Cancer_visible.  The reference's loader shuffles without a seed; this one keeps the CSV's order."""
+    import pandas as pd
+    df = pd.read_csv(os.path.join(root, csv))
+    if split is not None:
+        df = df.loc[df["split"] == split]
+    return [(os.path.join(images, name[:-4] + ".png"), label) for name, label in zip(df["anon_filename"], df["Cancer_visible"])]
+
+
+def decode_vindr(path):
+    """Image.open(path).convert('RGB') (image_classification_zs.py:72-73) with the replication left out: a mode-L file
+    stays uint8 [H, W] -- .convert('RGB') of it is the same byte three times, and one byte per pixel is uploaded --
+    anything else is converted to uint8 [H, W, 3]."""
     import numpy as np
     from PIL import Image
+    with Image.open(path) as img:
+        if img.mode == "L":
+            return np.asarray(img, dtype=np.uint8)
+        return np.asarray(img.convert("RGB"), dtype=np.uint8)
+
+
+def decode_csaw(path):
+    """np.array(Image.open(path)) of a grey file (CSAW_dataset.py:49-52).  Mode L: uint8 [H, W], converted on the device.
+    Any other 2-D mode (I;16, I, F): float32 [H, W] as the reference's np.array(image, dtype=np.float32) gives it (there
+    is no 16-bit kernel).  A file that decodes to three dimensions is a ValueError (the reference's repeat fails on it)."""
+    import numpy as np
+    from PIL import Image
+    with Image.open(path) as img:
+        arr = np.asarray(img, dtype=np.uint8) if img.mode == "L" else np.array(img, dtype=np.float32)
+    if arr.ndim != 2:
+        raise ValueError("csaw: %s decodes to shape %s; the set takes grey images [H, W]" % (path, arr.shape))
+    return arr
+
+
+def host_minmax(arr, mean, std):
+    """The host route of the vindr transform and the yardstick of K23: image_classification_zs.py:81-85 in numpy on one
+    uint8 [H, W, 3] (or [H, W], replicated as .convert('RGB') does) array -- float32, in-place minus min, in-place
+    divided by max, then (img - mean) / std with the Python floats -- and utils.py:176's permute -> fp32 [3, H, W]."""
+    import numpy as np
+    img = np.asarray(arr)
+    if img.ndim == 2:
+        img = np.repeat(img[:, :, None], 3, axis=2)
+    img = img.astype("float32")
+    with np.errstate(invalid="ignore", divide="ignore"):      # a constant image is 0 / 0: NaN, as in the reference
+        img -= img.min()
+        img /= img.max()
+        t = torch.tensor((img - mean) / std, dtype=torch.float32)
+    return t.permute(2, 0, 1).contiguous()
+
+
+def host_raw(arr):
+    """The host route of the csaw transform: CSAW_dataset.py:50-52 (float32, repeated to three channels) and ToTensor,
+    which on a float array is the permute alone -> fp32 [3, H, W]."""
+    import numpy as np
+    image = np.array(arr, dtype=np.float32)
+    image = np.repeat(image[:, :, np.newaxis], 3, axis=2)
+    return torch.from_numpy(image).permute(2, 0, 1).contiguous()
+
+
+def host_preprocess(arr, pre):
+    """The host route, and the yardstick of K22: `pre` on one uint8 [H, W, 3] array with PIL itself (Image.resize,
+    Image.crop) and the three torch operations of ToTensor / Normalize -> fp32 [3, OH, OW] on the CPU.  The per-pixel
+    specs go to their own host routes (host_minmax, host_raw)."""
+    import numpy as np
+    from PIL import Image
+    if isinstance(pre, core.MinMaxNormalize):
+        return host_minmax(arr, pre.mean, pre.std)
+    if isinstance(pre, core.RawGray):
+        return host_raw(arr)
     plan = pre.plan(arr.shape[0], arr.shape[1])
     img = Image.fromarray(np.ascontiguousarray(arr), "RGB")
     if (plan.RH, plan.RW) != (plan.H, plan.W):
@@ -1597,6 +1685,8 @@ class ImageFileProbe(torch.utils.data.Dataset):
     name or a core.Preprocess); clip_preprocess: the dissector's when it differs -- every item / batch is then the pair
     (target view, dissector view) made from ONE decoded image.  decode: path -> uint8 [H, W, 3] (default decode_rgb).
     lo / hi: this rank's shard of the sample list.
+    A per-pixel spec (core.MinMaxNormalize: vindr, core.RawGray: csaw) is the only view of its set; its decode
+    (decode_vindr, decode_csaw) may give uint8 [H, W] as well, and its device route is K23 (core.image_minmax_normalize).
 
     Host route (device None): dataset[i] -> (tensor, label), PIL + torch (host_preprocess).
     Device route (a CUDA device): device_batches(batch_size) decodes on a thread pool one batch ahead, uploads the
@@ -1611,7 +1701,13 @@ class ImageFileProbe(torch.utils.data.Dataset):
         self.preprocess = core.get_preprocess(preprocess)
         clip = None if clip_preprocess is None else core.get_preprocess(clip_preprocess)
         self.clip_preprocess = None if clip == self.preprocess else clip
-        self.decode = decode_rgb if decode is None else decode
+        pixel = [isinstance(p, (core.MinMaxNormalize, core.RawGray)) for p in self.views]
+        if any(pixel) and len(pixel) > 1:
+            raise ValueError("ImageFileProbe: %r is the transform of its set for both views, not one of a pair"
+                             % (self.views[pixel.index(True)],))
+        if decode is None:
+            decode = {core.MinMaxNormalize: decode_vindr, core.RawGray: decode_csaw}.get(type(self.preprocess), decode_rgb)
+        self.decode = decode
         self.device = None if device is None or torch.device(device).type != "cuda" else torch.device(device)
 
     @property
@@ -1654,8 +1750,37 @@ class ImageFileProbe(torch.utils.data.Dataset):
                 ahead = submit(spans[k + 1]) if k + 1 < len(spans) else None     # decoded while the GPU works on batch k
                 yield self._to_device(arrays)
 
+    def _pixels_to_device(self, arrays, spec):
+        """One batch of a per-pixel spec (MinMaxNormalize, RawGray): a run of consecutive images of one shape, channel
+        count and dtype -> one pinned upload -> one K23 call into the batch slice.  float32 arrays (a 16-bit csaw file)
+        and images past K23's limits are made on the host and uploaded."""
+        sizes = {tuple(a.shape[:2]) for a in arrays}
+        if len(sizes) != 1:
+            raise ValueError("ImageFileProbe: %r gives images of different sizes in one batch: %s" % (spec, sorted(sizes)))
+        H, W = sizes.pop()
+        out = torch.empty((len(arrays), 3, H, W), dtype=torch.float32, device=self.device)
+        i = 0
+        while i < len(arrays):
+            a = arrays[i]
+            j = i + 1
+            while j < len(arrays) and arrays[j].shape == a.shape and arrays[j].dtype == a.dtype:
+                j += 1
+            if a.dtype.name == "uint8" and a.size < 2 ** 31 and 12 * H * W < 2 ** 31:
+                pinned = torch.empty((j - i,) + tuple(a.shape), dtype=torch.uint8, pin_memory=True)
+                staged = pinned.numpy()
+                for r in range(i, j):
+                    staged[r - i] = arrays[r]
+                src = pinned.to(self.device, non_blocking=True)
+                core.image_minmax_normalize(src, spec.mean, spec.std, spec.mode, out=out[i:j])
+            else:
+                out[i:j].copy_(torch.stack([host_preprocess(b, spec) for b in arrays[i:j]]))
+            i = j
+        return [out]
+
     def _to_device(self, arrays):
         """One batch: uint8 [H, W, 3] arrays -> a [B, 3, OH, OW] device tensor per view."""
+        if isinstance(self.preprocess, (core.MinMaxNormalize, core.RawGray)):
+            return self._pixels_to_device(arrays, self.preprocess)
         plans = [[p.plan(a.shape[0], a.shape[1]) for a in arrays] for p in self.views]
         outs = []
         for p, pl in zip(self.views, plans):
@@ -1691,14 +1816,25 @@ DATASET_KINDS = {"imagenet_subsets": ("txt", "tensor"), "imagenet_val": ("folder
                  "broden": ("folder", "imagenet"), "imagenet_broden": ("concat", "imagenet"),
                  "embed_png": ("csv:Implant_type", "embed"), "embed_marker_84": ("csv:Marker", "embed"),
                  "embed_implant": ("csv:Implant_type", "embed"), "embed_marker_only": ("csv:Marker", "embed"),
-                 "embed_non_implant": ("csv:Implant_type", "embed"), "embed_non_implant_100": ("csv:Implant_type", "embed")}
+                 "embed_non_implant": ("csv:Implant_type", "embed"), "embed_non_implant_100": ("csv:Implant_type", "embed"),
+                 "vindr": ("vindr", "vindr"), "vindr_alt": ("vindr", "vindr"),
+                 "csaw": ("csaw:test", "csaw"), "csaw_all_splits": ("csaw:", "csaw")}
+# the mammogram sets always use their own transform, for the target and for the dissector: the reference's get_data
+# ignores `preprocess` for them and one loader feeds both models (utils.py:523-551)
+FIXED_TRANSFORM = ("vindr", "vindr_alt", "csaw", "csaw_all_splits")
+# a set that is registered under another name: the reference's two differ in returning a loader or its dataset
+# (vindr_alt) or in the split filter (csaw_all_splits)
+REGISTERED_AS = {"vindr_alt": "vindr", "csaw_all_splits": "csaw"}
 CONCAT_PARTS = {"imagenet_broden": ("imagenet_val", "broden")}
 DATASET_ROOTS = {}
 
 
 def register_dataset(name, path=None, root=None, csv=None, kind=None, default_preprocess=None):
     """Where a probe set lives: `path` (the text file of a 'txt' set, the class-folder tree of a 'folder' set) or
-    `root` + `csv` (a 'csv:<label column>' set).  kind / default_preprocess: for a name the reference does not have."""
+    `root` + `csv` (a 'csv:<label column>' set).  kind / default_preprocess: for a name the reference does not have.
+    vindr: root = the reference's data_dir; path (the image folder) and csv are relative to it and default to the
+    reference's VINDR_IMG_DIR and VINDR_CSV.  csaw: root, csv (relative to root) and path (the image folder, taken as it
+    is: the reference's imagefolder_path)."""
     if name not in DATASET_KINDS:
         if kind is None:
             raise ValueError("register_dataset: %r is not one of the reference's probe sets; give its kind "
@@ -1722,9 +1858,13 @@ def _list_samples(name):
     if kind == "concat":
         return [s for part in CONCAT_PARTS[name] for s in _list_samples(part)]
     entry = _registered(name)
+    if entry is None and name in REGISTERED_AS:
+        entry = _registered(REGISTERED_AS[name])
     if entry is None:
         raise ValueError("dataset %r has no path: register_dataset(%r, ...) or name a JSON table in MCD_DATASETS"
                          % (name, name))
+    if kind == "vindr" or kind.startswith("csaw:"):
+        return _list_mammo(name, kind, entry)
     paths = [entry.get("root"), entry.get("csv")] if kind.startswith("csv:") else [entry.get("path")]
     for p in paths:
         if p is None or not os.path.exists(p):
@@ -1734,6 +1874,22 @@ def _list_samples(name):
     if kind == "folder":
         return list_folder(paths[0])
     return list_csv(paths[0], paths[1], kind[len("csv:"):])
+
+
+def _list_mammo(name, kind, entry):
+    root = entry.get("root")
+    if kind == "vindr":
+        img_dir, csv = entry.get("path") or VINDR_IMG_DIR, entry.get("csv") or VINDR_CSV
+    else:
+        img_dir, csv = entry.get("path"), entry.get("csv")
+    under = [csv, img_dir] if kind == "vindr" else [csv]          # csaw's image folder is a path of its own, as in the reference
+    needed = [root] + [None if p is None or root is None else os.path.join(root, p) for p in under]
+    for p in needed if kind == "vindr" else needed + [img_dir]:
+        if p is None or not os.path.exists(p):
+            raise FileNotFoundError("dataset %r: %s does not exist" % (name, p))
+    if kind == "vindr":
+        return list_vindr(root, img_dir, csv)
+    return list_csaw(root, csv, img_dir, kind[len("csaw:"):] or None)
 
 
 def target_preset(target_name):
@@ -1746,7 +1902,8 @@ def get_data(dataset_name, preprocess=None, device=None, lo=0, hi=None, clip_pre
     """'synthetic_<N>', 'synthetic_<N>_<size>' (e.g. synthetic_10000_224) or 'synthetic_<N>_<H>x<W>' (H rows, W columns,
     e.g. synthetic_64_1520x912): with a CUDA `device` the probe set is generated on the device and stays resident there
     (DeviceSyntheticImages); lo/hi select a rank's shard of it.
-    The reference's file sets (DATASET_KINDS: imagenet_subsets, imagenet_val, broden, imagenet_broden, embed_*) once
+    The reference's file sets (DATASET_KINDS: imagenet_subsets, imagenet_val, broden, imagenet_broden, embed_*, and the
+    mammogram sets vindr, vindr_alt, csaw, csaw_all_splits, which keep their own transform: K23, FIXED_TRANSFORM) once
     their paths are registered: an ImageFileProbe over images lo..hi-1.  preprocess / clip_preprocess: a preset name, a
     core.Preprocess or None (preprocess: the set's own default, 'tensor', 'imagenet' or 'embed' as in the reference;
     clip_preprocess: no second view; 'default' there names the set's own default).  With a CUDA `device` the set
@@ -1765,9 +1922,20 @@ def get_data(dataset_name, preprocess=None, device=None, lo=0, hi=None, clip_pre
         return ds
     if dataset_name in DATASET_KINDS:
         default = DATASET_KINDS[dataset_name][1]
+        if dataset_name in FIXED_TRANSFORM:
+            for given in (preprocess, clip_preprocess):
+                if not (given is None or (isinstance(given, str) and given == "default")
+                        or core.get_preprocess(given) == core.PRESETS[default]):
+                    raise ValueError("dataset %r always uses its own transform %r for the target and for the dissector "
+                                     "(the reference ignores `preprocess` for it); got %r"
+                                     % (dataset_name, core.PRESETS[default], given))
+            return ImageFileProbe(_list_samples(dataset_name), default, None, lo=lo, hi=hi, device=device)
         if isinstance(clip_preprocess, str) and clip_preprocess == "default":
             clip_preprocess = default
         return ImageFileProbe(_list_samples(dataset_name), default if preprocess is None else preprocess,
                               clip_preprocess, lo=lo, hi=hi, device=device)
+    if dataset_name == "combined":
+        raise ValueError("dataset 'combined' is not available offline: it mixes imagenet_subsets (224 x 224) and vindr_alt "
+                         "(1520 x 912) in one loader, and a batch here holds images of one size; dissect the two sets apart")
     raise ValueError("dataset %r is not available offline; use synthetic_<N>[_<size> | _<H>x<W>] or one of %s"
                      % (dataset_name, ", ".join(sorted(DATASET_KINDS))))

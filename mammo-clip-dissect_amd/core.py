@@ -1048,9 +1048,43 @@ PRESETS = {
 }
 
 
+class _PixelSpec:
+    """A transform that keeps the source size and maps every byte on its own (K23): no plan, no resample table."""
+    _fields = ()
+
+    def _key(self):
+        return tuple(getattr(self, f) for f in self._fields)
+
+    def __eq__(self, other):
+        return type(other) is type(self) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash((type(self).__name__,) + self._key())
+
+    def __repr__(self):
+        return "%s(%s)" % (type(self).__name__, ", ".join("%s=%r" % (f, getattr(self, f)) for f in self._fields))
+
+
+class MinMaxNormalize(_PixelSpec):
+    """The vindr transform (image_classification_zs.py:81-84): per-image min-max over all channels to [0, 1], then
+    (x - mean) / std with one scalar mean and std.  Output size = source size."""
+    _fields = ("mean", "std")
+    mode = "minmax"
+
+    def __init__(self, mean, std):
+        self.mean, self.std = float(mean), float(std)
+
+
+class RawGray(_PixelSpec):
+    """The csaw transform (CSAW_dataset.py:49-55): the grey values as fp32, repeated to three channels.  Output size =
+    source size."""
+    mode = "raw"
+    mean, std = 0.0, 1.0
+
+
 def get_preprocess(p):
-    """A preset name or a Preprocess -> the Preprocess."""
-    if isinstance(p, Preprocess):
+    """A preset name or a spec (Preprocess, MinMaxNormalize, RawGray) -> the spec."""
+    if isinstance(p, (Preprocess, _PixelSpec)):
         return p
     if p not in PRESETS:
         raise ValueError("unknown preprocess %r (presets: %s)" % (p, ", ".join(sorted(PRESETS))))
@@ -1098,4 +1132,44 @@ def image_preprocess(src_u8, preprocess, out=None):
                                  None if ytab is None else ytab.data_ptr(), ky, plan.RH, plan.top, plan.left, plan.OH,
                                  plan.OW, lut.data_ptr(), out.data_ptr(), out.stride(0) if n > 1 else 3 * plan.OH * plan.OW,
                                  _stream()))
+    return out
+
+
+# ---- K23: per-image min-max normalisation (csrc/k_image.hip) -----------------------------------------
+IMAGE_MINMAX_CHUNK = 16384                 # MCD_IMAGE_MINMAX_CHUNK: the bytes one workgroup of the reduction covers
+IMAGE_MODES = {"minmax": 0, "raw": 1}      # MCD_IMG_MINMAX, MCD_IMG_RAW
+PRESETS["vindr"] = MinMaxNormalize(0.3089279, 0.25053555408335154)                  # concept_vit/data_utils.py:121-122
+PRESETS["csaw"] = RawGray()                                                         # concept_vit/data_utils.py:254-257
+
+
+@_on_device
+def image_minmax_normalize(src_u8, mean, std, mode="minmax", out=None):
+    """K23: uint8 images of one size on the GPU, contiguous [n, H, W, 3] or [n, H, W] (grey) -> fp32 [n, 3, H, W].
+    mode 'minmax': ((v - min) / (max - min) - mean) / std with the image's own min and max over all channels, the fp32
+    bits of the reference's numpy operations (a constant image is NaN); 'raw': f32(v), mean and std ignored.  out: where
+    to write, e.g. a slice of a batch tensor: fp32 [n, 3, H, W] with each image contiguous (image_preprocess's rules)."""
+    _need_gpu(src_u8, out)
+    if src_u8.dtype != torch.uint8 or not src_u8.is_contiguous() or not (
+            src_u8.dim() == 3 or (src_u8.dim() == 4 and src_u8.shape[3] == 3)):
+        raise TypeError("image_minmax_normalize: src must be a contiguous uint8 [n, H, W, 3] or [n, H, W] tensor")
+    if mode not in IMAGE_MODES:
+        raise ValueError("image_minmax_normalize: mode must be one of %s, got %r" % (sorted(IMAGE_MODES), mode))
+    n, H, W = src_u8.shape[:3]
+    channels = 3 if src_u8.dim() == 4 else 1
+    shape = (n, 3, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=src_u8.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != shape or (n > 0 and not out[0].is_contiguous()) \
+            or (n > 1 and out.stride(0) < 3 * H * W):
+        raise ValueError("image_minmax_normalize: out must be float32 %s with contiguous images" % (shape,))
+    if n == 0:
+        return out
+    L = _lib.load()
+    ws, ws_bytes = None, 0
+    if mode == "minmax":
+        ws_bytes = int(L.mcd_image_minmax_workspace(n, H, W, channels))
+        ws = torch.empty((max(ws_bytes, 8) // 4,), dtype=torch.int32, device=src_u8.device)
+    check(L.mcd_image_minmax_normalize(src_u8.data_ptr(), n, H, W, channels, IMAGE_MODES[mode], float(mean), float(std),
+                                       out.data_ptr(), out.stride(0) if n > 1 else 3 * H * W,
+                                       None if ws is None else ws.data_ptr(), ws_bytes, _stream()))
     return out

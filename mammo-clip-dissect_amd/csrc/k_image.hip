@@ -1,4 +1,5 @@
-// k_image.hip -- K22: probe-image preprocessing, packed RGB uint8 [n, H, W, 3] -> fp32 [n, 3, OH, OW] in one launch.
+// k_image.hip -- K22 and K23: the probe sets' image transforms on the device (K23: per-image min-max, below K22).
+// K22: probe-image preprocessing, packed RGB uint8 [n, H, W, 3] -> fp32 [n, 3, OH, OW] in one launch.
 //   replaces Resize -> CenterCrop -> ToTensor -> Normalize on PIL images:
 //     get_resnet_imagenet_preprocess   concept_vit/data_utils.py:95-100
 //     CLIP's _transform                concept_vit/clip/clip.py:79-86
@@ -189,5 +190,242 @@ extern "C" int mcd_image_preprocess(const uint8_t* src, int64_t n, int64_t H, in
                        (int)H, (int)W, xtab, (int)kx, ytab, (int)ky, (int)top, (int)left, (int)OH, (int)OW, TH, (int)tiles_x,
                        (int)tiles, (int)need, lut, dst, dst_img);
     MCD_LAUNCH_CHECK("image_preprocess_kernel");
+    return MCD_OK;
+}
+
+// ---- K23: per-image min-max normalisation of the mammogram probe sets ---------------------------------------------------
+//   replaces img.astype('float32'); img -= img.min(); img /= img.max(); (img - mean) / std
+//                                            data/dataset/image_classification_zs.py:81-84  (vindr, vindr_alt)
+//            the permute to [B, 3, H, W]     concept_vit/utils.py:176
+//            np.array(Image.open(path), dtype=np.float32) repeated to three channels + ToTensor
+//                                            data/dataset/CSAW_dataset.py:49-55             (csaw, csaw_all_splits)
+// Two launches, no atomics, no memset:
+//   (a) minmax_partial_kernel, grid (chunks, n): a workgroup reduces one contiguous chunk of an image's bytes to an int32
+//       (min, max) pair.  16-byte loads on the aligned body, bytes on the chunk's head and tail; nothing outside the image
+//       is read.
+//   (b) minmax_apply_kernel, grid (tiles, n): every workgroup folds its image's <= 256 pairs, thread v computes the table
+//       entry of byte v with the reference's four fp32 operations (each rounded once: the file is compiled with
+//       -fno-fast-math -ffp-contract=off, and the divisions stay divisions), then the tile is streamed: packed bytes in,
+//       one LDS look-up per byte, fp32 planes out.  Wide path: a lane reads 4 consecutive pixels (one dword, three for
+//       RGB) and stores one float4 per plane, so a wave's store instruction covers 1 KB of one plane without a gap.
+// min and max are integers, so their fold is order-independent: an image's bits depend neither on the batch nor on its
+// place in it.
+namespace {
+
+constexpr int kMinMaxChunk = MCD_IMAGE_MINMAX_CHUNK;   // bytes of one partial reduction (doubled while an image has more than 256)
+constexpr int kMinMaxMaxChunks = 256;
+constexpr int kApplyTile = 8192;                       // pixels of one apply workgroup: 8 steps of 256 lanes x 4 pixels
+
+typedef unsigned short mcd_u16x2 __attribute__((ext_vector_type(2)));
+
+// chunk bytes for an image of `bytes` bytes: kMinMaxChunk, doubled until at most 256 chunks cover the image
+inline int64_t minmax_chunk_bytes(int64_t bytes) {
+    int64_t c = kMinMaxChunk;
+    while (mcd_cdiv(bytes, c) > kMinMaxMaxChunks) c *= 2;
+    return c;
+}
+
+__device__ __forceinline__ void fold_byte(int v, int& mn, int& mx) {
+    mn = v < mn ? v : mn;
+    mx = v > mx ? v : mx;
+}
+
+// min / max over the four bytes of w, two bytes at a time as packed 16-bit lanes
+__device__ __forceinline__ void fold_dword(uint32_t w, mcd_u16x2& mn, mcd_u16x2& mx) {
+    const uint32_t e = w & 0x00ff00ffu, o = (w >> 8) & 0x00ff00ffu;
+    const mcd_u16x2 ev = __builtin_bit_cast(mcd_u16x2, e), ov = __builtin_bit_cast(mcd_u16x2, o);
+    mn = __builtin_elementwise_min(mn, __builtin_elementwise_min(ev, ov));
+    mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(ev, ov));
+}
+
+// (min, max) over the workgroup's 256 threads; the result is valid in every thread
+__device__ __forceinline__ void block_minmax(int& mn, int& mx, int* smem /* [8] */) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int a = __shfl_xor(mn, o, 64), b = __shfl_xor(mx, o, 64);
+        mn = a < mn ? a : mn;
+        mx = b > mx ? b : mx;
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        smem[wave] = mn;
+        smem[4 + wave] = mx;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        mn = smem[w] < mn ? smem[w] : mn;
+        mx = smem[4 + w] > mx ? smem[4 + w] : mx;
+    }
+}
+
+__global__ __launch_bounds__(256) void minmax_partial_kernel(const uint8_t* __restrict__ src, int64_t img_bytes, int chunk,
+                                                             int chunks, int32_t* __restrict__ ws) {
+    __shared__ int smem[8];
+    const int tid = threadIdx.x;
+    const uint8_t* __restrict__ s = src + (int64_t)blockIdx.y * img_bytes;
+    const int64_t c0 = (int64_t)blockIdx.x * chunk;
+    const int len = (int)(img_bytes - c0 < chunk ? img_bytes - c0 : chunk);       // >= 1: chunks = cdiv(img_bytes, chunk)
+    const uint8_t* __restrict__ p = s + c0;
+    // head: the bytes in front of the first 16-byte boundary; body: whole 16-byte pieces; tail: what is left
+    int head = (int)((16 - ((uintptr_t)p & 15)) & 15);
+    head = head > len ? len : head;
+    const int body = (len - head) / 16;
+    int mn = 255, mx = 0;
+    if (tid < head) fold_byte(p[tid], mn, mx);
+    const uint4* __restrict__ q = reinterpret_cast<const uint4*>(p + head);
+    mcd_u16x2 vmn = {255, 255}, vmx = {0, 0};
+    for (int i = tid; i < body; i += 256) {
+        const uint4 w = q[i];
+        fold_dword(w.x, vmn, vmx);
+        fold_dword(w.y, vmn, vmx);
+        fold_dword(w.z, vmn, vmx);
+        fold_dword(w.w, vmn, vmx);
+    }
+    const int bmn = vmn.x < vmn.y ? vmn.x : vmn.y, bmx = vmx.x > vmx.y ? vmx.x : vmx.y;     // {255, 0} without a body
+    mn = bmn < mn ? bmn : mn;
+    mx = bmx > mx ? bmx : mx;
+    const int t0 = head + body * 16;
+    if (t0 + tid < len) fold_byte(p[t0 + tid], mn, mx);                             // the tail is under 16 bytes
+    block_minmax(mn, mx, smem);
+    if (tid == 0) {
+        int32_t* __restrict__ o = ws + 2 * ((int64_t)blockIdx.y * chunks + blockIdx.x);
+        o[0] = mn;
+        o[1] = mx;
+    }
+}
+
+// CH: 1 (grey [n, H, W]) or 3 (packed RGB [n, H, W, 3]).  WIDE: HW % 16 == 0 and src, dst, dst_img aligned for dword loads
+// of 4 pixels and float4 stores.  chunks == 0: MCD_IMG_RAW, the table is f32(v) and ws is not read.
+template <int CH, bool WIDE>
+__global__ __launch_bounds__(256) void minmax_apply_kernel(const uint8_t* __restrict__ src, int HW, const int32_t* __restrict__ ws,
+                                                           int chunks, float mean, float std, float* __restrict__ dst,
+                                                           int64_t dst_img) {
+    __shared__ float slut[256];
+    __shared__ int smem[8];
+    const int tid = threadIdx.x;
+    const int64_t img = blockIdx.y;
+    if (chunks > 0) {
+        int mn = 255, mx = 0;
+        if (tid < chunks) {
+            const int32_t* __restrict__ w = ws + 2 * (img * chunks + tid);
+            mn = w[0];
+            mx = w[1];
+        }
+        block_minmax(mn, mx, smem);
+        float t = (float)tid - (float)mn;      // img -= img.min()
+        t = t / (float)(mx - mn);              // img /= img.max()    (0 / 0 = NaN for a constant image)
+        t = t - mean;
+        t = t / std;
+        slut[tid] = t;
+    } else {
+        slut[tid] = (float)tid;
+    }
+    __syncthreads();
+
+    const uint8_t* __restrict__ s = src + img * ((int64_t)HW * CH);
+    float* __restrict__ d = dst + img * dst_img;
+    const int p0 = blockIdx.x * kApplyTile;
+    if (WIDE) {
+        constexpr int kSteps = kApplyTile / 1024;
+        uint32_t w[kSteps][CH];
+#pragma unroll
+        for (int k = 0; k < kSteps; ++k) {
+            const int p = p0 + k * 1024 + tid * 4;
+            if (p < HW) {                      // HW % 4 == 0: the four pixels are inside together
+                const uint32_t* __restrict__ q = reinterpret_cast<const uint32_t*>(s + (int64_t)p * CH);
+#pragma unroll
+                for (int c = 0; c < CH; ++c) w[k][c] = q[c];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kSteps; ++k) {
+            const int p = p0 + k * 1024 + tid * 4;
+            if (p < HW) {
+                if (CH == 1) {
+                    const uint32_t v = w[k][0];
+                    const float4 o = make_float4(slut[v & 255], slut[(v >> 8) & 255], slut[(v >> 16) & 255], slut[v >> 24]);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) *reinterpret_cast<float4*>(d + (int64_t)c * HW + p) = o;
+                } else {
+                    // 12 bytes r0 g0 b0 r1 g1 b1 r2 g2 b2 r3 g3 b3 in three dwords
+                    float f[12];
+#pragma unroll
+                    for (int j = 0; j < 12; ++j) f[j] = slut[(w[k][(j / 4) % CH] >> (8 * (j % 4))) & 255];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c)
+                        *reinterpret_cast<float4*>(d + (int64_t)c * HW + p) = make_float4(f[c], f[3 + c], f[6 + c], f[9 + c]);
+                }
+            }
+        }
+    } else {
+        const int p1 = HW - p0 < kApplyTile ? HW : p0 + kApplyTile;
+        for (int p = p0 + tid; p < p1; p += 256) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) d[(int64_t)c * HW + p] = slut[s[(int64_t)p * CH + (CH == 1 ? 0 : c)]];
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" size_t mcd_image_minmax_workspace(int64_t n, int64_t H, int64_t W, int64_t channels) {
+    if (n < 1 || H < 1 || W < 1 || (channels != 1 && channels != 3)) return 0;
+    if (H > (((int64_t)1 << 31) - 1) / channels / W) return 0;
+    const int64_t bytes = H * W * channels;
+    return (size_t)(n * mcd_cdiv(bytes, minmax_chunk_bytes(bytes)) * 2 * (int64_t)sizeof(int32_t));
+}
+
+extern "C" int mcd_image_minmax_normalize(const uint8_t* src, int64_t n, int64_t H, int64_t W, int64_t channels, int mode,
+                                          float mean, float std, float* dst, int64_t dst_img, void* ws, size_t ws_bytes,
+                                          mcd_stream_t stream) {
+    MCD_REQUIRE(src && dst, MCD_E_ARG, "mcd_image_minmax_normalize: NULL pointer");
+    MCD_REQUIRE(channels == 1 || channels == 3, MCD_E_ARG, "mcd_image_minmax_normalize: channels %lld is not 1 or 3",
+                (long long)channels);
+    MCD_REQUIRE(mode == MCD_IMG_MINMAX || mode == MCD_IMG_RAW, MCD_E_ARG, "mcd_image_minmax_normalize: unknown mode %d", mode);
+    MCD_REQUIRE(n >= 0 && H >= 1 && W >= 1, MCD_E_ARG, "mcd_image_minmax_normalize: bad shape n=%lld H=%lld W=%lld",
+                (long long)n, (long long)H, (long long)W);
+    MCD_REQUIRE((uintptr_t)dst % 4 == 0 && (uintptr_t)ws % 8 == 0, MCD_E_ARG,
+                "mcd_image_minmax_normalize: dst must be 4-byte and ws 8-byte aligned");
+    const bool minmax = mode == MCD_IMG_MINMAX;
+    MCD_REQUIRE(!minmax || ws, MCD_E_ARG, "mcd_image_minmax_normalize: MCD_IMG_MINMAX needs a workspace");
+    const int64_t lim = (int64_t)1 << 31;
+    MCD_REQUIRE(n <= 65535, MCD_E_UNSUPPORTED, "mcd_image_minmax_normalize: n %lld > 65535 images in one call", (long long)n);
+    MCD_REQUIRE(H <= (lim - 1) / channels / W && H <= (lim - 1) / 12 / W, MCD_E_UNSUPPORTED,
+                "mcd_image_minmax_normalize: one image (H*W*channels or 3*H*W*4 bytes) reaches 2^31");
+    const int64_t HW = H * W, img_bytes = HW * channels;
+    MCD_REQUIRE(dst_img >= 3 * HW && dst_img < ((int64_t)1 << 40), MCD_E_ARG,
+                "mcd_image_minmax_normalize: dst_img %lld is not in [3*H*W, 2^40)", (long long)dst_img);
+    if (n == 0) return MCD_OK;
+    const int64_t out_bytes = ((n - 1) * dst_img + 3 * HW) * 4;
+    const int64_t chunk = minmax_chunk_bytes(img_bytes), chunks = mcd_cdiv(img_bytes, chunk);
+    const int64_t need = n * chunks * 2 * (int64_t)sizeof(int32_t);
+    MCD_REQUIRE(!overlaps(src, n * img_bytes, dst, out_bytes), MCD_E_ARG, "mcd_image_minmax_normalize: src overlaps dst");
+    if (minmax) {
+        MCD_REQUIRE(ws_bytes >= (size_t)need, MCD_E_WORKSPACE,
+                    "mcd_image_minmax_normalize: workspace %zu < %lld bytes", ws_bytes, (long long)need);
+        MCD_REQUIRE(!overlaps(ws, need, dst, out_bytes), MCD_E_ARG, "mcd_image_minmax_normalize: ws overlaps dst");
+    }
+
+    hipStream_t st = (hipStream_t)stream;
+    int32_t* pairs = static_cast<int32_t*>(ws);
+    if (minmax) {
+        hipLaunchKernelGGL(minmax_partial_kernel, dim3((unsigned)chunks, (unsigned)n), dim3(256), 0, st, src, img_bytes,
+                           (int)chunk, (int)chunks, pairs);
+        MCD_LAUNCH_CHECK("minmax_partial_kernel");
+    }
+    const bool wide = HW % 16 == 0 && dst_img % 4 == 0 && (uintptr_t)dst % 16 == 0 && (uintptr_t)src % 4 == 0;
+    const dim3 grid((unsigned)mcd_cdiv(HW, kApplyTile), (unsigned)n);
+    const int fold = minmax ? (int)chunks : 0;
+#define MCD_APPLY(CH, WIDE)                                                                                              \
+    hipLaunchKernelGGL((minmax_apply_kernel<CH, WIDE>), grid, dim3(256), 0, st, src, (int)HW, pairs, fold, mean, std, dst, \
+                       dst_img)
+    if (channels == 1) {
+        if (wide) MCD_APPLY(1, true); else MCD_APPLY(1, false);
+    } else {
+        if (wide) MCD_APPLY(3, true); else MCD_APPLY(3, false);
+    }
+#undef MCD_APPLY
+    MCD_LAUNCH_CHECK("minmax_apply_kernel");
     return MCD_OK;
 }
