@@ -21,7 +21,9 @@ typedef void* mcd_blaslt_stream_t; /* hipStream_t */
 /* text of the last error of this thread (libmcd_blaslt.so keeps its own) */
 const char* mcd_blaslt_last_error(void);
 
-/* bytes of workspace the caller should provide (32 MiB) */
+/* bytes of workspace the caller should provide (32 MiB).  A recommendation, not a requirement: ws / ws_bytes bound the hipBLASLt
+ * algorithms a shape's first call may choose from (ws == NULL or ws_bytes == 0: those that need none), so a smaller workspace is no
+ * error by itself.  A later call of that shape with less than the kept algorithm needs is MCD_E_ARG, and nothing is written. */
 size_t mcd_linear_residual_workspace(void);
 
 /* out[M,N] = res[M,N] + h[M,K] . W[N,K]^T + bias[N], all fp32 row-major with leading dimensions ld*.

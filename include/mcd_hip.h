@@ -101,7 +101,8 @@ int mcd_prepare_rows_gathered(const float* src, int64_t ld_src, int64_t ld_block
  *           (og_utils.py:501, CLIP_og_utils.py:160)
  * ws: optional scratch of mcd_embed_gemm_workspace() bytes (0 for MCD_GEMM_F32 and for small problems).  With
  * it, the bf16 modes convert the operands to bf16 once and run the 256x256-tile kernel (the stress shape);
- * without it (NULL / too small) they run the 128x128 kernel that converts while staging -- same results per mode.
+ * without it (NULL / fewer bytes than that / not 16-byte aligned) they run the 128x128 kernel that converts while staging and
+ * leave ws alone -- same results per mode (MCD_OK either way: a workspace is never an error of this entry).
  * ------------------------------------------------------------------------------------------- */
 size_t mcd_embed_gemm_workspace(int64_t N, int64_t C, int64_t D, int mode);
 int mcd_embed_gemm(const float* I, int64_t ldi, const float* T, int64_t ldt, int64_t N, int64_t C, int64_t D,
@@ -124,7 +125,9 @@ int mcd_row_softmax(const float* P, int64_t ldp, int64_t N, int64_t C, float a, 
  * A element (n,u) at A[n*stride_n + u*stride_u]; exactly one of the strides must be 1
  * (image-major: stride_u == 1; neuron-major: stride_n == 1).
  * Outputs are NEURON-major: vals[u*ldo + j], idx[u*ldo + j], j < K (either may be NULL).
- * Image-major input is transposed through `ws` (mcd_col_topk_workspace bytes; 0 for neuron-major).
+ * ws: mcd_col_topk_workspace() bytes, 16-byte aligned, for either layout: one "left to the streaming kernel" word per neuron
+ * (rounded up to 256 bytes), which the entry writes before it reads it, and behind them, for image-major input, the [U, ceil4(N)]
+ * transposed copy.  ws == NULL or ws_bytes too small: MCD_E_WORKSPACE; ws not 16-byte aligned: MCD_E_ARG; nothing is written.
  * Returns MCD_E_RANGE when K > N (torch raises "selected index k out of range").
  * ------------------------------------------------------------------------------------------- */
 size_t mcd_col_topk_workspace(int64_t N, int64_t U, int64_t stride_n, int64_t stride_u, int K);
@@ -166,7 +169,10 @@ int mcd_wpmi_score(const float* S, int64_t ldS, int64_t N, int64_t C, const int3
  *   or raw with MCD_GEMM_EXP_NORMALIZE in `flags`;
  *   E is [N, ldE] bf16, ldE a multiple of 16 (anything else: MCD_E_UNSUPPORTED; K4s wants a multiple of 128), columns
  *   C..ldE-1 written as 0; rinv[n] = 1 / (the sum of row n's STORED bf16 values), so E * rinv sums to 1 over a row; ws of
- *   mcd_embed_gemm_exp_workspace() bytes holds the bf16 operands and the per-tile partial row sums.
+ *   mcd_embed_gemm_exp_workspace() bytes, 16-byte aligned, holds the bf16 operands and the per-tile partial row sums (the entry
+ *   writes every byte it later reads, the zero padding of the operand image included); ws == NULL, ws_bytes too small or ws not
+ *   16-byte aligned: MCD_E_WORKSPACE, nothing is written.  mcd_wpmi_score_bf16: ws of mcd_wpmi_score_bf16_workspace() bytes,
+ *   8-byte aligned; NULL, too small or misaligned: MCD_E_WORKSPACE, nothing is written.
  * replaces  clip_feats = image_features @ text_features.T                 concept_vit/utils.py:594
  *           clip_feats = torch.nn.functional.softmax(a*clip_feats, dim=1)  concept_vit/similarity.py:54, :80
  * K4 on that representation:
@@ -201,7 +207,9 @@ int mcd_wpmi_score_bf16(const uint16_t* E, int64_t ldE, int64_t N, int64_t C, co
  *           mutual_info = prob_d_given_e - lam*prob_d                     concept_vit/similarity.py:70-72, :92-96
  * seg_offsets is a HOST array of n_seg+1 ascending row offsets (n_seg <= 64; a segment without rows is skipped); out may alias pdge.
  * ws: device scratch of mcd_logsumexp_sub_workspace(total rows, C, n_seg) bytes (column maxima and the
- * 16-row partial sums that ATen's summation order chains).
+ * 16-row partial sums that ATen's summation order chains), aligned for float; only the three-pass path (a segment of more than
+ * 3840 rows) uses it, and it writes what it reads.  ws == NULL or ws_bytes too small: MCD_E_WORKSPACE on either path, nothing is
+ * written.  seg_offsets is read during the call only (a captured graph keeps no pointer to it).
  * ------------------------------------------------------------------------------------------- */
 size_t mcd_logsumexp_sub_workspace(int64_t U_total, int64_t C, int n_seg);
 int mcd_logsumexp_sub(const float* pdge, int64_t ld, int64_t C, const int64_t* seg_offsets, int n_seg, float lam,
@@ -235,7 +243,7 @@ int mcd_hook_pool(const float* x, int64_t B, int64_t Cout, int64_t HW, int mode,
  *      descending order and their image indices (mcd_col_topk's output); perms is int32 [U, n_perm, top_n],
  *      the random permutations of the baseline (the reference draws them with torch.randperm on the global CPU
  *      generator, 5 per neuron in neuron order -- the host mirror does the same so a seeded run reproduces the
- *      reference); baseline_ws is caller-owned scratch of U floats.
+ *      reference); baseline_ws is caller-owned scratch of U floats (no ws_bytes: NULL is MCD_E_ARG), written before it is read.
  *      out[u,c] = -( mean_j |t_j - st[rank_jc]|^p / baseline_u ) / mean_j(P[idx_j, c])^scale_p
  * replaces  the per-neuron Python loop of rank_reorder                    concept_vit/similarity.py:107-132
  * ------------------------------------------------------------------------------------------- */

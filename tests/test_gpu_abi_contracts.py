@@ -23,11 +23,12 @@ import numpy as np
 import pytest
 import torch
 
-from util import GAP_FILLS, OUT_FILL, check_frame, framed, int_bits
+from util import FRAME_GUARD as GUARD   # elements: 256 bytes of fp32 / int32, 128 of bf16 -- base offset 0 is 16-byte aligned
+from util import GAP_FILLS, OUT_FILL, check_frame, int_bits
+from util import FramedIn as In, FramedOut as Out
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64          # elements: 256 bytes of fp32 / int32, 128 of bf16 -- base offset 0 is 16-byte aligned
 IDX_FILL = -77777   # the OUT_FILL of int32 outputs
 
 
@@ -68,31 +69,6 @@ def one_at_a_time(*classes, offs):
             out.append((tuple(base), tuple(zero[:i] + [1] + zero[i + 1:])))
     out.append((tuple(next((p for p in c if p % 2), c[1]) for c in classes), tuple(1 if o else 0 for o in offs)))
     return uniq(out)
-
-
-class In:
-    """A matrix inside a framed allocation whose gaps hold `gap`; .same() says the call left the allocation untouched."""
-
-    def __init__(self, data, pitch, off, gap):
-        rows, width = data.shape      # (the last row whole, as a caller's matrix has it: a 16-byte path may read its padding)
-        self.flat, self.view = framed(rows, width, pitch, off, GUARD, gap, data.dtype, data.device, tail=pitch - width)
-        self.view.copy_(data)
-        self.snap = self.flat.clone()
-        self.ptr, self.ld = self.view.data_ptr(), pitch
-        self.spec = (rows, width, pitch, off, GUARD, gap)
-
-    def same(self):
-        assert torch.equal(int_bits(self.flat), int_bits(self.snap)), "the call changed an input"
-
-
-class Out:
-    def __init__(self, rows, width, pitch, off, dtype, dev, tail=0, fill=OUT_FILL):
-        self.spec = (rows, width, pitch, off, GUARD, fill)
-        self.flat, self.view = framed(*self.spec, dtype, dev, tail=tail)
-        self.ptr, self.ld = self.view.data_ptr(), pitch
-
-    def check(self, expected, zero_pad=False, what=""):
-        check_frame(self.flat, self.spec, expected, zero_pad=zero_pad, what=str(what))
 
 
 def dense(view):

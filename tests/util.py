@@ -471,3 +471,84 @@ def check_frame(flat, view_spec, expected_bits, zero_pad=False, what=""):
             ("the leading guard / base offset" if o < 0 else "the trailing guard")
         raise AssertionError("%s: %d elements outside the logical region changed (or a promised zero is not +0), the first "
                              "at flat[%d] = %s" % (what, bad.shape[0], int(bad[0, 0]), where))
+
+
+FRAME_GUARD = 64    # elements of guard on each side of a FramedIn / FramedOut: 256 bytes of fp32 / int32, 128 of bf16
+
+
+class FramedIn:
+    """A matrix inside a framed allocation whose gaps hold `gap`; .same() says the call left the allocation untouched."""
+
+    def __init__(self, data, pitch, off, gap):
+        rows, width = data.shape      # (the last row whole, as a caller's matrix has it: a 16-byte path may read its padding)
+        self.flat, self.view = framed(rows, width, pitch, off, FRAME_GUARD, gap, data.dtype, data.device, tail=pitch - width)
+        self.view.copy_(data)
+        self.snap = self.flat.clone()
+        self.ptr, self.ld = self.view.data_ptr(), pitch
+        self.spec = (rows, width, pitch, off, FRAME_GUARD, gap)
+
+    def same(self):
+        assert torch.equal(int_bits(self.flat), int_bits(self.snap)), "the call changed an input"
+
+
+class FramedOut:
+    def __init__(self, rows, width, pitch, off, dtype, dev, tail=0, fill=OUT_FILL):
+        self.spec = (rows, width, pitch, off, FRAME_GUARD, fill)
+        self.flat, self.view = framed(*self.spec, dtype, dev, tail=tail)
+        self.ptr, self.ld = self.view.data_ptr(), pitch
+
+    def check(self, expected, zero_pad=False, what=""):
+        check_frame(self.flat, self.spec, expected, zero_pad=zero_pad, what=str(what))
+
+
+# ---- framed workspaces: the C ABI's workspace contract (test_gpu_workspace_contracts.py, test_exec_contract_cpu.py) ---------
+WS_GUARD = 4096                   # bytes of guard on each side of a workspace frame
+WS_ALIGN = 256                    # alignment of a framed workspace's interior
+WS_FILLS = (0x00, 0xFF, 0x7F)     # what a workspace (and its guards) holds before the call, one run each: 0xFF.. is int32 -1 (K3's
+                                  # mark) and a NaN as fp32 and as bf16; 0x7F.. is a large finite fp32 (3.4e38) and a bf16 NaN
+
+
+def framed_ws(nbytes, guard_bytes=WS_GUARD, fill_byte=0xFF, device="cpu"):
+    """(flat, ptr, nbytes): ONE uint8 allocation -- guard | nbytes | guard, the interior WS_ALIGN-byte aligned -- all of it,
+    the interior included, `fill_byte`; ptr = the address of the interior.  (The bytes in front of the leading guard that the
+    alignment costs and those behind the trailing guard belong to the guards: check_ws_guards() wants all of them kept.)"""
+    assert nbytes >= 0 and guard_bytes >= 0 and 0 <= fill_byte <= 255
+    flat = torch.full((guard_bytes + nbytes + guard_bytes + WS_ALIGN,), fill_byte, dtype=torch.uint8, device=device)
+    start = guard_bytes + (-(flat.data_ptr() + guard_bytes)) % WS_ALIGN
+    flat.ws_start = start
+    return flat, flat.data_ptr() + start, nbytes
+
+
+def ws_interior(flat, nbytes):
+    return flat[flat.ws_start:flat.ws_start + nbytes]
+
+
+def check_ws_guards(flat, nbytes, fill_byte, what=""):
+    """Both guards of a framed_ws() allocation -- every byte outside the `nbytes` of the interior -- still hold the fill."""
+    start = flat.ws_start
+    for name, part, base in (("leading", flat[:start], 0), ("trailing", flat[start + nbytes:], start + nbytes)):
+        bad = (part != fill_byte).nonzero()
+        assert bad.numel() == 0, "%s: %d bytes of the workspace's %s guard changed, the first %d bytes %s" % (
+            what, bad.shape[0], name, (start - int(bad[0, 0])) if name == "leading" else int(bad[0, 0]) + 1,
+            "in front of the workspace" if name == "leading" else "past its end")
+
+
+def check_ws_untouched(flat, fill_byte, what=""):
+    """A refused call: the whole allocation, interior and guards, still holds the fill."""
+    bad = (flat != fill_byte).nonzero()
+    assert bad.numel() == 0, "%s: a refused call wrote %d bytes of its workspace" % (what, bad.shape[0])
+
+
+def assert_same_bits(runs, what=""):
+    """runs: [(label, [output tensors / arrays])], one entry per run of the same call under another workspace fill, another
+    stale output content or on another stream.  Every run's outputs must equal the first run's bit for bit (NaNs by payload):
+    a result that depends on what a workspace or an output held before the call differs between two of them."""
+    label0, first = runs[0]
+    for label, outs in runs[1:]:
+        assert len(outs) == len(first), what
+        for j, (a, b) in enumerate(zip(first, outs)):
+            a, b = int_bits(a), int_bits(b)
+            assert a.shape == b.shape, (what, label, j)
+            bad = (a.reshape(-1) != b.reshape(-1).to(a.device)).nonzero()
+            assert bad.numel() == 0, "%s: output %d of run %r differs from run %r in %d elements, the first at flat index %d" % (
+                what, j, label, label0, bad.shape[0], int(bad[0, 0]))
