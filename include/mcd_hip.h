@@ -18,6 +18,10 @@
  *   concatenated), K = top_k activating images per neuron.
  *   "image-major"  [N, U]: element (n,u) at base[n*ld + u]   (what torch.cat of hook outputs gives)
  *   "neuron-major" [U, N]: element (n,u) at base[u*ld + n]   (what the fused pipeline keeps in HBM)
+ *
+ * The text tower's entries of this library -- K9M mcd_vit_attention_keylen (K9 with a key count per sequence) and K24
+ * mcd_text_embed_ln (BERT's embedding rows in one launch) -- are declared in mcd_text.h, which includes this header and
+ * follows every convention above.  They are additive: mcd_abi_version() stays 9.
  */
 #ifndef MCD_HIP_H
 #define MCD_HIP_H

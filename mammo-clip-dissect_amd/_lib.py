@@ -59,6 +59,11 @@ SIGNATURES = {
     "mcd_image_minmax_workspace": (_sz, [_i64, _i64, _i64, _i64]),
     "mcd_image_minmax_normalize": (_int, [_p, _i64, _i64, _i64, _i64, _int, _f, _f, _p, _i64, _p, _sz, _p]),
 }
+# the text-tower entries of the same library, declared in include/mcd_text.h (additive to ABI version 9)
+TEXT_SIGNATURES = {
+    "mcd_vit_attention_keylen": (_int, [_p, _i64, _i64, _i64, _p, _p, _p]),
+    "mcd_text_embed_ln": (_int, [_p, _p, _p, _p, _p, _p, _p, _f, _i64, _i64, _i64, _i64, _i64, _p, _p]),
+}
 
 MCD_E_ARG = -1
 MCD_E_RANGE = -2
@@ -85,7 +90,7 @@ def load():
                 "mammo-clip-dissect_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; "
                 "g.build()'` or `make -C mammo-clip-dissect_amd/csrc`. There is no CPU fallback." % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -22,6 +22,7 @@ dissection core they feed is the HIP library.
 """
 import math
 import os
+import unicodedata
 import zlib
 
 import torch
@@ -68,7 +69,11 @@ HIP_RESNET = os.environ.get("MCD_NO_HIP_RESNET", "0") != "1"
 # blocks on GEMMs + K18 + K20 (the 2x2 average pooling that stands in for every stride), the attention pool on K21, two
 # GEMMs, K9C and c_proj.  MCD_NO_HIP_CLIP_RN=1 (or setting this to False) keeps the ATen route of the same modules.
 HIP_CLIP_RN = os.environ.get("MCD_NO_HIP_CLIP_RN", "0") != "1"
-MAX_BATCH = 65535      # the images of one call that the K12-K18 entries accept
+# The BERT text tower's inference route (text_route): the embedding rows on K24, per layer the fused qkv GEMM, K9M (the
+# attention with a key count per sequence: the padded batch's mask), the two residual GEMMs and K10 behind each.
+# MCD_NO_HIP_TEXT=1 (or setting this to False) keeps the ATen route of the same modules, SDPA under the mask included.
+HIP_TEXT = os.environ.get("MCD_NO_HIP_TEXT", "0") != "1"
+MAX_BATCH = 65535     # the images of one call that the K12-K18 entries accept
 
 
 # ---- the gate: when a forward may leave ATen for the HIP kernels ---------------------------------------------------------
@@ -658,6 +663,355 @@ class TextTower(nn.Module):
         return self.encoder(x, attn)
 
 
+# ------------------------------------------------------------------------------------------------------
+# the reference's own text tower: transformers.BertModel (Bio_ClinicalBERT) restated, and its WordPiece tokenizer
+#   model/modules/text_encoder.py:37,48 (BertModel(config), output["last_hidden_state"]); model/clip.py:17, :60-79
+# Module tree and state-dict keys are those of transformers 4.41.1, the reference's pin: a Mammo-CLIP checkpoint's
+# text_encoder.text_encoder.* keys load unchanged.  Post-norm blocks, erf GELU, eps from the configuration (1e-12).
+# ------------------------------------------------------------------------------------------------------
+def prefix_mask_lengths(mask):
+    """The key count of every row of a PREFIX attention mask [B, T] -- ones (non-zeros), then zeros, at least one 1 per
+    row: what padding to the longest sequence produces -- as an int32 [B] tensor on the mask's device, or None for any
+    other mask (a hole, a leading zero, an all-zero row): only a prefix mask is a key count, which is what K9M takes.
+    One device-to-host sync for a mask on the GPU."""
+    if mask.dim() != 2 or mask.shape[1] < 1:
+        return None
+    m = mask != 0
+    lens = m.sum(dim=1)
+    prefix = torch.arange(mask.shape[1], device=mask.device)[None, :] < lens[:, None]
+    if not bool(((m == prefix).all() & (lens >= 1).all()).item()):
+        return None
+    return lens.to(torch.int32)
+
+
+def text_route(tower, ids):
+    """'hip' when a BertTextTower call on the token ids `ids` may leave ATen: HIP_TEXT on, the weights fp32 on the GPU
+    with the ids beside them, no autograd (_hip_eligible), eval mode, hidden = 64 * heads (K9M's head width), at most
+    core.VIT_ATTENTION_MAX_T tokens and no more than the position table has rows, a width K10 / K24 take, and the
+    fused-residual library loaded (every projection is its GEMM).  Otherwise 'aten'.  The mask and the hooks are looked
+    at by the caller: a mask that is not a prefix mask takes SDPA, a layer with a hook inside takes its ATen modules."""
+    w = tower.embeddings.word_embeddings.weight
+    B, T = ids.shape
+    D = w.shape[1]
+    ok = (HIP_TEXT and _hip_eligible(w.is_cuda and ids.is_cuda, w.dtype, torch.is_grad_enabled()) and not tower.training
+          and D == 64 * tower.heads and 1 <= T <= min(core.VIT_ATTENTION_MAX_T, tower.embeddings.position_embeddings.num_embeddings)
+          and D % 4 == 0 and D <= 2048 and 1 <= B <= MAX_BATCH and FUSED_RESIDUAL and core.linear_residual_available())
+    return "hip" if ok else "aten"
+
+
+_BERT_EMB_SKIPPED = ("word_embeddings", "position_embeddings", "token_type_embeddings", "LayerNorm")
+_BERT_LAYER_SKIPPED = ("attention", "intermediate", "output")
+
+
+class _BertEmbeddings(nn.Module):
+    def __init__(self, vocab, hidden, max_pos, n_type, eps):
+        super().__init__()
+        self.word_embeddings = nn.Embedding(vocab, hidden)
+        self.position_embeddings = nn.Embedding(max_pos, hidden)
+        self.token_type_embeddings = nn.Embedding(n_type, hidden)
+        self.LayerNorm = nn.LayerNorm(hidden, eps=eps)
+
+    def forward(self, ids, type_ids=None, hip=False):
+        if hip and not _hooks_on(self, _BERT_EMB_SKIPPED):       # K24: the three gathers, both adds and the LayerNorm
+            n = self.LayerNorm
+            return core.text_embed_ln(ids, type_ids, self.word_embeddings.weight, self.position_embeddings.weight,
+                                      self.token_type_embeddings.weight, n.weight, n.bias, n.eps)
+        if type_ids is None:
+            type_ids = torch.zeros_like(ids)
+        pos = self.position_embeddings(torch.arange(ids.shape[1], device=ids.device))
+        return self.LayerNorm((self.word_embeddings(ids) + self.token_type_embeddings(type_ids)) + pos[None])   # HF's order
+
+
+class _BertSelfAttention(nn.Module):
+    def __init__(self, hidden, heads):
+        super().__init__()
+        self.heads = heads
+        self.query = nn.Linear(hidden, hidden)
+        self.key = nn.Linear(hidden, hidden)
+        self.value = nn.Linear(hidden, hidden)
+
+    def forward(self, x, mask=None):
+        B, T, D = x.shape
+        q, k, v = (m(x).view(B, T, self.heads, D // self.heads).transpose(1, 2) for m in (self.query, self.key, self.value))
+        return F.scaled_dot_product_attention(q, k, v, attn_mask=mask).transpose(1, 2).reshape(B, T, D)
+
+    def fused_qkv(self):
+        """(weight [3 D, D], bias [3 D]) of query | key | value as ONE projection -- the [B, T, 3, heads, 64] operand K9M
+        reads -- concatenated once (_folded: nothing is registered, the cache follows the three modules' parameters)."""
+        return _folded(self, ("query", "key", "value"),
+                       lambda m: (torch.cat([m.query.weight, m.key.weight, m.value.weight]).contiguous(),
+                                  torch.cat([m.query.bias, m.key.bias, m.value.bias]).contiguous()))
+
+
+class _BertAddNorm(nn.Module):
+    """BertSelfOutput / BertOutput: LayerNorm(dense(h) + residual) (dropout is the identity at inference)."""
+
+    def __init__(self, in_dim, hidden, eps):
+        super().__init__()
+        self.dense = nn.Linear(in_dim, hidden)
+        self.LayerNorm = nn.LayerNorm(hidden, eps=eps)
+
+    def forward(self, h, residual):
+        return self.LayerNorm(self.dense(h) + residual)
+
+
+class _BertAttention(nn.Module):
+    def __init__(self, hidden, heads, eps):
+        super().__init__()
+        setattr(self, "self", _BertSelfAttention(hidden, heads))
+        self.output = _BertAddNorm(hidden, hidden, eps)
+
+    def forward(self, x, mask=None):
+        return self.output(getattr(self, "self")(x, mask), x)
+
+
+class _BertIntermediate(nn.Module):
+    def __init__(self, hidden, mlp):
+        super().__init__()
+        self.dense = nn.Linear(hidden, mlp)
+
+    def forward(self, x):
+        return F.gelu(self.dense(x))
+
+
+class _BertLayer(nn.Module):
+    """BertLayer, post-norm: x1 = LN(x + proj(attention(x))), out = LN(x1 + fc2(gelu(fc1(x1))))."""
+
+    def __init__(self, hidden, heads, mlp, eps):
+        super().__init__()
+        self.attention = _BertAttention(hidden, heads, eps)
+        self.intermediate = _BertIntermediate(hidden, mlp)
+        self.output = _BertAddNorm(mlp, hidden, eps)
+
+    def forward(self, x, mask=None, lens=None, hip=False):
+        """mask: None or the bool [B, 1, 1, T] key mask for SDPA; hip (the tower has checked text_route and the mask):
+        the HIP route with lens (int32 [B] key counts, None = all T) -- unless a hook sits inside this layer."""
+        if hip and not _hooks_on(self, _BERT_LAYER_SKIPPED):
+            return self._forward_hip(x, lens)
+        x1 = self.attention(x, mask)
+        return self.output(self.intermediate(x1), x1)
+
+    def _forward_hip(self, x, lens):
+        s, so, o = getattr(self.attention, "self"), self.attention.output, self.output
+        wqkv, bqkv = s.fused_qkv()
+        a = core.vit_attention_keylen(core.linear_residual(None, x, wqkv, bqkv), s.heads, lens)            # K9M
+        x1 = core.layer_norm(core.linear_residual(x, a, so.dense.weight, so.dense.bias), so.LayerNorm.weight,
+                             so.LayerNorm.bias, so.LayerNorm.eps)                                          # K10
+        h = F.gelu(core.linear_residual(None, x1, self.intermediate.dense.weight, self.intermediate.dense.bias))
+        return core.layer_norm(core.linear_residual(x1, h, o.dense.weight, o.dense.bias), o.LayerNorm.weight,
+                               o.LayerNorm.bias, o.LayerNorm.eps)
+
+
+class _BertEncoder(nn.Module):
+    def __init__(self, depth, hidden, heads, mlp, eps):
+        super().__init__()
+        self.layer = nn.ModuleList([_BertLayer(hidden, heads, mlp, eps) for _ in range(depth)])
+
+    def forward(self, x, mask=None, lens=None, hip=False):
+        for layer in self.layer:
+            x = layer(x, mask, lens, hip)
+        return x
+
+
+class BertTextTower(nn.Module):
+    """transformers.BertModel without its pooler (nothing reads pooler_output): forward(tokens) -> last_hidden_state
+    [B, T, hidden] for the tokenizer's dict (input_ids, attention_mask, token_type_ids; the last two optional).
+    heads = hidden / 64 (BERT's head width at every size the reference uses, and K9M's)."""
+
+    def __init__(self, vocab=28996, hidden=768, depth=12, mlp=3072, max_pos=512, n_type=2, eps=1e-12, heads=None):
+        super().__init__()
+        self.out_dim = hidden
+        self.heads = hidden // 64 if heads is None else heads
+        if hidden % self.heads:
+            raise ValueError("BertTextTower: hidden %d is not a multiple of %d heads" % (hidden, self.heads))
+        self.embeddings = _BertEmbeddings(vocab, hidden, max_pos, n_type, eps)
+        self.encoder = _BertEncoder(depth, hidden, self.heads, mlp, eps)
+
+    def forward(self, tokens):
+        ids, mask, type_ids = tokens["input_ids"], tokens.get("attention_mask"), tokens.get("token_type_ids")
+        hip = text_route(self, ids) == "hip"
+        lens = None
+        if hip and mask is not None:
+            lens = prefix_mask_lengths(mask)          # the one sync of the text path
+            layers_hip = lens is not None             # any other mask: SDPA
+        else:
+            layers_hip = hip
+        x = self.embeddings(ids, type_ids, hip)
+        attn = None if mask is None else mask[:, None, None, :].bool()
+        return self.encoder(x, attn, lens, layers_hip)
+
+
+def bert_config_from_state_dict(sd, prefix="text_encoder.text_encoder."):
+    """BertTextTower's constructor arguments read from the shapes of a checkpoint's tensors under `prefix`."""
+    def shape(name):
+        key = prefix + name
+        if key not in sd:
+            raise RuntimeError("the checkpoint has text keys under %r but lacks %r" % (prefix, key))
+        return tuple(sd[key].shape)
+    vocab, hidden = shape("embeddings.word_embeddings.weight")
+    layer = prefix + "encoder.layer."
+    depth = 1 + max([int(k[len(layer):].split(".")[0]) for k in sd if k.startswith(layer)], default=-1)
+    if depth < 1:
+        raise RuntimeError("the checkpoint has no %s* keys" % layer)
+    return dict(vocab=vocab, hidden=hidden, depth=depth, mlp=shape("encoder.layer.0.intermediate.dense.weight")[0],
+                max_pos=shape("embeddings.position_embeddings.weight")[0],
+                n_type=shape("embeddings.token_type_embeddings.weight")[0])
+
+
+class HFTextEncoder(nn.Module):
+    """The reference's HuggingfaceTextEncoder (model/modules/text_encoder.py:5-49): holds the tower as .text_encoder, so
+    that inside BreastClip its keys are text_encoder.text_encoder.*, and returns last_hidden_state."""
+
+    def __init__(self, **config):
+        super().__init__()
+        self.text_encoder = BertTextTower(**config)
+        self.out_dim = self.text_encoder.out_dim
+
+    def forward(self, tokens):
+        return self.text_encoder(tokens)
+
+
+def _is_cjk(cp):
+    return (0x4E00 <= cp <= 0x9FFF or 0x3400 <= cp <= 0x4DBF or 0x20000 <= cp <= 0x2A6DF or 0x2A700 <= cp <= 0x2B73F
+            or 0x2B740 <= cp <= 0x2B81F or 0x2B820 <= cp <= 0x2CEAF or 0xF900 <= cp <= 0xFAFF or 0x2F800 <= cp <= 0x2FA1F)
+
+
+def _is_punct(ch):
+    cp = ord(ch)
+    if 33 <= cp <= 47 or 58 <= cp <= 64 or 91 <= cp <= 96 or 123 <= cp <= 126:     # all of ASCII's, `$` and `^` included
+        return True
+    return unicodedata.category(ch).startswith("P")
+
+
+class WordPieceTokenizer:
+    """BertTokenizerFast restated in pure Python (no transformers import): what the reference's tokenize() runs
+    (model/clip.py:81-101 on AutoTokenizer('emilyalsentzer/Bio_ClinicalBERT')), from a local vocab.txt.
+
+      1. clean the text: drop NUL, U+FFFD and control characters, every whitespace character becomes a space;
+      2. spaces around CJK characters;
+      3. with do_lower_case: NFD, drop the combining marks (Mn), lower-case;
+      4. split on whitespace, then every punctuation character is a word of its own;
+      5. greedy longest-match WordPiece, continuation pieces prefixed ##; a word with a piece the vocabulary lacks, or
+         longer than 100 characters, is [UNK];
+      6. [CLS] ids [SEP], truncated to max_length so that [SEP] survives, padded with [PAD] to the longest sequence.
+    Returns {input_ids, token_type_ids, attention_mask}, int64 [B, L]: the dict the reference's tokenize() returns.
+
+    do_lower_case=True is BertTokenizerFast's own default, and by our reading of its hub repository -- which ships no
+    tokenizer configuration -- it is what the reference gets for Bio_ClinicalBERT, a cased vocabulary notwithstanding.
+    That reading cannot be checked offline.  Not restated: special-token strings such as '[SEP]' inside the text (the
+    fast tokenizer maps them to the special ids; here they are split like any other text)."""
+
+    def __init__(self, vocab_file, do_lower_case=True, max_chars_per_word=100):
+        with open(vocab_file, encoding="utf-8") as f:
+            tokens = [line.rstrip("\n") for line in f]
+        while tokens and tokens[-1] == "":
+            tokens.pop()
+        self.vocab = {}
+        for i, t in enumerate(tokens):
+            self.vocab[t] = i                     # (a repeated token keeps its last id, as a dict built in file order does)
+        self.vocab_size = len(tokens)
+        self.do_lower_case = do_lower_case
+        self.max_chars = max_chars_per_word
+        missing = [t for t in ("[PAD]", "[UNK]", "[CLS]", "[SEP]") if t not in self.vocab]
+        if missing:
+            raise ValueError("%s lacks the special tokens %s" % (vocab_file, missing))
+        self.pad_id, self.unk_id, self.cls_id, self.sep_id = (self.vocab[t] for t in ("[PAD]", "[UNK]", "[CLS]", "[SEP]"))
+
+    def words(self, text):
+        out = []
+        for ch in text:
+            cp, cat = ord(ch), unicodedata.category(ch)
+            if ch in " \t\n\r":
+                out.append(" ")
+            elif cp == 0 or cp == 0xFFFD or cat.startswith("C"):
+                continue
+            elif cat == "Zs" or ch.isspace():
+                out.append(" ")
+            elif _is_cjk(cp):
+                out += [" ", ch, " "]
+            else:
+                out.append(ch)
+        text = "".join(out)
+        if self.do_lower_case:
+            text = "".join(c for c in unicodedata.normalize("NFD", text) if unicodedata.category(c) != "Mn").lower()
+        words = []
+        for w in text.split():
+            cur = ""
+            for ch in w:
+                if _is_punct(ch):
+                    if cur:
+                        words.append(cur)
+                    words.append(ch)
+                    cur = ""
+                else:
+                    cur += ch
+            if cur:
+                words.append(cur)
+        return words
+
+    def wordpiece(self, word):
+        if len(word) > self.max_chars:
+            return [self.unk_id]
+        ids, start = [], 0
+        while start < len(word):
+            end = len(word)
+            while end > start:
+                piece = ("##" if start else "") + word[start:end]
+                if piece in self.vocab:
+                    break
+                end -= 1
+            if end == start:
+                return [self.unk_id]
+            ids.append(self.vocab[piece])
+            start = end
+        return ids
+
+    def encode(self, text, max_length=None, truncation=True):
+        ids = [i for w in self.words(text) for i in self.wordpiece(w)]
+        if truncation and max_length is not None:
+            ids = ids[:max(max_length - 2, 0)]
+        return [self.cls_id] + ids + [self.sep_id]
+
+    def __call__(self, texts, max_length=256, padding=True, truncation=True, return_tensors="pt"):
+        if isinstance(texts, str):
+            texts = [texts]
+        rows = [self.encode(t, max_length, truncation) for t in texts]
+        L = max(len(r) for r in rows) if padding else None
+        if L is None and len(set(len(r) for r in rows)) > 1:
+            raise ValueError("WordPieceTokenizer: sequences of different lengths need padding=True")
+        L = len(rows[0]) if L is None else L
+        input_ids = torch.full((len(rows), L), self.pad_id, dtype=torch.long)
+        mask = torch.zeros(len(rows), L, dtype=torch.long)
+        for i, r in enumerate(rows):
+            input_ids[i, :len(r)] = torch.tensor(r, dtype=torch.long)
+            mask[i, :len(r)] = 1
+        return {"input_ids": input_ids, "token_type_ids": torch.zeros_like(input_ids), "attention_mask": mask}
+
+
+TOKENIZER_VOCABS = {}
+
+
+def register_tokenizer(name, vocab_path, do_lower_case=True):
+    """Where a text tower's vocabulary lives (like register_dataset for probe sets): name 'bert', a LOCAL vocab.txt.  The
+    environment variable MCD_BERT_VOCAB=/path/vocab.txt does the same for a process that registers nothing."""
+    if name != "bert":
+        raise ValueError("register_tokenizer: %r is not a tokenizer of this package ('bert')" % (name,))
+    TOKENIZER_VOCABS[name] = (vocab_path, bool(do_lower_case))
+
+
+def bert_tokenizer():
+    """The WordPieceTokenizer of the registered vocabulary; without one an error -- never the hashing stand-in, whose ids
+    would address arbitrary rows of a real embedding table."""
+    entry = TOKENIZER_VOCABS.get("bert")
+    if entry is None and os.environ.get("MCD_BERT_VOCAB"):
+        entry = (os.environ["MCD_BERT_VOCAB"], True)
+    if entry is None:
+        raise RuntimeError("the BERT text tower needs its WordPiece vocabulary: call data_utils.register_tokenizer('bert', "
+                           "'/path/vocab.txt') or set MCD_BERT_VOCAB=/path/vocab.txt (the vocab.txt of the checkpoint's "
+                           "text model, e.g. Bio_ClinicalBERT's); there is no fallback to the hashing tokenizer")
+    return WordPieceTokenizer(entry[0], do_lower_case=entry[1])
+
+
 class LinearProjectionHead(nn.Module):
     def __init__(self, in_dim, proj_dim):
         super().__init__()
@@ -673,21 +1027,28 @@ class LinearProjectionHead(nn.Module):
 class BreastClip(nn.Module):
     """encode_image / encode_text / tokenize / image_projection / text_projection / projection, as the
     reference's utils.py:315-414 uses them.  image tower: 'cnn' = EfficientNet-B5 (the shipped Mammo-CLIP),
-    'vit' = ViT-B/16 (reference model/modules/image_encoder.py:14-52, CLS token model/clip.py:49-52)."""
+    'vit' = ViT-B/16 (reference model/modules/image_encoder.py:14-52, CLS token model/clip.py:49-52).
+    text tower: 'stand-in' (the default) = TextTower + HashTokenizer; 'bert' = the reference's own, HFTextEncoder around
+    BertTextTower (bert_config: its constructor arguments) with the WordPiece tokenizer of the registered vocabulary.
+    text_pooling: 'eos' (the default), 'bos' or 'mean' (model/clip.py:66-77)."""
 
-    def __init__(self, image_tower="cnn", image_size=224, text_depth=12):
+    def __init__(self, image_tower="cnn", image_size=224, text_depth=12, text_tower="stand-in", bert_config=None,
+                 text_pooling="eos"):
         super().__init__()
         self.model_type = image_tower
         if image_tower == "cnn":
             self.image_encoder = EfficientNetB5Tower()
         else:
             self.image_encoder = ViTTower(image_size=image_size)
-        self.text_encoder = TextTower(depth=text_depth)
-        self.text_pooling = "eos"
+        if text_tower not in ("stand-in", "bert"):
+            raise ValueError("text_tower must be 'stand-in' or 'bert', got %r" % (text_tower,))
+        self.text_tower = text_tower
+        self.text_encoder = TextTower(depth=text_depth) if text_tower == "stand-in" else HFTextEncoder(**(bert_config or {}))
+        self.text_pooling = text_pooling
         self.projection = True
         self.image_projection = LinearProjectionHead(self.image_encoder.out_dim, PROJ_DIM)
         self.text_projection = LinearProjectionHead(self.text_encoder.out_dim, PROJ_DIM)
-        self.tokenizer = HashTokenizer()
+        self.tokenizer = HashTokenizer() if text_tower == "stand-in" else None    # 'bert': resolved at tokenize()
 
     def encode_image(self, image):
         if self.model_type == "cnn":
@@ -698,13 +1059,28 @@ class BreastClip(nn.Module):
         if not isinstance(text_tokens, dict):
             raise ValueError("Text tokens must be a dictionary")
         f = self.text_encoder(text_tokens)
-        eos = text_tokens["attention_mask"].sum(dim=-1) - 1  # 'eos' pooling, model/clip.py:66-69
-        return f[torch.arange(f.shape[0], device=f.device), eos]
+        if self.text_pooling == "eos":
+            eos = text_tokens["attention_mask"].sum(dim=-1) - 1  # 'eos' pooling, model/clip.py:66-69
+            return f[torch.arange(f.shape[0], device=f.device), eos]
+        if self.text_pooling == "bos":                           # model/clip.py:70-71
+            return f[:, 0]
+        if self.text_pooling == "mean":                          # model/clip.py:72-75
+            m = text_tokens["attention_mask"].unsqueeze(-1).expand(f.size()).float()
+            return torch.sum(f * m, dim=1) / torch.clamp(m.sum(dim=1), min=1e-9)
+        raise NotImplementedError("Not supported pooling method : %s" % (self.text_pooling,))
 
     def tokenize(self, texts, max_length=256, padding=True, truncation=True):
         if isinstance(texts, str):
             texts = [texts]
-        return self.tokenizer(texts, max_length=max_length, padding=padding, truncation=truncation)
+        if self.tokenizer is None:      # the BERT tower: its own vocabulary or an error, never the hashing stand-in
+            self.tokenizer = bert_tokenizer()
+        tok = self.tokenizer(texts, max_length=max_length, padding=padding, truncation=truncation)
+        if self.text_tower == "bert":   # the ids are still on the host: refuse what the embedding table does not have
+            rows = self.text_encoder.text_encoder.embeddings.word_embeddings.num_embeddings
+            if tok["input_ids"].numel() and int(tok["input_ids"].max()) >= rows:
+                raise ValueError("the vocabulary gives token id %d, the checkpoint's embedding table has %d rows: this is "
+                                 "not the vocab.txt of the checkpoint's text model" % (int(tok["input_ids"].max()), rows))
+        return tok
 
 
 class BreastClipClassifier(nn.Module):
@@ -1376,17 +1752,39 @@ CLIP_RESNETS = {"clip_rn50": ((3, 4, 6, 3), 1024), "clip_rn101": ((3, 4, 23, 3),
 # ------------------------------------------------------------------------------------------------------
 # factories
 # ------------------------------------------------------------------------------------------------------
-def _load_local(model, ckpt):
-    """ckpt: None, a state dict, {'model': state dict} (reference utils.py:451-455), or a LOCAL path
-    (loaded with weights_only=True: nothing from the file is executed)."""
-    if ckpt is None:
-        return model
+BERT_PREFIX = "text_encoder.text_encoder."
+_BERT_IGNORED = (BERT_PREFIX + "pooler.", BERT_PREFIX + "embeddings.position_ids")
+
+
+def _state_dict_of(ckpt):
+    """The state dict in ckpt: a state dict, {'model': state dict} (reference utils.py:451-455), or a LOCAL path to
+    either (loaded with weights_only=True: nothing from the file is executed)."""
     if isinstance(ckpt, str):
         ckpt = torch.load(ckpt, map_location="cpu", weights_only=True)
-    sd = ckpt["model"] if isinstance(ckpt, dict) and "model" in ckpt else ckpt
+    return ckpt["model"] if isinstance(ckpt, dict) and "model" in ckpt else ckpt
+
+
+def _load_local(model, ckpt, text_strict=False):
+    """ckpt: None, a state dict, {'model': state dict} (reference utils.py:451-455), or a LOCAL path
+    (loaded with weights_only=True: nothing from the file is executed).
+    text_strict (a BreastClip with the BERT tower): the text side loads strictly -- pooler.* and
+    embeddings.position_ids are ignored by name (BertTextTower has no pooler; 4.41.1 no longer stores the buffer, older
+    checkpoints do), any other missing or unexpected key under text_encoder. is an error instead of a tower of random
+    weights."""
+    if ckpt is None:
+        return model
+    sd = _state_dict_of(ckpt)
     if isinstance(model, _HFClassifier):             # transformers' key names -> the mirror's
         sd = model.convert_state_dict(sd)
-    model.load_state_dict(sd, strict=False)
+    if text_strict:
+        sd = {k: v for k, v in sd.items() if not k.startswith(_BERT_IGNORED)}
+    result = model.load_state_dict(sd, strict=False)
+    if text_strict:
+        missing = [k for k in result.missing_keys if k.startswith("text_encoder.")]
+        unexpected = [k for k in result.unexpected_keys if k.startswith("text_encoder.")]
+        if missing or unexpected:
+            raise RuntimeError("the checkpoint's text tower does not match BertTextTower: %d missing key(s) %s, %d unexpected "
+                               "key(s) %s" % (len(missing), missing[:4], len(unexpected), unexpected[:4]))
     return model
 
 
@@ -1411,13 +1809,28 @@ def _load_places(model, ckpt):
     return model
 
 
-def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, finetuned_ckpt=None, seed=0, image_size=224):
+def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, finetuned_ckpt=None, seed=0, image_size=224,
+                     text_tower=None):
     """Returns (target model in eval mode, preprocess) -- reference data_utils.py:38-93.  Weights are
     random-init under `seed` unless a local checkpoint is given; nothing is downloaded.
     image_size: input resolution of the ViT towers, an int (square) or (H, W) (position embeddings are sized for it;
     the reference's HF ViT is built for its checkpoint's resolution the same way); also accepted as a suffix,
     'breastclip_vit_1024' or 'breastclip_vit_1520x912' (H x W, Mammo-CLIP's own input).  The attention is HIP at
-    every resolution: K9 up to 256 tokens, K9L beyond (attention_route)."""
+    every resolution: K9 up to 256 tokens, K9L beyond (attention_route).
+    text_tower (breastclip, breastclip_vit): 'stand-in', 'bert', or None = 'bert' exactly when the checkpoint's state dict
+    has keys starting text_encoder.text_encoder. (a Mammo-CLIP checkpoint), else the stand-in.  The BERT tower's hidden
+    size, depth, intermediate size, vocabulary and position rows are read from the checkpoint's shapes."""
+    if text_tower not in (None, "stand-in", "bert"):
+        raise ValueError("text_tower must be None, 'stand-in' or 'bert', got %r" % (text_tower,))
+    text_kw = {}
+    if target_name.startswith("breastclip") and target_name != "breastclip_classifier" and (ckpt is not None or text_tower):
+        if ckpt is not None:
+            ckpt = _state_dict_of(ckpt)
+        has_bert = ckpt is not None and any(k.startswith(BERT_PREFIX) for k in ckpt)
+        if text_tower is None:
+            text_tower = "bert" if has_bert else "stand-in"
+        if text_tower == "bert":
+            text_kw = dict(text_tower="bert", bert_config=bert_config_from_state_dict(ckpt) if has_bert else None)
     if target_name.startswith("breastclip_vit_"):
         hw = _parse_hw(target_name[len("breastclip_vit_"):])
         if hw is not None:
@@ -1426,9 +1839,9 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
         if target_name == "breastclip":
-            model = BreastClip("cnn")
+            model = BreastClip("cnn", **text_kw)
         elif target_name == "breastclip_vit":
-            model = BreastClip("vit", image_size=image_size)
+            model = BreastClip("vit", image_size=image_size, **text_kw)
         elif target_name == "breastclip_classifier":
             if n_class is None:
                 raise ValueError("Arguments `args`, `ckpt`, and `n_class` must be provided for BreastClipClassifier.")
@@ -1458,7 +1871,7 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
     if target_name == "resnet18_places":
         _load_places(model, ckpt)
     else:
-        _load_local(model, ckpt)
+        _load_local(model, ckpt, text_strict=bool(text_kw))
     _load_local(model, finetuned_ckpt)
     return model.to(device).eval(), None
 

@@ -326,13 +326,14 @@ def _probe_data(d_probe, device, preprocess=None, clip_preprocess=None):
     return data_utils.get_data(d_probe, preprocess, None if on_host else device, lo, hi, clip_preprocess=clip_preprocess)
 
 
-def build_mammo_models(target_name, device, breast_clip_ckh=None, fine_tuned_ckh=None, args=None):
+def build_mammo_models(target_name, device, breast_clip_ckh=None, fine_tuned_ckh=None, args=None, text_tower=None):
     """The model side of save_activations (reference :443-483): (dissector, target).  Separate so that a caller that
-    dissects repeatedly (bench.py) builds the models once."""
+    dissects repeatedly (bench.py) builds the models once.  text_tower: the dissector's text tower, passed to
+    data_utils.get_target_model (None: the BERT tower exactly when the checkpoint carries one)."""
     finetuned = fine_tuned_ckh
     tower = "vit" if target_name.startswith("breastclip_vit") else "cnn"
     clip_model, _ = data_utils.get_target_model(target_name if tower == "vit" else "breastclip", device,
-                                                ckpt=breast_clip_ckh)
+                                                ckpt=breast_clip_ckh, text_tower=text_tower)
     if (target_name == "breastclip" or tower == "vit") and finetuned is None:
         target_model = clip_model          # same weights: encode the probe set once
     elif target_name == "breastclip_classifier":

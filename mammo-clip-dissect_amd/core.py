@@ -444,6 +444,31 @@ def vit_attention_long(qkv, heads, out=None):
     return _attention("mcd_vit_attention_long", qkv, heads, out)
 
 
+# ---- K9M -----------------------------------------------------------------------------------------
+@_on_device
+def vit_attention_keylen(qkv, heads, lens, out=None):
+    """vit_attention with a key count per sequence (K9M, include/mcd_text.h): qkv [B, T, 3*heads*64], T <= 256; lens a
+    contiguous int32 [B] tensor on qkv's device, or None (every length is T: vit_attention's bits).  Sequence b attends to
+    keys 0 .. L-1, L = clamp(lens[b], 1, T) -- the kernel clamps, the values are not read back.  Every query row is
+    computed, padded ones included; no K or V row >= L is read."""
+    _need_gpu(qkv, lens)
+    if qkv.dtype != torch.float32 or qkv.dim() != 3 or not qkv.is_contiguous():
+        raise TypeError("qkv must be a contiguous float32 [B, T, 3*heads*64] tensor")
+    B, T, W = qkv.shape
+    if W != 3 * heads * 64:
+        raise ValueError("qkv last dimension %d is not 3 * %d heads * 64" % (W, heads))
+    if lens is not None and (lens.dtype != torch.int32 or tuple(lens.shape) != (B,) or not lens.is_contiguous()
+                             or lens.device != qkv.device):
+        raise TypeError("lens must be a contiguous int32 [B] tensor on qkv's device (or None)")
+    if out is None:
+        out = torch.empty((B, T, heads * 64), dtype=torch.float32, device=qkv.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, T, heads * 64) or not out.is_contiguous():
+        raise TypeError("out must be a contiguous float32 [B, T, heads*64] tensor")
+    check(_lib.load().mcd_vit_attention_keylen(qkv.data_ptr(), B, T, heads, None if lens is None else lens.data_ptr(),
+                                               out.data_ptr(), _stream()))
+    return out
+
+
 # ---- K9C -----------------------------------------------------------------------------------------
 VIT_ATTENTION_CLS_MAX_T = 32768
 
@@ -491,6 +516,42 @@ def layer_norm(x, weight, bias, eps):
     check(L.mcd_layer_norm(x.data_ptr(), x.numel() // D, D, weight.data_ptr(), bias.data_ptr(), float(eps), y.data_ptr(),
                            _stream()))
     return y
+
+
+# ---- K24 -----------------------------------------------------------------------------------------
+@_on_device
+def text_embed_ln(ids, type_ids, word, pos, type_table, weight, bias, eps, out=None):
+    """BERT's embedding rows in one launch (K24, include/mcd_text.h): ids [B, T] int64 (type_ids the same shape, or None =
+    row 0 of type_table), word [vocab, D], pos [>= T, D], type_table [n_type, D], weight / bias [D] ->
+    LayerNorm((word[ids] + type_table[type_ids]) + pos[:T]) as [B, T, D]: the bits of layer_norm on ATen's sum.
+    The ids are range-checked HERE when they are still host tensors (the tokenizer's output: no sync); device ids are
+    passed on as they are and the kernel clamps them into the tables."""
+    _need_gpu(word, pos, type_table, weight, bias, out)
+    if ids.dim() != 2 or ids.dtype != torch.int64 or (type_ids is not None and (type_ids.dtype != torch.int64
+                                                                               or type_ids.shape != ids.shape)):
+        raise TypeError("text_embed_ln: ids (and type_ids) must be int64 [B, T]")
+    B, T = ids.shape
+    tables = (word, pos, type_table)
+    if any(t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() for t in tables):
+        raise TypeError("text_embed_ln: contiguous float32 [rows, D] tables")
+    D = word.shape[1]
+    if pos.shape[1] != D or type_table.shape[1] != D or weight.shape != (D,) or bias.shape != (D,):
+        raise ValueError("text_embed_ln: the tables, weight and bias must share the width D=%d" % D)
+    if T < 1 or T > pos.shape[0]:
+        raise ValueError("text_embed_ln: T=%d tokens, the position table has %d rows" % (T, pos.shape[0]))
+    for name, t, n in (("ids", ids, word.shape[0]), ("type_ids", type_ids, type_table.shape[0])):
+        if t is not None and not t.is_cuda and t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
+            raise ValueError("text_embed_ln: %s outside [0, %d)" % (name, n))
+    ids = ids.to(word.device).contiguous()
+    type_ids = None if type_ids is None else type_ids.to(word.device).contiguous()
+    if out is None:
+        out = torch.empty((B, T, D), dtype=torch.float32, device=word.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, T, D) or not out.is_contiguous():
+        raise TypeError("out must be a contiguous float32 [B, T, D] tensor")
+    check(_lib.load().mcd_text_embed_ln(ids.data_ptr(), None if type_ids is None else type_ids.data_ptr(), word.data_ptr(),
+                                        pos.data_ptr(), type_table.data_ptr(), weight.data_ptr(), bias.data_ptr(), float(eps),
+                                        B * T, T, D, word.shape[0], type_table.shape[0], out.data_ptr(), _stream()))
+    return out
 
 
 # ---- K11 -----------------------------------------------------------------------------------------

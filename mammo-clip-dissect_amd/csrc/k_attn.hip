@@ -34,6 +34,14 @@
 // of a head, each streaming all of the head's key tiles.  At T = 4 097 attention is half of the tower's flops; PyTorch's
 // fp32 SDPA (its memory-efficient kernel) ran the same shapes at 0.56-0.60 of the fp32 MFMA peak, K9L at 0.68-0.71.
 //
+// K9M (mcd_vit_attention_keylen): K9 with a key count per sequence, for the BERT text tower's padded batches
+//     model/modules/text_encoder.py:48  BertModel(**tokens) under a key-padding attention_mask (ones, then zeros)
+// Sequence b attends to keys 0 .. L-1, L = clamp(lens[b], 1, T) -- lens lives on the device, the host cannot see it, so
+// the clamp is the kernel's.  The same workgroup body with L as the key count: ceil(L / 32) tiles (a short sequence in a
+// long batch skips its padded tiles), the loader clamps to row L-1, so no K or V row >= L is read and a NaN there reaches
+// nothing.  Rows 0 .. L-1 are K9's bits on the sequence truncated to L tokens; the padded query rows are computed too
+// (BertModel and SDPA do the same).  A NaN in q reaches that output row of that head only; +-Inf inputs: unspecified.
+//
 // K9C (mcd_vit_attention_cls): attention for ONE query row per image -- the class token of the last encoder block, the
 // only row of that block anything downstream reads (concept_vit/data_utils.py, cls_tail_route).  2 * 64 flops per 512
 // bytes of K and V: a streaming kernel, bound by reading every K and V head row once (2 * B * T * H * 256 bytes), not
@@ -44,6 +52,7 @@
 // once, through 4 KB of LDS.  q, k and v come with their own row / image strides: the [B, T, 2, H, 64] output of a
 // K|V-only projection and a plain [B, T, 3, H, 64] qkv are both addressed in place.
 #include "mcd_common.h"
+#include "../../include/mcd_text.h"
 
 namespace {
 
@@ -59,10 +68,15 @@ constexpr int AT_NSTAGE = 4;       // ring of tiles: two pairs
 // The workgroup body of both forms: queries q0 .. q0 + 32 * ncw - 1 of head h of image b, one compute wave per 32 of
 // them (waves 0 .. ncw-1), wave ncw the loader; all ntile key tiles of (b, h) go through the LDS ring.  Which block a
 // query sits in does not enter its arithmetic: the long form gives K9's bits wherever both run.
+// KEYLEN (K9M): the keys are rows 0 .. L-1 of the sequence (1 <= L <= T, uniform over the workgroup) -- L takes T's place
+// in the tile count, in the loader's clamp and in the mask of the last tile, so no K or V row >= L is read; T keeps the
+// row strides and the query count.  Without KEYLEN the key count IS T (L is not looked at): K9 and K9L as they were.
+template <bool KEYLEN>
 __device__ __forceinline__ void attn_block(const float* __restrict__ qkv, int T, int H, int64_t b, int h, int q0, int ncw,
-                                           float* __restrict__ out) {
+                                           int L, float* __restrict__ out) {
     __shared__ __attribute__((aligned(1024))) char at_lds[AT_NSTAGE * AT_STAGE];   // [stage][K | V][32 rows x 256 B]
-    const int ntile = (T + 31) >> 5;
+    const int TK = KEYLEN ? L : T;     // keys
+    const int ntile = (TK + 31) >> 5;
     const int64_t row_stride = (int64_t)3 * H * AT_D;                 // floats between two tokens of qkv
     const float* base = qkv + b * T * row_stride + (int64_t)h * AT_D;  // q of token 0; k at +H*64, v at +2*H*64
     const int lane = threadIdx.x & 63;
@@ -86,7 +100,7 @@ __device__ __forceinline__ void attn_block(const float* __restrict__ qkv, int T,
                 const int r = 4 * p + (lane >> 4);
                 const int c = (lane & 15) ^ (r & 15);
                 int key = kt * 32 + r;
-                if (key >= T) key = T - 1;
+                if (key >= TK) key = TK - 1;
                 const unsigned off = (unsigned)(((int64_t)key * row_stride + (int64_t)(h + H) * AT_D + c * 4) * 4);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(dst + p * 1024), 16, off, 0, 0, 0);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(dst + AT_HALF + p * 1024), 16, off,
@@ -159,7 +173,7 @@ __device__ __forceinline__ void attn_block(const float* __restrict__ qkv, int T,
             c = __builtin_amdgcn_mfma_f32_32x32x2f32(ka.z, Qr[4 * j + 2], c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_32x32x2f32(ka.w, Qr[4 * j + 3], c, 0, 0, 0);
         }
-        const int nk = T - kt * 32;   // valid keys in this tile (>= 1)
+        const int nk = TK - kt * 32;   // valid keys in this tile (>= 1)
         if (nk < 32) {
 #pragma unroll
             for (int r = 0; r < 16; ++r)
@@ -225,7 +239,21 @@ __global__ __launch_bounds__(576, 4) void vit_attention_kernel(const float* __re
     const int ntile = (T + 31) >> 5;
     const int h = blockIdx.x;
     const int64_t b = blockIdx.y;
-    attn_block(qkv, T, H, b, h, 0, ntile, out);
+    attn_block<false>(qkv, T, H, b, h, 0, ntile, T, out);
+}
+
+// K9M: K9's grid and waves (one compute wave per 32 QUERIES, so ceil(T / 32) of them + the loader) with a key count per
+// sequence: L = clamp(lens[b], 1, T), T without lens.  Every query row t < T is computed and stored, rows >= L included
+// (they attend to the L valid keys, as SDPA's rows under a key-padding mask do).
+__global__ __launch_bounds__(576, 4) void vit_attention_keylen_kernel(const float* __restrict__ qkv, int T, int H,
+                                                                       const int32_t* __restrict__ lens,
+                                                                       float* __restrict__ out) {
+    const int ncw = (T + 31) >> 5;
+    const int h = blockIdx.x;
+    const int64_t b = blockIdx.y;
+    int L = T;
+    if (lens) L = min(max(lens[b], 1), T);
+    attn_block<true>(qkv, T, H, b, h, 0, ncw, __builtin_amdgcn_readfirstlane(L), out);
 }
 
 // K9L, the long form: one workgroup per (image, head, block of 32 * ncw queries), ncw = min(8, ceil(T / 32)).  Every
@@ -243,7 +271,7 @@ __global__ __launch_bounds__(576, 4) void vit_attention_long_kernel(const float*
     if (pair >= npairs) return;
     const int grp = pair / nqb;                    // b * H + h
     const int ncw = min(8, (T + 31) >> 5);
-    attn_block(qkv, T, H, grp / H, grp % H, (pair - grp * nqb) * 32 * ncw, ncw, out);
+    attn_block<false>(qkv, T, H, grp / H, grp % H, (pair - grp * nqb) * 32 * ncw, ncw, T, out);
 }
 
 // ---- K9C ----------------------------------------------------------------------------------------------------------------
@@ -371,6 +399,24 @@ extern "C" int mcd_vit_attention(const float* qkv, int64_t B, int64_t T, int64_t
     hipLaunchKernelGGL(vit_attention_kernel, dim3((unsigned)H, (unsigned)B), dim3(64 * nwaves), 0, (hipStream_t)stream, qkv,
                        (int)T, (int)H, out);
     MCD_LAUNCH_CHECK("vit_attention_kernel");
+    return MCD_OK;
+}
+
+extern "C" int mcd_vit_attention_keylen(const float* qkv, int64_t B, int64_t T, int64_t H, const int32_t* lens, float* out,
+                                        mcd_stream_t stream) {
+    MCD_REQUIRE(qkv && out, MCD_E_ARG, "mcd_vit_attention_keylen: NULL pointer");
+    MCD_REQUIRE(B >= 0 && T >= 1 && H >= 1, MCD_E_ARG, "mcd_vit_attention_keylen: bad shape B=%lld T=%lld H=%lld",
+                (long long)B, (long long)T, (long long)H);
+    MCD_REQUIRE(T <= AT_MAX_T, MCD_E_UNSUPPORTED,
+                "mcd_vit_attention_keylen: T=%lld tokens, at most %d (one wave per 32 queries, 8 waves)", (long long)T, AT_MAX_T);
+    MCD_REQUIRE(B <= 65535 && H <= 65535, MCD_E_UNSUPPORTED, "mcd_vit_attention_keylen: B and H must be <= 65535");
+    MCD_REQUIRE(((uintptr_t)qkv) % 16 == 0 && ((uintptr_t)out) % 16 == 0 && ((uintptr_t)lens) % 4 == 0, MCD_E_ARG,
+                "mcd_vit_attention_keylen: qkv and out must be 16-byte aligned, lens 4-byte aligned");
+    if (B == 0) return MCD_OK;
+    const int nwaves = (int)((T + 31) / 32) + 1;   // one per 32 queries + the loader
+    hipLaunchKernelGGL(vit_attention_keylen_kernel, dim3((unsigned)H, (unsigned)B), dim3(64 * nwaves), 0, (hipStream_t)stream,
+                       qkv, (int)T, (int)H, lens, out);
+    MCD_LAUNCH_CHECK("vit_attention_keylen_kernel");
     return MCD_OK;
 }
 

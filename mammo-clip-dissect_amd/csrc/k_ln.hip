@@ -5,25 +5,21 @@
 // Here one wave owns a row: the row lives in registers (NV float4 per lane), mean and the centred sum of squares are
 // two shuffle reductions over it (two-pass in registers: no E[x^2] - E[x]^2 cancellation), one read and one write of
 // HBM per element.  y = (x - mean) / sqrt(var + eps) * gamma + beta, biased variance, like torch.
+//
+// K24 (mcd_text_embed_ln): the embedding rows of the BERT text tower in one launch,
+//   replaces  BertEmbeddings.forward inside BertModel(**tokens) (model/modules/text_encoder.py:48): three gathers, two adds
+//             and embeddings.LayerNorm -- six ATen kernels and three [rows, D] temporaries.
+// out[r] = LayerNorm((word[ids[r]] + type[type_ids[r]]) + pos[r % T]): one wave gathers the three table rows into K10's
+// registers and runs K10's row routine (ln_row) on them, so the result is K10's on ATen's sum, bit for bit.
 #include "mcd_common.h"
+#include "../../include/mcd_text.h"
 
 namespace {
 
+// The row routine of K10 and K24: the row is in v (float4 q = lane + 64 i of it, zeros past nq = D / 4); writes row `row` of y.
 template <int NV>
-__global__ __launch_bounds__(256) void layer_norm_kernel(const float* __restrict__ x, int64_t rows, int D,
-                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                          float eps, float* __restrict__ y) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const float4* xr = reinterpret_cast<const float4*>(x + row * D);
-    const int nq = D >> 2;
-    float4 v[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int q = lane + 64 * i;
-        v[i] = q < nq ? xr[q] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+__device__ __forceinline__ void ln_row(const float4 (&v)[NV], int lane, int nq, int D, const float* __restrict__ gamma,
+                                       const float* __restrict__ beta, float eps, float* __restrict__ y, int64_t row) {
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
@@ -51,6 +47,57 @@ __global__ __launch_bounds__(256) void layer_norm_kernel(const float* __restrict
     }
 }
 
+template <int NV>
+__global__ __launch_bounds__(256) void layer_norm_kernel(const float* __restrict__ x, int64_t rows, int D,
+                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                          float eps, float* __restrict__ y) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float4* xr = reinterpret_cast<const float4*>(x + row * D);
+    const int nq = D >> 2;
+    float4 v[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int q = lane + 64 * i;
+        v[i] = q < nq ? xr[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    ln_row<NV>(v, lane, nq, D, gamma, beta, eps, y, row);
+}
+
+// K24: the row is gathered instead of read -- (word[id] + type[type id]) + pos[row % T], HF's order of the two adds
+// (BertEmbeddings: inputs_embeds + token_type_embeddings, then + position_embeddings), one rounding each -- and goes
+// through the same routine: what K10 gives on ATen's sum of the three gathers, bit for bit.  Ids are clamped into their
+// tables (the binding refuses a bad id on the host; the kernel never reads out of range).
+template <int NV>
+__global__ __launch_bounds__(256) void text_embed_ln_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ type_ids,
+                                                             const float* __restrict__ word, const float* __restrict__ pos,
+                                                             const float* __restrict__ type, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, float eps, int64_t rows, int T,
+                                                             int D, int64_t vocab, int64_t n_type, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    int64_t id = ids[row], tid = type_ids ? type_ids[row] : 0;
+    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+    tid = tid < 0 ? 0 : (tid >= n_type ? n_type - 1 : tid);
+    const float4* wr = reinterpret_cast<const float4*>(word + id * D);
+    const float4* tr = reinterpret_cast<const float4*>(type + tid * D);
+    const float4* pr = reinterpret_cast<const float4*>(pos + (row % T) * D);
+    const int nq = D >> 2;
+    float4 v[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int q = lane + 64 * i;
+        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (q < nq) {
+            const float4 w = wr[q], t = tr[q], p = pr[q];
+            v[i] = make_float4((w.x + t.x) + p.x, (w.y + t.y) + p.y, (w.z + t.z) + p.z, (w.w + t.w) + p.w);
+        }
+    }
+    ln_row<NV>(v, lane, nq, D, gamma, beta, eps, out, row);
+}
+
 }  // namespace
 
 extern "C" int mcd_layer_norm(const float* x, int64_t rows, int64_t D, const float* gamma, const float* beta, float eps,
@@ -73,6 +120,36 @@ extern "C" int mcd_layer_norm(const float* x, int64_t rows, int64_t D, const flo
     else MCD_LN(8);
 #undef MCD_LN
     MCD_LAUNCH_CHECK("layer_norm_kernel");
+    return MCD_OK;
+}
+
+extern "C" int mcd_text_embed_ln(const int64_t* ids, const int64_t* type_ids, const float* word, const float* pos,
+                                 const float* type, const float* gamma, const float* beta, float eps, int64_t rows, int64_t T,
+                                 int64_t D, int64_t vocab, int64_t n_type, float* out, mcd_stream_t stream) {
+    MCD_REQUIRE(ids && word && pos && type && gamma && beta && out, MCD_E_ARG, "mcd_text_embed_ln: NULL pointer");
+    MCD_REQUIRE(rows >= 0 && T >= 1 && vocab >= 1 && n_type >= 1 && T <= INT32_MAX, MCD_E_ARG,
+                "mcd_text_embed_ln: bad shape rows=%lld T=%lld vocab=%lld n_type=%lld", (long long)rows, (long long)T,
+                (long long)vocab, (long long)n_type);
+    MCD_REQUIRE(D >= 4 && D % 4 == 0 && D <= 2048, MCD_E_UNSUPPORTED,
+                "mcd_text_embed_ln: D=%lld must be a multiple of 4 in [4, 2048]", (long long)D);
+    MCD_REQUIRE(((uintptr_t)word) % 16 == 0 && ((uintptr_t)pos) % 16 == 0 && ((uintptr_t)type) % 16 == 0 &&
+                    ((uintptr_t)gamma) % 16 == 0 && ((uintptr_t)beta) % 16 == 0 && ((uintptr_t)out) % 16 == 0 &&
+                    ((uintptr_t)ids) % 8 == 0 && ((uintptr_t)type_ids) % 8 == 0,
+                MCD_E_ARG, "mcd_text_embed_ln: float pointers must be 16-byte aligned, id pointers 8-byte aligned");
+    if (rows == 0) return MCD_OK;
+    const unsigned grid = (unsigned)mcd_cdiv(rows, 4);
+    const int nv = (int)mcd_cdiv(D / 4, 64);
+#define MCD_TE(NV)                                                                                                             \
+    hipLaunchKernelGGL(text_embed_ln_kernel<NV>, dim3(grid), dim3(256), 0, (hipStream_t)stream, ids, type_ids, word, pos, type, \
+                       gamma, beta, eps, rows, (int)T, (int)D, vocab, n_type, out)
+    if (nv <= 1) MCD_TE(1);
+    else if (nv == 2) MCD_TE(2);
+    else if (nv == 3) MCD_TE(3);
+    else if (nv == 4) MCD_TE(4);
+    else if (nv <= 6) MCD_TE(6);
+    else MCD_TE(8);
+#undef MCD_TE
+    MCD_LAUNCH_CHECK("text_embed_ln_kernel");
     return MCD_OK;
 }
 
