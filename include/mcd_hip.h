@@ -22,6 +22,8 @@
  * The text tower's entries of this library -- K9M mcd_vit_attention_keylen (K9 with a key count per sequence) and K24
  * mcd_text_embed_ln (BERT's embedding rows in one launch) -- are declared in mcd_text.h, which includes this header and
  * follows every convention above.  They are additive: mcd_abi_version() stays 9.
+ * The OpenAI-CLIP entries -- K9A mcd_vit_attention_causal (K9 under a causal mask) and K25 mcd_quick_gelu -- are declared in
+ * mcd_clip.h in the same way.
  */
 #ifndef MCD_HIP_H
 #define MCD_HIP_H

@@ -64,6 +64,11 @@ TEXT_SIGNATURES = {
     "mcd_vit_attention_keylen": (_int, [_p, _i64, _i64, _i64, _p, _p, _p]),
     "mcd_text_embed_ln": (_int, [_p, _p, _p, _p, _p, _p, _p, _f, _i64, _i64, _i64, _i64, _i64, _p, _p]),
 }
+# the OpenAI-CLIP entries of the same library, declared in include/mcd_clip.h (additive to ABI version 9)
+CLIP_SIGNATURES = {
+    "mcd_vit_attention_causal": (_int, [_p, _i64, _i64, _i64, _p, _p]),
+    "mcd_quick_gelu": (_int, [_p, _i64, _p, _p]),
+}
 
 MCD_E_ARG = -1
 MCD_E_RANGE = -2
@@ -90,7 +95,7 @@ def load():
                 "mammo-clip-dissect_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; "
                 "g.build()'` or `make -C mammo-clip-dissect_amd/csrc`. There is no CPU fallback." % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -17,6 +17,7 @@ dissection core they feed is the HIP library.
     resnet18 / 34          conv1, layer1..layer4                       64/64/128/256/512
     resnet18_places        as resnet18, 365 classes (reference :70-79)
     clip_rn50 / clip_rn101 visual.layer1..layer4, visual.attnpool      CLIP RN50 / RN101: 256/512/1024/2048, 1024 | 512
+    openai_clip            visual.transformer.resblocks[i], transformer.resblocks[i]   OpenAI CLIP under its own keys (ckpt=)
     vit / -cub / -bloodmnist   vit.encoder.layer[0..11]                HF ViT-B/16 classifier: 12 x 768
     dino / -cub / -bloodmnist  dinov2.encoder.layer[0..11]             HF DINOv2-base classifier (patch 14): 12 x 768
 """
@@ -73,6 +74,10 @@ HIP_CLIP_RN = os.environ.get("MCD_NO_HIP_CLIP_RN", "0") != "1"
 # attention with a key count per sequence: the padded batch's mask), the two residual GEMMs and K10 behind each.
 # MCD_NO_HIP_TEXT=1 (or setting this to False) keeps the ATen route of the same modules, SDPA under the mask included.
 HIP_TEXT = os.environ.get("MCD_NO_HIP_TEXT", "0") != "1"
+# OpenAIClip's inference route (clip_tower_route), both towers: per block K10, the fused qkv GEMM, K9A (the text side's causal
+# attention) or K9 / K9L (the image side), the two residual GEMMs and K25 (QuickGELU) behind c_fc.  MCD_NO_HIP_CLIP_TEXT=1 (or
+# setting this to False) keeps the ATen route of the same modules: SDPA with is_causal and x * sigmoid(1.702 x).
+HIP_CLIP_TEXT = os.environ.get("MCD_NO_HIP_CLIP_TEXT", "0") != "1"
 MAX_BATCH = 65535     # the images of one call that the K12-K18 entries accept
 
 
@@ -992,10 +997,18 @@ TOKENIZER_VOCABS = {}
 
 
 def register_tokenizer(name, vocab_path, do_lower_case=True):
-    """Where a text tower's vocabulary lives (like register_dataset for probe sets): name 'bert', a LOCAL vocab.txt.  The
-    environment variable MCD_BERT_VOCAB=/path/vocab.txt does the same for a process that registers nothing."""
-    if name != "bert":
-        raise ValueError("register_tokenizer: %r is not a tokenizer of this package ('bert')" % (name,))
+    """Where a text tower's vocabulary lives (like register_dataset for probe sets): name 'bert', a LOCAL vocab.txt, or
+    name 'clip', a LOCAL BPE merges file in bpe_simple_vocab_16e6.txt format, plain or gzipped (do_lower_case does not
+    apply: CLIP's tokenizer always lower-cases).  The environment variables MCD_BERT_VOCAB=/path/vocab.txt and
+    MCD_CLIP_BPE=/path/bpe_simple_vocab_16e6.txt.gz do the same for a process that registers nothing.  A 'clip' file is
+    read here, once: one that is no merges file is refused at registration."""
+    if name not in ("bert", "clip"):
+        raise ValueError("register_tokenizer: %r is not a tokenizer of this package ('bert', 'clip')" % (name,))
+    if name == "clip":
+        try:
+            ClipBPETokenizer(vocab_path)
+        except ValueError as e:
+            raise ValueError("register_tokenizer('clip', ...): %s (a WordPiece vocab.txt is registered as 'bert')" % (e,)) from e
     TOKENIZER_VOCABS[name] = (vocab_path, bool(do_lower_case))
 
 
@@ -1750,6 +1763,529 @@ CLIP_RESNETS = {"clip_rn50": ((3, 4, 6, 3), 1024), "clip_rn101": ((3, 4, 23, 3),
 
 
 # ------------------------------------------------------------------------------------------------------
+# OpenAI CLIP itself: the reference's concept_vit/clip/model.py CLIP (:239-383) restated under OpenAI's own parameter
+# names, so that a real state dict loads strictly, and its byte-pair tokenizer (simple_tokenizer.py, clip.py:196-232)
+# ------------------------------------------------------------------------------------------------------
+_CLIP_BLOCK_SKIPPED = ("ln_1", "attn", "mlp", "ln_2")
+_CLIP_IGNORED = ("input_resolution", "context_length", "vocab_size")       # scalars of OpenAI's archives; build_model deletes them
+
+
+def clip_tower_route(flag, on_gpu, dtype, grad, training, B, T, D, heads, fused_ok):
+    """'hip' when a tower of OpenAIClip may leave ATen for a call of B sequences of T tokens of width D: HIP_CLIP_TEXT
+    (`flag`) on, fp32 on the GPU without autograd (_hip_eligible), eval mode, D = 64 * heads (the head width of K9, K9A
+    and K9L), a width K10 takes, a token count one of the attention kernels takes, at most MAX_BATCH sequences, and
+    the fused-residual GEMMs available for the call (`fused_ok`: every projection is one).  Otherwise 'aten'.  Hooks are
+    looked at per block: one with a hook inside runs its ATen modules."""
+    ok = (flag and _hip_eligible(on_gpu, dtype, grad) and not training and D == 64 * heads and D % 4 == 0 and D <= 2048
+          and 1 <= T <= core.VIT_ATTENTION_LONG_MAX_T and _under_2g(T * 3 * D) and 1 <= B <= MAX_BATCH and fused_ok)
+    return "hip" if ok else "aten"
+
+
+def quick_gelu(x):
+    """x * sigmoid(1.702 x) on ATen (model.py:162-164): three launches on the GPU; the HIP route calls K25 instead."""
+    return x * torch.sigmoid(1.702 * x)
+
+
+class _QuickGELU(nn.Module):
+    def forward(self, x):
+        return quick_gelu(x)
+
+
+class _ClipMHA(nn.Module):
+    """The parameters of nn.MultiheadAttention under its names (in_proj_weight, in_proj_bias, out_proj.*), batch first,
+    self-attention only; forward is the ATen route: one projection, SDPA (is_causal for the text side), out_proj."""
+
+    def __init__(self, dim, heads):
+        super().__init__()
+        self.heads = heads
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * dim, dim))
+        self.in_proj_bias = nn.Parameter(torch.zeros(3 * dim))
+        self.out_proj = nn.Linear(dim, dim)
+
+    def forward(self, x, causal=False):
+        B, T, D = x.shape
+        q, k, v = F.linear(x, self.in_proj_weight, self.in_proj_bias).view(B, T, 3, self.heads, D // self.heads).permute(2, 0, 3, 1, 4)
+        o = F.scaled_dot_product_attention(q, k, v, is_causal=causal)
+        return self.out_proj(o.transpose(1, 2).reshape(B, T, D))
+
+
+class _ClipResBlock(nn.Module):
+    """ResidualAttentionBlock (model.py:167-188), pre-norm: x1 = x + attn(ln_1(x)), out = x1 + c_proj(QuickGELU(c_fc(ln_2(x1)))).
+    causal: the text transformer's mask (model.py:324-330), query t sees keys 0 .. t."""
+
+    def __init__(self, dim, heads, causal=False):
+        super().__init__()
+        self.causal = causal
+        self.attn = _ClipMHA(dim, heads)
+        self.ln_1 = nn.LayerNorm(dim)
+        self.mlp = nn.Sequential()
+        self.mlp.add_module("c_fc", nn.Linear(dim, 4 * dim))
+        self.mlp.add_module("gelu", _QuickGELU())
+        self.mlp.add_module("c_proj", nn.Linear(4 * dim, dim))
+        self.ln_2 = nn.LayerNorm(dim)
+
+    def forward(self, x, hip=False, cls_only=False):
+        """hip: the tower has checked clip_tower_route; the block takes the HIP route unless a hook sits inside it.
+        cls_only (the tower has checked cls_tail_route as well): the class-token row alone, as [B, 1, D]."""
+        if hip and not _hooks_on(self, _CLIP_BLOCK_SKIPPED):
+            return self._forward_cls(x) if cls_only else self._forward_hip(x)
+        x = x + self.attn(self.ln_1(x), self.causal)
+        return x + self.mlp(self.ln_2(x))
+
+    def _ln(self, ln, x):
+        return core.layer_norm(x, ln.weight, ln.bias, ln.eps)                                           # K10
+
+    def _forward_hip(self, x):
+        a, m = self.attn, self.mlp
+        x = x.contiguous()
+        qkv = core.linear_residual(None, self._ln(self.ln_1, x), a.in_proj_weight, a.in_proj_bias)
+        if self.causal:
+            o = core.vit_attention_causal(qkv, a.heads)                                                 # K9A
+        elif x.shape[1] <= core.VIT_ATTENTION_MAX_T:
+            o = core.vit_attention(qkv, a.heads)                                                        # K9
+        else:
+            o = core.vit_attention_long(qkv, a.heads)                                                   # K9L
+        x1 = core.linear_residual(x, o, a.out_proj.weight, a.out_proj.bias)       # a new tensor: the input is left alone
+        h = core.linear_residual(None, self._ln(self.ln_2, x1), m.c_fc.weight, m.c_fc.bias)
+        core.quick_gelu(h, out=h)                                                                       # K25, in place
+        return core.linear_residual(x1, h, m.c_proj.weight, m.c_proj.bias, out=x1)
+
+    def _forward_cls(self, x):
+        """_Block._forward_cls with this block's parameters: K and V for every token, the rest for row 0 alone."""
+        B, T, D = x.shape
+        a, m = self.attn, self.mlp
+        x = x.contiguous()
+        n = self._ln(self.ln_1, x)
+        w, b = a.in_proj_weight, a.in_proj_bias
+        kv = core.linear_residual(None, n, w[D:], b[D:]).view(B, T, 2, a.heads, D // a.heads)
+        q = core.linear_residual(None, n[:, 0], w[:D], b[:D])
+        o = core.vit_attention_cls(q, kv[:, :, 0], kv[:, :, 1])                                         # K9C
+        x1 = core.linear_residual(x[:, 0], o, a.out_proj.weight, a.out_proj.bias)                       # [B, D], a new tensor
+        h = core.linear_residual(None, self._ln(self.ln_2, x1), m.c_fc.weight, m.c_fc.bias)
+        core.quick_gelu(h, out=h)
+        return core.linear_residual(x1, h, m.c_proj.weight, m.c_proj.bias, out=x1).unsqueeze(1)
+
+
+class _ClipTransformer(nn.Module):
+    def __init__(self, width, layers, heads, causal=False):
+        super().__init__()
+        self.width, self.layers = width, layers
+        self.resblocks = nn.ModuleList([_ClipResBlock(width, heads, causal) for _ in range(layers)])
+
+    def forward(self, x, hip=False, cls_only=False):
+        """Each block through __call__, so that its hooks fire; cls_only prunes the last one to its class-token row."""
+        for i, blk in enumerate(self.resblocks):
+            x = blk(x, hip, cls_only and i == len(self.resblocks) - 1)
+        return x
+
+
+class _ClipVisionTransformer(nn.Module):
+    """VisionTransformer (model.py:202-236): a patch convolution WITHOUT bias, class_embedding, positional_embedding,
+    ln_pre, the blocks, ln_post on the class-token row, @ proj.  Returns [B, output_dim]."""
+
+    def __init__(self, input_resolution, patch_size, width, layers, heads, output_dim):
+        super().__init__()
+        self.input_resolution, self.output_dim = input_resolution, output_dim
+        self.conv1 = nn.Conv2d(3, width, patch_size, patch_size, bias=False)
+        scale = width ** -0.5
+        self.class_embedding = nn.Parameter(scale * torch.randn(width))
+        self.positional_embedding = nn.Parameter(scale * torch.randn((input_resolution // patch_size) ** 2 + 1, width))
+        self.ln_pre = nn.LayerNorm(width)
+        self.transformer = _ClipTransformer(width, layers, heads)
+        self.ln_post = nn.LayerNorm(width)
+        self.proj = nn.Parameter(scale * torch.randn(width, output_dim))
+
+    def route(self, x):
+        P = self.conv1.kernel_size[0]
+        n = self.positional_embedding.shape[0]
+        heads = self.transformer.resblocks[0].attn.heads if len(self.transformer.resblocks) else 0
+        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and x.is_contiguous()
+                and embed_gate(P, x.shape[2], x.shape[3], n)):
+            return "aten"
+        return clip_tower_route(HIP_CLIP_TEXT, x.is_cuda, x.dtype, torch.is_grad_enabled(), self.training, x.shape[0], n,
+                                self.conv1.out_channels, heads, _fused_residual_ok(x))
+
+    def forward(self, x):
+        x = x.to(self.conv1.weight.dtype)
+        if self.route(x) == "hip":
+            return self._forward_hip(x)
+        x = self.conv1(x).flatten(2).transpose(1, 2)
+        x = torch.cat([self.class_embedding.expand(x.shape[0], 1, -1), x], dim=1) + self.positional_embedding
+        x = self.transformer(self.ln_pre(x))
+        return self.ln_post(x[:, 0]) @ self.proj
+
+    def _forward_hip(self, x):
+        B = x.shape[0]
+        P = self.conv1.kernel_size[0]
+        # K11 + one GEMM without a bias term: the rows of patch pixels (a zero row in the class-token slot) times the conv
+        # weight, plus a residual operand that holds the position table with class_embedding + its row 0 in row 0
+        t = core.linear_residual(self._embed_residual(B), core.patchify(x, P), self.conv1.weight.view(self.conv1.out_channels, -1))
+        if _hooked(self.ln_pre) or _nn_module._global_forward_hooks or _nn_module._global_forward_pre_hooks:
+            t = self.ln_pre(t)
+        else:
+            t = core.layer_norm(t, self.ln_pre.weight, self.ln_pre.bias, self.ln_pre.eps)               # K10
+        t = self.transformer(t, True, self._cls_tail_ok(t))
+        row = t[:, 0].contiguous()
+        if _hooked(self.ln_post):
+            return self.ln_post(row) @ self.proj
+        return core.layer_norm(row, self.ln_post.weight, self.ln_post.bias, self.ln_post.eps) @ self.proj
+
+    def _embed_residual(self, B):
+        def build(m):
+            r = m.positional_embedding.detach().expand(B, -1, -1).contiguous()
+            r[:, 0] += m.class_embedding.detach()
+            return r
+        return _folded(self, ("positional_embedding", "class_embedding"), build, extra=(B,))
+
+    def _cls_tail_ok(self, t):
+        """cls_tail_route for the embedded tokens t [B, T, D] and the hooks this tower carries right now: nothing reads
+        any row of the last block but the class token's (forward slices it; the package's hooks declare token0_only)."""
+        blocks = self.transformer.resblocks
+        if len(blocks) == 0:
+            return False
+        last = blocks[-1]
+        clear = not (_nn_module._global_forward_hooks or _nn_module._global_forward_pre_hooks or last._forward_pre_hooks
+                     or any(_hooked(c) for c in last.children())
+                     or self.transformer._forward_hooks or self.transformer._forward_pre_hooks)
+        return cls_tail_route(CLS_ONLY_TAIL, _fused_residual_ok(t), False, self.training or last.training, t.shape[1],
+                              t.shape[2], last.attn.heads, len(blocks), clear, _token0_hooks(last))
+
+
+def openai_clip_config(sd):
+    """OpenAIClip's constructor arguments read from the shapes of an OpenAI CLIP state dict, as the reference's build_model
+    does (model.py:410-433): a ViT when the state dict has visual.proj, else a ModifiedResNet; heads = width // 64."""
+    def shape(key):
+        if key not in sd:
+            raise RuntimeError("not an OpenAI CLIP state dict: it lacks %r" % (key,))
+        return tuple(sd[key].shape)
+    if "visual.proj" in sd:
+        width, _, patch, _ = shape("visual.conv1.weight")
+        layers = len([k for k in sd if k.startswith("visual.") and k.endswith(".attn.in_proj_weight")])
+        grid = round((shape("visual.positional_embedding")[0] - 1) ** 0.5)
+        resolution = patch * grid
+    else:
+        layers = tuple(len(set(k.split(".")[2] for k in sd if k.startswith("visual.layer%d." % b))) for b in (1, 2, 3, 4))
+        width = shape("visual.layer1.0.conv1.weight")[0]
+        side = round((shape("visual.attnpool.positional_embedding")[0] - 1) ** 0.5)
+        if side * side + 1 != shape("visual.attnpool.positional_embedding")[0]:
+            raise RuntimeError("visual.attnpool.positional_embedding has %d rows: not a square grid plus one"
+                               % shape("visual.attnpool.positional_embedding")[0])
+        patch, resolution = None, side * 32
+    t_width = shape("ln_final.weight")[0]
+    return dict(embed_dim=shape("text_projection")[1], image_resolution=resolution, vision_layers=layers, vision_width=width,
+                vision_patch_size=patch, context_length=shape("positional_embedding")[0],
+                vocab_size=shape("token_embedding.weight")[0], transformer_width=t_width, transformer_heads=t_width // 64,
+                transformer_layers=len(set(k.split(".")[2] for k in sd if k.startswith("transformer.resblocks."))))
+
+
+VIT_B16 = dict(embed_dim=512, image_resolution=224, vision_layers=12, vision_width=768, vision_patch_size=16,
+               context_length=77, vocab_size=49408, transformer_width=512, transformer_heads=8, transformer_layers=12)
+
+
+class OpenAIClip(nn.Module):
+    """OpenAI CLIP as the reference's clip.load builds it (model.py:239-383), under OpenAI's parameter names: visual.*
+    (a _ClipVisionTransformer, or the ModifiedResNet of the RN dissectors when vision_layers is a tuple), transformer.*,
+    token_embedding, positional_embedding, ln_final, text_projection, logit_scale.  The default arguments are ViT-B/16's.
+
+    encode_image(image) -> [B, embed_dim]; encode_text(tokens) -> [B, embed_dim] for a plain int64 [B, context_length]
+    tensor of token ids (ClipBPETokenizer's output: the end-of-text id is the largest of a row, so argmax finds it);
+    forward(image) = encode_image, as ClipViT's.  Hook points: visual.transformer.resblocks[i] and
+    transformer.resblocks[i].  Block outputs are [B, T, D], batch first as everywhere in this project -- the reference's
+    blocks see [T, B, D].  Computes in fp32 (fp16 checkpoints are upcast on load: clip.load(device="cpu") does the same).
+
+    The HIP route (HIP_CLIP_TEXT, clip_tower_route): per block K10, the fused qkv GEMM, K9A (text: causal) or K9 / K9L
+    (image), the two residual GEMMs and K25 behind c_fc; the image side embeds through K11 + one GEMM and prunes its last
+    block to the class-token row (cls_tail_route, K9C)."""
+
+    def __init__(self, embed_dim=512, image_resolution=224, vision_layers=12, vision_width=768, vision_patch_size=16,
+                 context_length=77, vocab_size=49408, transformer_width=512, transformer_heads=8, transformer_layers=12):
+        super().__init__()
+        self.context_length, self.vocab_size, self.embed_dim = context_length, vocab_size, embed_dim
+        if isinstance(vision_layers, (tuple, list)):
+            self.visual = ModifiedResNet(tuple(vision_layers), embed_dim, vision_width * 32 // 64, image_resolution, vision_width)
+        else:
+            self.visual = _ClipVisionTransformer(image_resolution, vision_patch_size, vision_width, vision_layers,
+                                                 vision_width // 64, embed_dim)
+        self.transformer = _ClipTransformer(transformer_width, transformer_layers, transformer_heads, causal=True)
+        self.token_embedding = nn.Embedding(vocab_size, transformer_width)
+        self.positional_embedding = nn.Parameter(torch.empty(context_length, transformer_width))
+        self.ln_final = nn.LayerNorm(transformer_width)
+        self.text_projection = nn.Parameter(torch.empty(transformer_width, embed_dim))
+        self.logit_scale = nn.Parameter(torch.ones([]) * math.log(1 / 0.07))
+        self.tokenizer = None                       # resolved at tokenize(): the registered merges file or an error
+        self._init_parameters()
+
+    def _init_parameters(self):
+        """Seeded stand-in weights at the scales CLIP trains from (model.py:295-322), for a model built without a checkpoint."""
+        nn.init.normal_(self.token_embedding.weight, std=0.02)
+        nn.init.normal_(self.positional_embedding, std=0.01)
+        towers = [self.transformer] + ([self.visual.transformer] if isinstance(self.visual, _ClipVisionTransformer) else [])
+        for tr in towers:
+            for blk in tr.resblocks:
+                nn.init.normal_(blk.attn.in_proj_weight, std=tr.width ** -0.5)
+                nn.init.normal_(blk.attn.out_proj.weight, std=tr.width ** -0.5 * (2 * tr.layers) ** -0.5)
+                nn.init.normal_(blk.mlp.c_fc.weight, std=(2 * tr.width) ** -0.5)
+                nn.init.normal_(blk.mlp.c_proj.weight, std=tr.width ** -0.5 * (2 * tr.layers) ** -0.5)
+        nn.init.normal_(self.text_projection, std=self.transformer.width ** -0.5)
+
+    @classmethod
+    def from_state_dict(cls, sd):
+        """The model of an OpenAI CLIP state dict: the configuration from its shapes (openai_clip_config), the three
+        scalar keys input_resolution / context_length / vocab_size ignored by name, floating tensors upcast to fp32, and
+        a STRICT load: a missing or an unexpected key is an error, never a tower of random weights."""
+        sd = {k: (v.float() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in sd.items()
+              if k not in _CLIP_IGNORED}
+        model = cls(**openai_clip_config(sd))
+        model.load_state_dict(sd, strict=True)
+        return model
+
+    def text_route(self, tokens):
+        """clip_tower_route for the text side on the ids `tokens` [B, T]; K9A takes up to core.VIT_ATTENTION_MAX_T tokens."""
+        w = self.token_embedding.weight
+        B, T = tokens.shape
+        if T > core.VIT_ATTENTION_MAX_T or not self.transformer.layers:
+            return "aten"
+        return clip_tower_route(HIP_CLIP_TEXT, w.is_cuda and tokens.is_cuda, w.dtype, torch.is_grad_enabled(), self.training,
+                                B, T, w.shape[1], self.transformer.resblocks[0].attn.heads,
+                                FUSED_RESIDUAL and core.linear_residual_available())
+
+    def encode_image(self, image):
+        return self.visual(image)
+
+    def encode_text(self, tokens):
+        if isinstance(tokens, dict) or tokens.dim() != 2 or tokens.dtype != torch.int64:
+            raise ValueError("OpenAIClip.encode_text takes an int64 [B, context_length] tensor of token ids")
+        if tokens.shape[1] > self.context_length:
+            raise ValueError("%d tokens, the position table has %d rows" % (tokens.shape[1], self.context_length))
+        x = self.token_embedding(tokens) + self.positional_embedding[:tokens.shape[1]]
+        x = self.transformer(x, self.text_route(tokens) == "hip")
+        # the end-of-text row (the largest id of a sequence), THEN ln_final on those B rows: LayerNorm is per row
+        x = x[torch.arange(x.shape[0], device=x.device), tokens.argmax(dim=-1)]
+        return self.ln_final(x) @ self.text_projection
+
+    def forward(self, image):
+        return self.encode_image(image)
+
+    def tokenize(self, texts, truncate=False):
+        """clip.tokenize at this model's context length, with the registered merges file (register_tokenizer('clip', path)
+        or MCD_CLIP_BPE); without one an error -- never the hashing stand-in."""
+        if self.tokenizer is None:
+            self.tokenizer = clip_tokenizer()
+        tok = self.tokenizer(texts, context_length=self.context_length, truncate=truncate)
+        if tok.numel() and int(tok.max()) >= self.vocab_size:
+            raise ValueError("the merges file gives token id %d, the checkpoint's embedding table has %d rows: this is not "
+                             "the merges file of the checkpoint's tokenizer" % (int(tok.max()), self.vocab_size))
+        return tok
+
+
+# the White_Space property: what \s of the reference's pattern (the `regex` package, a str pattern) matches
+_UNICODE_SPACE = frozenset("\t\n\x0b\x0c\r \x85\xa0\u1680\u2000\u2001\u2002\u2003\u2004\u2005\u2006\u2007\u2008\u2009\u200a"
+                           "\u2028\u2029\u202f\u205f\u3000")
+_CLIP_CONTRACTIONS = ("'s", "'t", "'re", "'ve", "'m", "'ll", "'d")  # in the pattern's order
+_CLIP_SOT, _CLIP_EOT = "<|startoftext|>", "<|endoftext|>"
+
+
+def _clip_byte_table():
+    """byte -> the printable character that stands for it in the merges file (GPT-2's table): the printable Latin-1 bytes
+    are themselves, the other 68 take the code points from 256 up, in byte order."""
+    keep = list(range(0x21, 0x7F)) + list(range(0xA1, 0xAD)) + list(range(0xAE, 0x100))
+    table = {b: chr(b) for b in keep}
+    spare = 256
+    for b in range(256):
+        if b not in table:
+            table[b] = chr(spare)
+            spare += 1
+    return keep + [b for b in range(256) if b not in set(keep)], table
+
+
+class ClipBPETokenizer:
+    """OpenAI CLIP's tokenizer restated in pure Python (standard library + torch; neither `regex` nor `ftfy`): the
+    reference's SimpleTokenizer (concept_vit/clip/simple_tokenizer.py) and clip.tokenize (clip.py:196-232), from a local
+    merges file in bpe_simple_vocab_16e6.txt format, plain or gzipped.
+
+      1. clean: html.unescape twice, strip, every run of white space becomes one space, strip, lower-case;
+      2. split: at each position the first that applies of -- one of the two special strings; one of the contractions
+         's 't 're 've 'm 'll 'd; a run of letters (category L*); ONE number character (N*); a run of anything that is
+         neither white space, letter nor number -- a scanner over unicodedata categories for the reference's pattern;
+      3. each piece: its UTF-8 bytes through the byte table, the last character marked </w>, then the lowest-ranked
+         adjacent pair is merged, all its occurrences at once, until no pair of the word has a rank;
+      4. start id + ids + end id, zero padding to context_length; longer: RuntimeError, or with truncate=True cut to
+         context_length with the end id last.
+    Vocabulary: the 256 byte characters, the same with </w>, one entry per merge -- lines [1 : 49152 - 256 - 2 + 1] of the
+    file, the reference's slice -- then the two specials, whose ids are read from the vocabulary that results: a shorter
+    merges file gives a consistent smaller vocabulary, and the end-of-text id is always the largest.
+    Not restated: ftfy.fix_text in front of step 1 (mojibake repair) -- text is taken as given."""
+
+    MAX_MERGES = 49152 - 256 - 2
+
+    def __init__(self, bpe_path):
+        with open(bpe_path, "rb") as f:
+            raw = f.read()
+        if raw[:2] == b"\x1f\x8b":
+            import gzip
+            raw = gzip.decompress(raw)
+        lines = raw.decode("utf-8").split("\n")[1:self.MAX_MERGES + 1]
+        merges = [tuple(line.split()) for line in lines]        # (an empty line is the entry '' here as in the reference)
+        bad = [i + 2 for i, m in enumerate(merges) if len(m) not in (0, 2)]
+        if bad or not any(merges):
+            raise ValueError("%r is not a BPE merges file: line %s is not a pair of symbols" % (bpe_path, bad[0] if bad else 2))
+        order, self.byte_table = _clip_byte_table()
+        vocab = [self.byte_table[b] for b in order]
+        vocab = vocab + [v + "</w>" for v in vocab] + ["".join(m) for m in merges] + [_CLIP_SOT, _CLIP_EOT]
+        self.encoder = {}
+        for i, v in enumerate(vocab):
+            self.encoder[v] = i                    # a repeated entry keeps its last id, as the reference's dict(zip()) does
+        self.vocab_size = len(vocab)
+        self.ranks = {}
+        for i, m in enumerate(merges):
+            self.ranks[m] = i
+        self.sot_id, self.eot_id = self.encoder[_CLIP_SOT], self.encoder[_CLIP_EOT]
+        self._cache = {}
+
+    @staticmethod
+    def clean(text):
+        import html
+        text = html.unescape(html.unescape(text)).strip()
+        out, gap = [], False
+        for ch in text:
+            if ch in _UNICODE_SPACE:
+                gap = True
+                continue
+            if gap and out:
+                out.append(" ")
+            gap = False
+            out.append(ch)
+        return "".join(out).lower()
+
+    @staticmethod
+    def split(text):
+        pieces, i, n = [], 0, len(text)
+        while i < n:
+            ch = text[i]
+            special = next((s for s in (_CLIP_SOT, _CLIP_EOT) + _CLIP_CONTRACTIONS if text.startswith(s, i)), None)
+            if special is not None:
+                pieces.append(special)
+                i += len(special)
+                continue
+            kind = unicodedata.category(ch)[0]
+            if kind == "N":
+                pieces.append(ch)
+                i += 1
+                continue
+            if ch in _UNICODE_SPACE:
+                i += 1
+                continue
+            j = i + 1
+            if kind == "L":
+                while j < n and unicodedata.category(text[j])[0] == "L":
+                    j += 1
+            else:
+                while j < n and text[j] not in _UNICODE_SPACE and unicodedata.category(text[j])[0] not in "LN":
+                    j += 1
+            pieces.append(text[i:j])
+            i = j
+        return pieces
+
+    def bpe(self, piece):
+        """The ids of one piece of the split."""
+        if piece in self._cache:
+            return self._cache[piece]
+        if piece in (_CLIP_SOT, _CLIP_EOT):
+            ids = [self.encoder[piece]]
+        else:
+            word = [self.byte_table[b] for b in piece.encode("utf-8")]
+            word[-1] += "</w>"
+            while len(word) > 1:
+                best = min(zip(word, word[1:]), key=lambda p: self.ranks.get(p, float("inf")))
+                if best not in self.ranks:
+                    break
+                merged, k = [], 0
+                while k < len(word):
+                    if k + 1 < len(word) and (word[k], word[k + 1]) == best:
+                        merged.append(word[k] + word[k + 1])
+                        k += 2
+                    else:
+                        merged.append(word[k])
+                        k += 1
+                word = merged
+            ids = [self.encoder[w] for w in word]
+        self._cache[piece] = ids
+        return ids
+
+    def encode(self, text):
+        return [i for piece in self.split(self.clean(text)) for i in self.bpe(piece)]
+
+    def __call__(self, texts, context_length=77, truncate=False):
+        if isinstance(texts, str):
+            texts = [texts]
+        out = torch.zeros(len(texts), context_length, dtype=torch.long)
+        for r, text in enumerate(texts):
+            ids = [self.sot_id] + self.encode(text) + [self.eot_id]
+            if len(ids) > context_length:
+                if not truncate:
+                    raise RuntimeError("Input %s is too long for context length %d" % (text, context_length))
+                ids = ids[:context_length]
+                ids[-1] = self.eot_id
+            out[r, :len(ids)] = torch.tensor(ids, dtype=torch.long)
+        return out
+
+
+def clip_tokenizer():
+    """The ClipBPETokenizer of the registered merges file; without one an error -- never the hashing stand-in, whose ids
+    would address arbitrary rows of a real embedding table."""
+    entry = TOKENIZER_VOCABS.get("clip")
+    path = entry[0] if entry is not None else os.environ.get("MCD_CLIP_BPE")
+    if not path:
+        raise RuntimeError("OpenAI CLIP's text tower needs its BPE merges file: call data_utils.register_tokenizer('clip', "
+                           "'/path/bpe_simple_vocab_16e6.txt.gz') or set MCD_CLIP_BPE=/path/bpe_simple_vocab_16e6.txt.gz; "
+                           "there is no fallback to the hashing tokenizer")
+    return ClipBPETokenizer(path)
+
+
+# --clip_model name (or any name) -> a LOCAL OpenAI CLIP checkpoint, like register_dataset for probe sets
+CLIP_CHECKPOINTS = {}
+
+
+def register_clip_checkpoint(name, path):
+    """Where the OpenAI CLIP checkpoint of --clip_model `name` lives (a state dict file or OpenAI's TorchScript archive).
+    The environment variable MCD_CLIP_CKPTS='ViT-B/16=/path/a.pt,RN50=/path/b.pt' does the same for a process that
+    registers nothing."""
+    CLIP_CHECKPOINTS[name] = path
+
+
+def clip_checkpoint(name):
+    """The registered checkpoint path of `name`, or None."""
+    if name in CLIP_CHECKPOINTS:
+        return CLIP_CHECKPOINTS[name]
+    for item in os.environ.get("MCD_CLIP_CKPTS", "").split(","):
+        key, sep, path = item.partition("=")
+        if sep and key.strip() == name:
+            return path.strip()
+    return None
+
+
+def _is_torchscript_archive(path):
+    """A zip with TorchScript's code/ folder and constants.pkl beside data.pkl: what torch.jit.save writes and OpenAI
+    distributes; torch.save writes neither."""
+    import zipfile
+    if not zipfile.is_zipfile(path):
+        return False
+    with zipfile.ZipFile(path) as z:
+        names = z.namelist()
+    return any(n.endswith("/constants.pkl") for n in names) and any("/code/" in n for n in names)
+
+
+def openai_clip_state_dict(ckpt):
+    """ckpt: a state dict, or a LOCAL path to one (read with weights_only=True) or to a TorchScript archive, whose
+    state_dict() is taken as clip.load does (clip.py:126-138; loading such an archive unpickles its code)."""
+    if isinstance(ckpt, str):
+        if _is_torchscript_archive(ckpt):
+            return dict(torch.jit.load(ckpt, map_location="cpu").state_dict())
+        ckpt = torch.load(ckpt, map_location="cpu", weights_only=True)
+    return ckpt["model"] if isinstance(ckpt, dict) and "model" in ckpt and "text_projection" not in ckpt else ckpt
+
+
+# ------------------------------------------------------------------------------------------------------
 # factories
 # ------------------------------------------------------------------------------------------------------
 BERT_PREFIX = "text_encoder.text_encoder."
@@ -1822,6 +2358,13 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
     size, depth, intermediate size, vocabulary and position rows are read from the checkpoint's shapes."""
     if text_tower not in (None, "stand-in", "bert"):
         raise ValueError("text_tower must be None, 'stand-in' or 'bert', got %r" % (text_tower,))
+    if target_name == "openai_clip":
+        # OpenAI CLIP itself: ckpt a state dict, or a LOCAL path to one or to OpenAI's TorchScript archive -- the model is
+        # sized from its shapes and loaded strictly; without ckpt, ViT-B/16's configuration with seeded weights
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(seed)
+            model = OpenAIClip(**VIT_B16) if ckpt is None else OpenAIClip.from_state_dict(openai_clip_state_dict(ckpt))
+        return model.to(device).eval(), None
     text_kw = {}
     if target_name.startswith("breastclip") and target_name != "breastclip_classifier" and (ckpt is not None or text_tower):
         if ckpt is not None:
@@ -1865,7 +2408,7 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
                         image_size=image_size)
         else:
             raise ValueError("unknown target model %r (offline build: breastclip, breastclip_vit, "
-                             "breastclip_classifier, clip, clip_rn50, clip_rn101, resnet18, resnet18_places, resnet34, "
+                             "breastclip_classifier, clip, openai_clip, clip_rn50, clip_rn101, resnet18, resnet18_places, resnet34, "
                              "resnet50, resnet101, resnet152, vit, vit-cub, vit-bloodmnist, dino, dino-cub, "
                              "dino-bloodmnist)" % (target_name,))
     if target_name == "resnet18_places":

@@ -4,8 +4,11 @@ Kept contracts (reference og_utils.py): get_activation :31-56, get_save_names :5
 save_activations :374-471, get_similarity_from_activations :474-518 (no `top_k` argument: the similarity
 function runs with its own default, as in the reference).  The CLIP dissector is the offline ClipViT of
 data_utils, or its ClipResNet for --clip_model RN50 / RN101 (reference: clip.load(clip_name), a URL download); text
-goes through the same offline tokenizer.
+goes through the same offline tokenizer.  With a local OpenAI CLIP checkpoint (a path as --clip_model, or one registered
+for the name) the dissector is data_utils.OpenAIClip and the text goes through its byte-pair tokenizer (_clip_dissector).
 """
+import os
+
 import torch
 
 from . import data_utils
@@ -29,8 +32,16 @@ CLIP_DISSECTORS = {"RN50": "clip_rn50", "RN101": "clip_rn101"}
 
 
 def _clip_dissector(device, clip_name="ViT-B/16"):
-    """(dissector, tokenize) for --clip_model `clip_name` (reference: clip.load(clip_name)): ClipResNet for RN50 /
-    RN101, ClipViT otherwise."""
+    """(dissector, tokenize) for --clip_model `clip_name` (reference: clip.load(clip_name), clip.tokenize).
+    With a checkpoint -- `clip_name` an existing local file, the path clip.load takes as well, or a name with a
+    registered checkpoint (data_utils.register_clip_checkpoint / MCD_CLIP_CKPTS) -- OpenAI CLIP itself: OpenAIClip sized
+    from the checkpoint, ViT or ResNet, with the ClipBPETokenizer of the registered merges file at the model's context
+    length.  Without one, the shaped stand-ins as before: ClipResNet for RN50 / RN101, ClipViT otherwise, with the
+    hashing tokenizer."""
+    ckpt = clip_name if isinstance(clip_name, str) and os.path.isfile(clip_name) else data_utils.clip_checkpoint(clip_name)
+    if ckpt is not None:
+        model, _ = data_utils.get_target_model("openai_clip", device, ckpt=ckpt)
+        return model, model.tokenize
     model, _ = data_utils.get_target_model(CLIP_DISSECTORS.get(clip_name, "clip"), device)
     tok = data_utils.HashTokenizer()
     return model, (lambda texts: tok(texts, max_length=77))

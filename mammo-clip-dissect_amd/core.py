@@ -469,6 +469,30 @@ def vit_attention_keylen(qkv, heads, lens, out=None):
     return out
 
 
+# ---- K9A -----------------------------------------------------------------------------------------
+@_on_device
+def vit_attention_causal(qkv, heads, out=None):
+    """vit_attention under a causal mask (K9A, include/mcd_clip.h): query t attends to keys 0 .. t.  The same layout and
+    limits (T <= 256); row t carries the bits of vit_attention on the sequence truncated to t + 1 tokens."""
+    return _attention("mcd_vit_attention_causal", qkv, heads, out)
+
+
+# ---- K25 -----------------------------------------------------------------------------------------
+@_on_device
+def quick_gelu(x, out=None):
+    """x * sigmoid(1.702 x) in one launch (K25, include/mcd_clip.h): x a contiguous float32 tensor of any shape; out None
+    (a new tensor), x itself (in place) or another contiguous float32 tensor of x's shape."""
+    _need_gpu(x, out)
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise TypeError("x must be a contiguous float32 tensor")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.dtype != torch.float32 or out.shape != x.shape or not out.is_contiguous():
+        raise TypeError("out must be a contiguous float32 tensor of x's shape")
+    check(_lib.load().mcd_quick_gelu(x.data_ptr(), x.numel(), out.data_ptr(), _stream()))
+    return out
+
+
 # ---- K9C -----------------------------------------------------------------------------------------
 VIT_ATTENTION_CLS_MAX_T = 32768
 

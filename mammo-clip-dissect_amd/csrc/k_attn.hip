@@ -42,6 +42,13 @@
 // nothing.  Rows 0 .. L-1 are K9's bits on the sequence truncated to L tokens; the padded query rows are computed too
 // (BertModel and SDPA do the same).  A NaN in q reaches that output row of that head only; +-Inf inputs: unspecified.
 //
+// K9A (mcd_vit_attention_causal, include/mcd_clip.h): K9 under a causal mask, for OpenAI CLIP's text transformer
+//     concept_vit/clip/model.py:181-183, :324-330  nn.MultiheadAttention under attn_mask = triu(-inf, 1)
+// Query t attends to keys 0 .. t.  Compute wave w (queries 32w .. 32w+31) needs the key tiles 0 .. w only: its tile loop
+// ends after tile w, where the keys above the lane's own query get -inf in place of K9's end-of-sequence mask, and it then
+// meets the loader at the remaining pair barriers with nothing between them.  Tile count, masked key set and online-softmax
+// steps of row t are those of K9 on the sequence truncated to t + 1 tokens: the same bits, whatever follows token t.
+//
 // K9C (mcd_vit_attention_cls): attention for ONE query row per image -- the class token of the last encoder block, the
 // only row of that block anything downstream reads (concept_vit/data_utils.py, cls_tail_route).  2 * 64 flops per 512
 // bytes of K and V: a streaming kernel, bound by reading every K and V head row once (2 * B * T * H * 256 bytes), not
@@ -53,6 +60,7 @@
 // K|V-only projection and a plain [B, T, 3, H, 64] qkv are both addressed in place.
 #include "mcd_common.h"
 #include "../../include/mcd_text.h"
+#include "../../include/mcd_clip.h"
 
 namespace {
 
@@ -71,7 +79,9 @@ constexpr int AT_NSTAGE = 4;       // ring of tiles: two pairs
 // KEYLEN (K9M): the keys are rows 0 .. L-1 of the sequence (1 <= L <= T, uniform over the workgroup) -- L takes T's place
 // in the tile count, in the loader's clamp and in the mask of the last tile, so no K or V row >= L is read; T keeps the
 // row strides and the query count.  Without KEYLEN the key count IS T (L is not looked at): K9 and K9L as they were.
-template <bool KEYLEN>
+// CAUSAL (K9A): query q sees keys 0 .. q.  The loader stages every tile as always; compute wave w walks tiles
+// 0 .. (q0 / 32) + w, masks the keys above each lane's query in the last of them, and idles through the pair barriers left.
+template <bool KEYLEN, bool CAUSAL = false>
 __device__ __forceinline__ void attn_block(const float* __restrict__ qkv, int T, int H, int64_t b, int h, int q0, int ncw,
                                            int L, float* __restrict__ out) {
     __shared__ __attribute__((aligned(1024))) char at_lds[AT_NSTAGE * AT_STAGE];   // [stage][K | V][32 rows x 256 B]
@@ -149,7 +159,9 @@ __device__ __forceinline__ void attn_block(const float* __restrict__ qkv, int T,
         for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
     float m = -INFINITY, l = 0.f;
 
-    for (int kt = 0; kt < ntile; ++kt) {
+    // CAUSAL: the diagonal tile is this wave's last (it exists: wave < ncw and q0 + 32 * wave < T for every launched wave)
+    const int ntile_w = CAUSAL ? min(ntile, (q0 >> 5) + wave + 1) : ntile;
+    for (int kt = 0; kt < ntile_w; ++kt) {
         if ((kt & 1) == 0) __builtin_amdgcn_s_barrier();   // the loader says tiles kt and kt+1 are in LDS
         asm volatile("" ::: "memory");
         const char* kb = at_lds + (kt % AT_NSTAGE) * AT_STAGE;
@@ -173,11 +185,22 @@ __device__ __forceinline__ void attn_block(const float* __restrict__ qkv, int T,
             c = __builtin_amdgcn_mfma_f32_32x32x2f32(ka.z, Qr[4 * j + 2], c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_32x32x2f32(ka.w, Qr[4 * j + 3], c, 0, 0, 0);
         }
-        const int nk = TK - kt * 32;   // valid keys in this tile (>= 1)
-        if (nk < 32) {
+        if constexpr (CAUSAL) {
+            // the diagonal tile: key 32 kt + j is above query 32 kt + ql when j > ql.  That covers the keys past T of a
+            // short last tile (a stored row has q < T <= key), so K9's mask is not needed beside it; key 32 kt itself is
+            // never masked and the running maximum stays finite.
+            if (kt == ntile_w - 1) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r)
-                if ((r & 3) + 8 * (r >> 2) + 4 * half >= nk) c[r] = -INFINITY;
+                for (int r = 0; r < 16; ++r)
+                    if ((r & 3) + 8 * (r >> 2) + 4 * half > ql) c[r] = -INFINITY;
+            }
+        } else {
+            const int nk = TK - kt * 32;   // valid keys in this tile (>= 1)
+            if (nk < 32) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if ((r & 3) + 8 * (r >> 2) + 4 * half >= nk) c[r] = -INFINITY;
+            }
         }
         float mt = c[0];
 #pragma unroll
@@ -231,6 +254,11 @@ __device__ __forceinline__ void attn_block(const float* __restrict__ qkv, int T,
                 *reinterpret_cast<float4*>(dst + 32 * i + 8 * g) = t;
             }
     }
+    if constexpr (CAUSAL) {
+        // the pair barriers of the tiles above the diagonal: a second, empty loop -- the loader counts on every wave at
+        // every barrier, and a branch around the tile loop's body would cost what the comment on pv_step says
+        for (int kt = (ntile_w + 1) & ~1; kt < ntile; kt += 2) __builtin_amdgcn_s_barrier();
+    }
 }
 
 // K9: one workgroup per (image, head), one compute wave per 32 queries (T <= 256) + the loader.
@@ -254,6 +282,15 @@ __global__ __launch_bounds__(576, 4) void vit_attention_keylen_kernel(const floa
     int L = T;
     if (lens) L = min(max(lens[b], 1), T);
     attn_block<true>(qkv, T, H, b, h, 0, ncw, __builtin_amdgcn_readfirstlane(L), out);
+}
+
+// K9A: K9's grid and waves under the causal mask.
+__global__ __launch_bounds__(576, 4) void vit_attention_causal_kernel(const float* __restrict__ qkv, int T, int H,
+                                                                       float* __restrict__ out) {
+    const int ntile = (T + 31) >> 5;
+    const int h = blockIdx.x;
+    const int64_t b = blockIdx.y;
+    attn_block<false, true>(qkv, T, H, b, h, 0, ntile, T, out);
 }
 
 // K9L, the long form: one workgroup per (image, head, block of 32 * ncw queries), ncw = min(8, ceil(T / 32)).  Every
@@ -417,6 +454,23 @@ extern "C" int mcd_vit_attention_keylen(const float* qkv, int64_t B, int64_t T, 
     hipLaunchKernelGGL(vit_attention_keylen_kernel, dim3((unsigned)H, (unsigned)B), dim3(64 * nwaves), 0, (hipStream_t)stream,
                        qkv, (int)T, (int)H, lens, out);
     MCD_LAUNCH_CHECK("vit_attention_keylen_kernel");
+    return MCD_OK;
+}
+
+extern "C" int mcd_vit_attention_causal(const float* qkv, int64_t B, int64_t T, int64_t H, float* out, mcd_stream_t stream) {
+    MCD_REQUIRE(qkv && out, MCD_E_ARG, "mcd_vit_attention_causal: NULL pointer");
+    MCD_REQUIRE(B >= 0 && T >= 1 && H >= 1, MCD_E_ARG, "mcd_vit_attention_causal: bad shape B=%lld T=%lld H=%lld", (long long)B,
+                (long long)T, (long long)H);
+    MCD_REQUIRE(T <= AT_MAX_T, MCD_E_UNSUPPORTED,
+                "mcd_vit_attention_causal: T=%lld tokens, at most %d (one wave per 32 queries, 8 waves)", (long long)T, AT_MAX_T);
+    MCD_REQUIRE(B <= 65535 && H <= 65535, MCD_E_UNSUPPORTED, "mcd_vit_attention_causal: B and H must be <= 65535");
+    MCD_REQUIRE(((uintptr_t)qkv) % 16 == 0 && ((uintptr_t)out) % 16 == 0, MCD_E_ARG,
+                "mcd_vit_attention_causal: qkv and out must be 16-byte aligned");
+    if (B == 0) return MCD_OK;
+    const int nwaves = (int)((T + 31) / 32) + 1;   // one per 32 queries + the loader
+    hipLaunchKernelGGL(vit_attention_causal_kernel, dim3((unsigned)H, (unsigned)B), dim3(64 * nwaves), 0, (hipStream_t)stream,
+                       qkv, (int)T, (int)H, out);
+    MCD_LAUNCH_CHECK("vit_attention_causal_kernel");
     return MCD_OK;
 }
 
