@@ -21,6 +21,7 @@ dissection core they feed is the HIP library.
     vit / -cub / -bloodmnist   vit.encoder.layer[0..11]                HF ViT-B/16 classifier: 12 x 768
     dino / -cub / -bloodmnist  dinov2.encoder.layer[0..11]             HF DINOv2-base classifier (patch 14): 12 x 768
 """
+import collections
 import math
 import os
 import unicodedata
@@ -132,7 +133,7 @@ def _fused_residual_ok(x):
 # ViT-B/16 tower (module names follow HF ViTModel: embeddings / encoder.layer[i] / layernorm)
 # ------------------------------------------------------------------------------------------------------
 def attention_route(T, D, heads, masked, on_gpu, dtype, needs_grad):
-    """Which attention _Attention.heads_out takes for T tokens of width D = 64 * heads: 'k9' (T <= 256), 'long' (K9L,
+    """Which attention a _Block takes for T tokens of width D = 64 * heads: 'k9' (T <= 256), 'long' (K9L,
     up to core.VIT_ATTENTION_LONG_MAX_T tokens and one image's qkv under 2^31 bytes) or 'sdpa' (masked, autograd,
     non-fp32 or off-GPU calls, HIP_ATTENTION off, other head widths, and anything past K9L's limits)."""
     if not (HIP_ATTENTION and not masked and _hip_eligible(on_gpu, dtype, needs_grad) and D == 64 * heads):
@@ -167,6 +168,120 @@ def _token0_hooks(m):
     return all(getattr(h, "token0_only", False) for h in m._forward_hooks.values())
 
 
+def _cls_tail_ok(x, blocks, container, clear=(), token0=()):
+    """cls_tail_route for the embedded tokens x [B, T, D] in front of `blocks`, the ModuleList inside `container`, and the
+    hooks the tower carries right now.  clear: further modules that must carry no hook, nor hold one inside (the ViT's
+    final LayerNorm); token0: the modules beside the last block whose forward hooks must declare token0_only (the ViT
+    tower, whose output is the pruned tensor; none for CLIP, whose forward slices the class-token row itself)."""
+    if not (CLS_ONLY_TAIL and isinstance(x, torch.Tensor) and x.dim() == 3) or len(blocks) == 0:
+        return False
+    last = blocks[-1]
+    hooks_clear = not (_nn_module._global_forward_hooks or _nn_module._global_forward_pre_hooks or last._forward_pre_hooks
+                       or any(_hooked(c) for c in last.children()) or any(_hooked(m) for m in clear)
+                       or container._forward_hooks or container._forward_pre_hooks)
+    return cls_tail_route(CLS_ONLY_TAIL, _fused_residual_ok(x), False, container.training or last.training, x.shape[1],
+                          x.shape[2], last.attn.heads, len(blocks), hooks_clear, all(_token0_hooks(m) for m in (last,) + token0))
+
+
+def _class_pos_residual(pos, cls, bias, B):
+    """[B, T, D]: the residual operand of the patch embedding written as K11 + one GEMM -- the position table pos [T, D]
+    for every image, with cls [D] + its row 0 - bias in row 0 (the class-token slot, a zero row of K11's; the GEMM adds the
+    bias back).  bias None: a convolution without one."""
+    r = pos.detach().expand(B, -1, -1).contiguous()
+    r[:, 0] = cls.detach() + pos.detach()[0] if bias is None else cls.detach() + pos.detach()[0] - bias.detach()
+    return r
+
+
+def _attend(qkv, heads, choice, arg=None):
+    """The concatenated head outputs [B, T, D] of the fused projection's output qkv [B, T, 3 D] -- attention before the
+    output projection -- on the kernel `choice` names: 'k9' (K9), 'long' (K9L: one workgroup per 256 queries of a head, no
+    T x T buffer), 'causal' (K9A), 'keylen' (K9M, arg: the int32 [B] key counts or None) or 'sdpa' (PyTorch's, arg: the
+    mask or None).  The HIP kernels (csrc/k_attn.hip) read the projection's layout and write the proj input's."""
+    B, T, D = qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3
+    if choice == "k9":
+        global _attention_calls
+        _attention_calls += 1
+        timed = ATTENTION_EVENTS is not None and _attention_calls % 8 == 0
+        if timed:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        o = core.vit_attention(qkv, heads)
+        if timed:
+            e1.record()
+            ATTENTION_EVENTS.append((e0, e1, B, T, heads))
+        return o
+    if choice == "long":
+        return core.vit_attention_long(qkv, heads)
+    if choice == "causal":
+        return core.vit_attention_causal(qkv, heads)
+    if choice == "keylen":
+        return core.vit_attention_keylen(qkv, heads, arg)
+    q, k, v = qkv.view(B, T, 3, heads, D // heads).permute(2, 0, 3, 1, 4)
+    o = F.scaled_dot_product_attention(q, k, v, attn_mask=arg)
+    return o.transpose(1, 2).reshape(B, T, D)
+
+
+def _attend_cls(q, kv):
+    """K9C: one query row per image, q [B, D], against the keys and values of kv [B, T, 2, heads, 64] -> [B, D]."""
+    return core.vit_attention_cls(q, kv[:, :, 0], kv[:, :, 1])
+
+
+# The operands of one transformer block on the HIP route (_block_hip): ln1 / ln2 as (weight, bias, eps), qkv / proj / fc1 /
+# fc2 as (weight, bias), the head count.  Each block class builds it from its own parameters (its _ops()).
+_BlockOps = collections.namedtuple("_BlockOps", "ln1 ln2 qkv proj fc1 fc2 heads")
+
+
+def _ln_ops(ln):
+    return ln.weight, ln.bias, ln.eps
+
+
+def _lin_ops(lin):
+    return lin.weight, lin.bias
+
+
+def _norm(x, ln, k10=True):
+    return core.layer_norm(x, *ln) if k10 else F.layer_norm(x, x.shape[-1:], *ln)                # K10, or ATen's
+
+
+def _gelu(h):
+    return F.gelu(h)                                                                              # erf GELU, ATen's
+
+
+def _quick_gelu_(h):
+    return core.quick_gelu(h, out=h)                                                              # K25, in place
+
+
+def _block_hip(p, x, attn, attn_arg=None, post=False, act=_gelu, cls_only=False, k10=True):
+    """One transformer block [B, T, D] -> [B, T, D] on the HIP route, from the operands p (a _BlockOps): the fused qkv
+    GEMM, the attention `attn` (_attend's choice, with attn_arg), the two residual GEMMs, `act` behind fc1.
+    Pre-norm (ViT, CLIP):    x1 = x + proj(attention(ln1(x))),    out = x1 + fc2(act(fc1(ln2(x1)))).
+    post=True (BERT):        x1 = ln1(x + proj(attention(x))),    out = ln2(x1 + fc2(act(fc1(x1)))).
+    x1 is a new tensor (the block's input is left alone); a pre-norm block's second update is in place on x1.  k10=False
+    keeps ATen's LayerNorm (_Block under HIP_LAYER_NORM).
+    cls_only (pre-norm; the caller has checked cls_tail_route): the class-token row of the same block, as [B, 1, D].  K and
+    V need every token -- ln1 and the K|V two thirds of the qkv projection run on all rows -- everything after them is
+    computed for row 0 of each image only.  The weight slices are contiguous views, x[:, 0] and ln1(x)[:, 0] go into the
+    GEMMs as row-strided operands: no copies."""
+    B, T, D = x.shape
+    x = x.contiguous()
+    n = x if post else _norm(x, p.ln1, k10)
+    w, b = p.qkv
+    if cls_only:
+        kv = core.linear_residual(None, n, w[D:], None if b is None else b[D:]).view(B, T, 2, p.heads, D // p.heads)
+        o = _attend_cls(core.linear_residual(None, n[:, 0], w[:D], None if b is None else b[:D]), kv)
+        x = x[:, 0]
+    else:
+        o = _attend(core.linear_residual(None, n, w, b), p.heads, attn, attn_arg).contiguous()
+    x1 = core.linear_residual(x, o, *p.proj)
+    if post:
+        x1 = _norm(x1, p.ln1, k10)
+    h = act(core.linear_residual(None, x1 if post else _norm(x1, p.ln2, k10), *p.fc1))
+    if post:
+        return _norm(core.linear_residual(x1, h, *p.fc2), p.ln2, k10)
+    out = core.linear_residual(x1, h, *p.fc2, out=x1)
+    return out.unsqueeze(1) if cls_only else out
+
+
 class _Attention(nn.Module):
     def __init__(self, dim, heads):
         super().__init__()
@@ -179,28 +294,10 @@ class _Attention(nn.Module):
 
     def heads_out(self, x, mask=None):
         """The concatenated head outputs [B, T, D], i.e. attention before the output projection."""
-        B, T, D = x.shape
-        qkv = _linear(self.qkv, x)
-        route = attention_route(T, D, self.heads, mask is not None, qkv.is_cuda, qkv.dtype,
+        qkv = self.qkv(x)
+        route = attention_route(x.shape[1], x.shape[2], self.heads, mask is not None, qkv.is_cuda, qkv.dtype,
                                 torch.is_grad_enabled() and qkv.requires_grad)
-        if route == "k9":
-            # K9 (csrc/k_attn.hip): one launch, reads the fused projection's layout, writes the proj input's
-            global _attention_calls
-            _attention_calls += 1
-            if ATTENTION_EVENTS is not None and _attention_calls % 8 == 0:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                o = core.vit_attention(qkv, self.heads)
-                e1.record()
-                ATTENTION_EVENTS.append((e0, e1, B, T, self.heads))
-                return o
-            return core.vit_attention(qkv, self.heads)
-        if route == "long":
-            # K9L (csrc/k_attn.hip): the same layouts, one workgroup per 256 queries of a head, no T x T buffer
-            return core.vit_attention_long(qkv, self.heads)
-        q, k, v = qkv.view(B, T, 3, self.heads, D // self.heads).permute(2, 0, 3, 1, 4)
-        o = F.scaled_dot_product_attention(q, k, v, attn_mask=mask)
-        return o.transpose(1, 2).reshape(B, T, D)
+        return _attend(qkv, self.heads, route, mask)
 
 
 class _LayerScale(nn.Module):
@@ -212,6 +309,9 @@ class _LayerScale(nn.Module):
 
     def forward(self, x):
         return x * self.lambda1
+
+
+_BLOCK_SKIPPED = ("norm1", "attn", "norm2", "fc1", "fc2", "layer_scale1", "layer_scale2")
 
 
 class _Block(nn.Module):
@@ -232,20 +332,23 @@ class _Block(nn.Module):
             self.layer_scale2 = _LayerScale(dim, layer_scale)
 
     def forward(self, x, mask=None, cls_only=False):
-        if cls_only and mask is None:      # a masked call keeps the full block whatever the caller asked for
-            return self._forward_cls(x)
-        if _fused_residual_ok(x):
-            x = x.contiguous()
-            wp, bp, w2, b2 = self._residual_weights()
-            # x1 is a new tensor (the block's input is left alone); the second update is in place on x1
-            x1 = core.linear_residual(x, self.attn.heads_out(self.norm1(x), mask).contiguous(), wp, bp)
-            h = F.gelu(_linear(self.fc1, self.norm2(x1)))
-            return core.linear_residual(x1, h, w2, b2, out=x1)
+        cls_only = cls_only and mask is None      # a masked call keeps the full block whatever the caller asked for
+        if cls_only or (_fused_residual_ok(x) and not _hooks_on(self, _BLOCK_SKIPPED)):
+            B, T, D = x.shape
+            route = attention_route(T, D, self.attn.heads, mask is not None, x.is_cuda, x.dtype, False)
+            return _block_hip(self._ops(), x, route, mask, cls_only=cls_only, k10=HIP_LAYER_NORM and D % 4 == 0 and D <= 2048)
+        # ATen, also for a block with a hook inside (or under a global one): every submodule through __call__, so that
+        # the hook fires, once, with the module's own output
         if self.scaled:
             x = x + self.layer_scale1(self.attn(self.norm1(x), mask))
             return x + self.layer_scale2(self.fc2(F.gelu(self.fc1(self.norm2(x)))))
         x = x + self.attn(self.norm1(x), mask)
         return x + self.fc2(F.gelu(self.fc1(self.norm2(x))))
+
+    def _ops(self):
+        wp, bp, w2, b2 = self._residual_weights()
+        return _BlockOps(_ln_ops(self.norm1), _ln_ops(self.norm2), _lin_ops(self.attn.qkv), (wp, bp), _lin_ops(self.fc1),
+                         (w2, b2), self.attn.heads)
 
     def _residual_weights(self):
         """(proj weight, proj bias, fc2 weight, fc2 bias) of the two fused residual GEMMs.  With LayerScale,
@@ -261,24 +364,6 @@ class _Block(nn.Module):
             return ((l1[:, None] * m.attn.proj.weight.detach()).contiguous(), (l1 * m.attn.proj.bias.detach()).contiguous(),
                     (l2[:, None] * m.fc2.weight.detach()).contiguous(), (l2 * m.fc2.bias.detach()).contiguous())
         return _folded(self, ("layer_scale1", "layer_scale2", "attn", "fc2"), build)
-
-    def _forward_cls(self, x):
-        """The class-token row of forward(x), as [B, 1, D] (the caller has checked cls_tail_route): K and V need every
-        token -- norm1 and the K|V two thirds of the qkv projection run on all rows -- everything after them is computed
-        for row 0 of each image only.  The weight slices are contiguous views, x[:, 0] and norm1(x)[:, 0] go into the
-        GEMMs as row-strided operands: no copies."""
-        B, T, D = x.shape
-        a = self.attn
-        x = x.contiguous()
-        n = self.norm1(x)
-        w, b = a.qkv.weight, a.qkv.bias
-        kv = core.linear_residual(None, n, w[D:], None if b is None else b[D:]).view(B, T, 2, a.heads, D // a.heads)
-        q = core.linear_residual(None, n[:, 0], w[:D], None if b is None else b[:D])
-        o = core.vit_attention_cls(q, kv[:, :, 0], kv[:, :, 1])                          # K9C
-        wp, bp, w2, b2 = self._residual_weights()
-        x1 = core.linear_residual(x[:, 0], o, wp, bp)                                    # [B, D], a new tensor
-        h = F.gelu(core.linear_residual(None, self.norm2(x1), self.fc1.weight, self.fc1.bias))
-        return core.linear_residual(x1, h, w2, b2, out=x1).unsqueeze(1)
 
 
 class _Encoder(nn.Module):
@@ -351,18 +436,8 @@ class ViTTower(nn.Module):
 
     def _cls_tail_ok(self, x):
         """cls_tail_route for the embedded tokens x [B, T, D] and the hooks this tower carries right now."""
-        if not (CLS_ONLY_TAIL and isinstance(x, torch.Tensor) and x.dim() == 3):
-            return False
         enc = self.encoder
-        blocks = getattr(enc, enc._list_name)
-        if len(blocks) == 0:
-            return False
-        last = blocks[-1]
-        clear = not (_nn_module._global_forward_hooks or _nn_module._global_forward_pre_hooks or last._forward_pre_hooks
-                     or any(_hooked(c) for c in last.children()) or _hooked(self.layernorm)
-                     or enc._forward_hooks or enc._forward_pre_hooks)
-        return cls_tail_route(CLS_ONLY_TAIL, _fused_residual_ok(x), False, self.training or last.training, x.shape[1],
-                              x.shape[2], last.attn.heads, len(blocks), clear, _token0_hooks(last) and _token0_hooks(self))
+        return _cls_tail_ok(x, getattr(enc, enc._list_name), enc, clear=(self.layernorm,), token0=(self,))
 
     def embed(self, x):
         """Patch embedding + class token + position embedding -> [B, 1 + n, dim]."""
@@ -382,12 +457,8 @@ class ViTTower(nn.Module):
     def _embed_residual(self, B, H, W):
         """[B, 1 + n, dim]: the position table of an H x W image (pos_table), with cls_token + its row 0 - bias in row 0
         (the GEMM adds the bias back)."""
-        def build(m):
-            pos = m.pos_table(H, W).detach()
-            r = pos.expand(B, -1, -1).contiguous()
-            r[:, 0] = m.cls_token.detach()[0, 0] + pos[0, 0] - m.patch_embed.bias.detach()
-            return r
-        return _folded(self, ("pos_embed", "cls_token", "patch_embed"), build, extra=(B, H, W))
+        return _folded(self, ("pos_embed", "cls_token", "patch_embed"), lambda m: _class_pos_residual(
+            m.pos_table(H, W)[0], m.cls_token[0, 0], m.patch_embed.bias, B), extra=(B, H, W))
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -478,7 +549,7 @@ def _hooks_on(module, names):
     ResNet downsample's convolution, say): the HIP route calls none of them."""
     if _nn_module._global_forward_hooks or _nn_module._global_forward_pre_hooks:
         return True
-    return any(m is not None and _hooked(m) for m in (getattr(module, n, None) for n in names))
+    return any(m is not None and _hooked(m) for m in map(module._modules.get, names))
 
 
 def mbconv_route(module, x):
@@ -792,19 +863,14 @@ class _BertLayer(nn.Module):
         """mask: None or the bool [B, 1, 1, T] key mask for SDPA; hip (the tower has checked text_route and the mask):
         the HIP route with lens (int32 [B] key counts, None = all T) -- unless a hook sits inside this layer."""
         if hip and not _hooks_on(self, _BERT_LAYER_SKIPPED):
-            return self._forward_hip(x, lens)
+            return _block_hip(self._ops(), x, "keylen", lens, post=True)                                   # K9M
         x1 = self.attention(x, mask)
         return self.output(self.intermediate(x1), x1)
 
-    def _forward_hip(self, x, lens):
+    def _ops(self):
         s, so, o = getattr(self.attention, "self"), self.attention.output, self.output
-        wqkv, bqkv = s.fused_qkv()
-        a = core.vit_attention_keylen(core.linear_residual(None, x, wqkv, bqkv), s.heads, lens)            # K9M
-        x1 = core.layer_norm(core.linear_residual(x, a, so.dense.weight, so.dense.bias), so.LayerNorm.weight,
-                             so.LayerNorm.bias, so.LayerNorm.eps)                                          # K10
-        h = F.gelu(core.linear_residual(None, x1, self.intermediate.dense.weight, self.intermediate.dense.bias))
-        return core.layer_norm(core.linear_residual(x1, h, o.dense.weight, o.dense.bias), o.LayerNorm.weight,
-                               o.LayerNorm.bias, o.LayerNorm.eps)
+        return _BlockOps(_ln_ops(so.LayerNorm), _ln_ops(o.LayerNorm), s.fused_qkv(), _lin_ops(so.dense),
+                         _lin_ops(self.intermediate.dense), _lin_ops(o.dense), s.heads)
 
 
 class _BertEncoder(nn.Module):
@@ -1670,8 +1736,7 @@ class AttentionPool2d(nn.Module):
         tok = core.attnpool_tokens(x.permute(0, 2, 3, 1), self.positional_embedding.detach())      # [B, T, C]
         kv = core.linear_residual(None, tok, wkv, bkv).view(B, tok.shape[1], 2, self.num_heads, 64)
         q = core.linear_residual(None, tok[:, 0], self.q_proj.weight, self.q_proj.bias)
-        o = core.vit_attention_cls(q, kv[:, :, 0], kv[:, :, 1])                                     # K9C
-        return core.linear_residual(None, o, self.c_proj.weight, self.c_proj.bias)
+        return core.linear_residual(None, _attend_cls(q, kv), self.c_proj.weight, self.c_proj.bias)      # K9C, c_proj
 
     def _fold(self):
         return (torch.cat([self.k_proj.weight.detach(), self.v_proj.weight.detach()]).contiguous(),
@@ -1828,42 +1893,15 @@ class _ClipResBlock(nn.Module):
         """hip: the tower has checked clip_tower_route; the block takes the HIP route unless a hook sits inside it.
         cls_only (the tower has checked cls_tail_route as well): the class-token row alone, as [B, 1, D]."""
         if hip and not _hooks_on(self, _CLIP_BLOCK_SKIPPED):
-            return self._forward_cls(x) if cls_only else self._forward_hip(x)
+            attn = "causal" if self.causal else "k9" if x.shape[1] <= core.VIT_ATTENTION_MAX_T else "long"   # K9A, K9, K9L
+            return _block_hip(self._ops(), x, attn, act=_quick_gelu_, cls_only=cls_only)
         x = x + self.attn(self.ln_1(x), self.causal)
         return x + self.mlp(self.ln_2(x))
 
-    def _ln(self, ln, x):
-        return core.layer_norm(x, ln.weight, ln.bias, ln.eps)                                           # K10
-
-    def _forward_hip(self, x):
+    def _ops(self):
         a, m = self.attn, self.mlp
-        x = x.contiguous()
-        qkv = core.linear_residual(None, self._ln(self.ln_1, x), a.in_proj_weight, a.in_proj_bias)
-        if self.causal:
-            o = core.vit_attention_causal(qkv, a.heads)                                                 # K9A
-        elif x.shape[1] <= core.VIT_ATTENTION_MAX_T:
-            o = core.vit_attention(qkv, a.heads)                                                        # K9
-        else:
-            o = core.vit_attention_long(qkv, a.heads)                                                   # K9L
-        x1 = core.linear_residual(x, o, a.out_proj.weight, a.out_proj.bias)       # a new tensor: the input is left alone
-        h = core.linear_residual(None, self._ln(self.ln_2, x1), m.c_fc.weight, m.c_fc.bias)
-        core.quick_gelu(h, out=h)                                                                       # K25, in place
-        return core.linear_residual(x1, h, m.c_proj.weight, m.c_proj.bias, out=x1)
-
-    def _forward_cls(self, x):
-        """_Block._forward_cls with this block's parameters: K and V for every token, the rest for row 0 alone."""
-        B, T, D = x.shape
-        a, m = self.attn, self.mlp
-        x = x.contiguous()
-        n = self._ln(self.ln_1, x)
-        w, b = a.in_proj_weight, a.in_proj_bias
-        kv = core.linear_residual(None, n, w[D:], b[D:]).view(B, T, 2, a.heads, D // a.heads)
-        q = core.linear_residual(None, n[:, 0], w[:D], b[:D])
-        o = core.vit_attention_cls(q, kv[:, :, 0], kv[:, :, 1])                                         # K9C
-        x1 = core.linear_residual(x[:, 0], o, a.out_proj.weight, a.out_proj.bias)                       # [B, D], a new tensor
-        h = core.linear_residual(None, self._ln(self.ln_2, x1), m.c_fc.weight, m.c_fc.bias)
-        core.quick_gelu(h, out=h)
-        return core.linear_residual(x1, h, m.c_proj.weight, m.c_proj.bias, out=x1).unsqueeze(1)
+        return _BlockOps(_ln_ops(self.ln_1), _ln_ops(self.ln_2), (a.in_proj_weight, a.in_proj_bias), _lin_ops(a.out_proj),
+                         _lin_ops(m.c_fc), _lin_ops(m.c_proj), a.heads)
 
 
 class _ClipTransformer(nn.Module):
@@ -1924,31 +1962,16 @@ class _ClipVisionTransformer(nn.Module):
             t = self.ln_pre(t)
         else:
             t = core.layer_norm(t, self.ln_pre.weight, self.ln_pre.bias, self.ln_pre.eps)               # K10
-        t = self.transformer(t, True, self._cls_tail_ok(t))
+        # nothing reads any row of the last block but the class token's: this forward slices it, the package's hooks declare it
+        t = self.transformer(t, True, _cls_tail_ok(t, self.transformer.resblocks, self.transformer))
         row = t[:, 0].contiguous()
         if _hooked(self.ln_post):
             return self.ln_post(row) @ self.proj
         return core.layer_norm(row, self.ln_post.weight, self.ln_post.bias, self.ln_post.eps) @ self.proj
 
     def _embed_residual(self, B):
-        def build(m):
-            r = m.positional_embedding.detach().expand(B, -1, -1).contiguous()
-            r[:, 0] += m.class_embedding.detach()
-            return r
-        return _folded(self, ("positional_embedding", "class_embedding"), build, extra=(B,))
-
-    def _cls_tail_ok(self, t):
-        """cls_tail_route for the embedded tokens t [B, T, D] and the hooks this tower carries right now: nothing reads
-        any row of the last block but the class token's (forward slices it; the package's hooks declare token0_only)."""
-        blocks = self.transformer.resblocks
-        if len(blocks) == 0:
-            return False
-        last = blocks[-1]
-        clear = not (_nn_module._global_forward_hooks or _nn_module._global_forward_pre_hooks or last._forward_pre_hooks
-                     or any(_hooked(c) for c in last.children())
-                     or self.transformer._forward_hooks or self.transformer._forward_pre_hooks)
-        return cls_tail_route(CLS_ONLY_TAIL, _fused_residual_ok(t), False, self.training or last.training, t.shape[1],
-                              t.shape[2], last.attn.heads, len(blocks), clear, _token0_hooks(last))
+        return _folded(self, ("positional_embedding", "class_embedding"), lambda m: _class_pos_residual(
+            m.positional_embedding, m.class_embedding, None, B), extra=(B,))
 
 
 def openai_clip_config(sd):

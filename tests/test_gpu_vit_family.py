@@ -158,6 +158,52 @@ def test_dinov2_block_against_float64(du, core, dev, monkeypatch, T):
         assert _nerr(blk(xg), ref) > 1e-3
 
 
+def test_hook_inside_a_block_fires_and_the_other_block_stays_on_hip(du, core, dev, monkeypatch):
+    """--target_layers may name any module path.  A forward hook on encoder.layer[0].attn.proj, .attn.qkv or .fc1 of a
+    two-block tower (dim 128, 2 heads, 32 x 32 images at patch 16: 5 tokens): block 0 calls its modules, so the hook fires
+    once with that module's output; block 1 keeps the HIP route (its four GEMMs on top of the embedding's, its K9 launch);
+    the tower's output stays within the bound of the unhooked one; with the hook removed the counts are the plain ones."""
+    g = torch.Generator().manual_seed(11)
+    tower = du.ViTTower(image_size=32, patch=16, dim=128, depth=2, heads=2, mlp=512).eval()
+    with torch.no_grad():
+        for p in tower.parameters():
+            p.copy_(torch.randn(p.shape, generator=g) / max(1, p.shape[-1]) ** 0.5)
+        for m in tower.modules():
+            if isinstance(m, torch.nn.LayerNorm):
+                m.weight.copy_(1 + 0.2 * torch.randn(128, generator=g))
+        x = torch.randn(2, 3, 32, 32, generator=g)
+        ref = tower.double()(x.double())
+        tower.float().to(dev)
+        xg = x.to(dev)
+        cnt = _counter(core, monkeypatch)
+        for f in ATEN_FLAGS:
+            monkeypatch.setattr(du, f, False)
+        aten = tower(xg)
+        assert cnt.n == {}
+        for f in ATEN_FLAGS:
+            monkeypatch.setattr(du, f, True)
+        plain = {"patchify": 1, "layer_norm": 5, "vit_attention": 2, "linear_residual": 1 + 2 * 4}
+        got = tower(xg)
+        assert cnt.n == plain, cnt.n
+        _bound(_nerr(got, ref), _nerr(aten, ref), "two-block tower")
+        for name, width in (("attn.proj", 128), ("attn.qkv", 384), ("fc1", 512)):
+            seen = []
+            h = tower.encoder.layer[0].get_submodule(name).register_forward_hook(lambda m, i, o: seen.append(tuple(o.shape)))
+            cnt.n.clear()
+            try:
+                hooked = tower(xg)
+            finally:
+                h.remove()
+            assert seen == [(2, 5, width)], (name, seen)
+            # block 0 on its modules -- its two _LayerNorms and its _Attention still pick K10 and K9 for themselves, as
+            # with FUSED_RESIDUAL off -- and no GEMM of the fused route; block 1 on the HIP route: K9 and four GEMMs
+            assert cnt.n == dict(plain, linear_residual=1 + 4), (name, cnt.n)
+            _bound(_nerr(hooked, ref), _nerr(aten, ref), "two-block tower, a hook on layer[0].%s" % name)
+            cnt.n.clear()
+            assert torch.equal(tower(xg), got) and cnt.n == plain, (name, cnt.n)
+    assert torch.equal(xg.cpu(), x)
+
+
 # ---- 4. the small towers against transformers' output -----------------------------------------------------------------------
 def _expected_calls(case, depth=2):
     T = 1 + (recipe.CASES[case][1] // 14) * (recipe.CASES[case][2] // 14) if case != "vit" else 17
