@@ -69,6 +69,10 @@ CLIP_SIGNATURES = {
     "mcd_vit_attention_causal": (_int, [_p, _i64, _i64, _i64, _p, _p]),
     "mcd_quick_gelu": (_int, [_p, _i64, _p, _p]),
 }
+# the token-reduction entry of the same library, declared in include/mcd_tokens.h (additive to ABI version 9)
+TOKEN_SIGNATURES = {
+    "mcd_token_mean": (_int, [_p, _int, _int, _int, _i64, _i64, _int, _p, _i64, _p]),
+}
 
 MCD_E_ARG = -1
 MCD_E_RANGE = -2
@@ -95,7 +99,8 @@ def load():
                 "mammo-clip-dissect_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; "
                 "g.build()'` or `make -C mammo-clip-dissect_amd/csrc`. There is no CPU fallback." % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(CLIP_SIGNATURES.items())
+                                  + list(TOKEN_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

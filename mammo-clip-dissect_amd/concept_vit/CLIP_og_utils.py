@@ -17,7 +17,13 @@ PM_SUFFIX = _u.PM_SUFFIX
 def save_activations(clip_name, target_name, target_layers, d_probe,
                      concept_set, batch_size, device, pool_mode, save_dir):
     clip_model, tokenize = _clip_dissector(device, clip_name)
-    target_model = clip_model if target_name == "clip" else data_utils.get_target_model(target_name, device)[0]
+    # a checkpoint registered for the target (data_utils.register_target_checkpoint) is what it is built from; `clip` with
+    # one is transformers' CLIPForImageClassification (data_utils.HFClip), without one the dissector itself
+    registered = data_utils.target_ckpt_or(target_name, None)
+    if target_name == "clip" and registered is None:
+        target_model = clip_model
+    else:
+        target_model = data_utils.get_target_model(target_name, device, ckpt=registered)[0]
     # reference :128-132: the dissector's copy of the probe set gets CLIP's transform, the target's copy its own
     data = _u._probe_data(d_probe, device, "clip" if target_name == "clip" else data_utils.target_preset(target_name), "clip")
     words = _u._read_concepts(concept_set)

@@ -12,7 +12,8 @@ dissection core they feed is the HIP library.
     breastclip             image_encoder._blocks[0..38]                EfficientNet-B5: 6992
     breastclip_vit         image_encoder.encoder.layer[0..11]          ViT-B/16: 12 x 768
     breastclip_classifier  image_encoder._blocks[0..38]                + linear head (n_class)
-    clip                   vision_model.encoder.layers[0..11]          CLIP ViT-B/16: 12 x 768
+    clip                   vision_model.encoder.layers[0..11]          CLIP ViT-B/16: 12 x 768 (with a checkpoint, ckpt= or
+                                                                       registered: HFClip = CLIPForImageClassification)
     resnet50 / 101 / 152   conv1, layer1..layer4                       64/256/512/1024/2048
     resnet18 / 34          conv1, layer1..layer4                       64/64/128/256/512
     resnet18_places        as resnet18, 365 classes (reference :70-79)
@@ -2309,6 +2310,299 @@ def openai_clip_state_dict(ckpt):
 
 
 # ------------------------------------------------------------------------------------------------------
+# The HF `clip` target: transformers' CLIPForImageClassification (the reference's MODELS["clip"] =
+# "openai/clip-vit-base-patch16" behind AutoModelForImageClassification, data_utils.py:21-36, :63-69) under its own names
+# ------------------------------------------------------------------------------------------------------
+# HFClip's inference route (clip_tower_route): K11 + one GEMM for the embedding, K10 for pre_layrnorm, per layer K10, the
+# fused qkv GEMM, K9 / K9L, the two residual GEMMs and K25 behind fc1, K26 for the mean of the patch tokens, one GEMM for the
+# classifier.  MCD_NO_HIP_HF_CLIP=1 (or setting this to False) keeps the ATen route of the same modules.
+HIP_HF_CLIP = os.environ.get("MCD_NO_HIP_HF_CLIP", "0") != "1"
+HF_CLIP_KEY = "vision_model.embeddings.class_embedding"      # what tells a CLIPForImageClassification state dict
+_HF_CLIP_LAYER_SKIPPED = ("self_attn", "layer_norm1", "mlp", "layer_norm2")
+# what a hub CLIPModel file carries beside the vision tower and from_pretrained drops for this class; older files store the
+# position_ids buffer
+_HF_CLIP_IGNORED = ("vision_model.embeddings.position_ids", "text_model.", "visual_projection.", "text_projection.",
+                    "logit_scale")
+
+
+class _HFClipEmbeddings(nn.Module):
+    """CLIPVisionEmbeddings: class_embedding [D], patch_embedding (a convolution WITHOUT bias), position_embedding (an
+    nn.Embedding of 1 + grid^2 rows).  No interpolation: an image of another patch grid is a ValueError."""
+
+    def __init__(self, dim, image_size, patch):
+        super().__init__()
+        self.image_size, self.patch_size = image_size, patch
+        self.class_embedding = nn.Parameter(torch.randn(dim))
+        self.patch_embedding = nn.Conv2d(3, dim, patch, patch, bias=False)
+        self.position_embedding = nn.Embedding((image_size // patch) ** 2 + 1, dim)
+
+    def check(self, x):
+        if x.dim() != 4 or tuple(x.shape[2:]) != (self.image_size, self.image_size):
+            raise ValueError("Input image size (%s) doesn't match model (%d*%d)."
+                             % ("*".join(str(s) for s in x.shape[2:]), self.image_size, self.image_size))
+
+    def forward(self, x):
+        self.check(x)
+        t = self.patch_embedding(x.to(self.patch_embedding.weight.dtype)).flatten(2).transpose(1, 2)
+        return torch.cat([self.class_embedding.expand(t.shape[0], 1, -1), t], dim=1) + self.position_embedding.weight
+
+
+class _HFClipAttention(nn.Module):
+    """CLIPAttention: k_proj, v_proj, q_proj, out_proj as four nn.Linear (each a hook point); forward is the ATen route."""
+
+    def __init__(self, dim, heads):
+        super().__init__()
+        self.heads = heads
+        self.k_proj = nn.Linear(dim, dim)
+        self.v_proj = nn.Linear(dim, dim)
+        self.q_proj = nn.Linear(dim, dim)
+        self.out_proj = nn.Linear(dim, dim)
+
+    def forward(self, x):
+        B, T, D = x.shape
+        q, k, v = (p(x).view(B, T, self.heads, D // self.heads).transpose(1, 2) for p in (self.q_proj, self.k_proj, self.v_proj))
+        return self.out_proj(F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(B, T, D))
+
+    def fused_qkv(self):
+        """([3D, D], [3D]): the three projections as the one GEMM the attention kernels read, cached until a parameter of
+        one of them is replaced or written."""
+        return _folded(self, ("q_proj", "k_proj", "v_proj"), lambda m: (
+            torch.cat([m.q_proj.weight, m.k_proj.weight, m.v_proj.weight]).contiguous(),
+            torch.cat([m.q_proj.bias, m.k_proj.bias, m.v_proj.bias]).contiguous()))
+
+
+class _HFClipMLP(nn.Module):
+    def __init__(self, dim, mlp, hidden_act):
+        super().__init__()
+        self.activation_fn = _QuickGELU() if hidden_act == "quick_gelu" else nn.GELU()
+        self.fc1 = nn.Linear(dim, mlp)
+        self.fc2 = nn.Linear(mlp, dim)
+
+    def forward(self, x):
+        return self.fc2(self.activation_fn(self.fc1(x)))
+
+
+class _HFClipLayer(nn.Module):
+    """CLIPEncoderLayer, pre-norm: x1 = x + self_attn(layer_norm1(x)), out = x1 + mlp(layer_norm2(x1)).  Returns the
+    hidden-state tensor."""
+
+    def __init__(self, dim, heads, mlp, hidden_act):
+        super().__init__()
+        self.self_attn = _HFClipAttention(dim, heads)
+        self.layer_norm1 = nn.LayerNorm(dim, eps=1e-5)
+        self.mlp = _HFClipMLP(dim, mlp, hidden_act)
+        self.layer_norm2 = nn.LayerNorm(dim, eps=1e-5)
+
+    def forward(self, x, hip=False):
+        """hip: the model has checked clip_tower_route; the layer takes the HIP route unless a hook sits inside it."""
+        if hip and not _hooks_on(self, _HF_CLIP_LAYER_SKIPPED):
+            attn = "k9" if x.shape[1] <= core.VIT_ATTENTION_MAX_T else "long"                     # K9, K9L
+            act = _quick_gelu_ if isinstance(self.mlp.activation_fn, _QuickGELU) else _gelu         # K25, or ATen's erf GELU
+            return _block_hip(self._ops(), x, attn, act=act)
+        x = x + self.self_attn(self.layer_norm1(x))
+        return x + self.mlp(self.layer_norm2(x))
+
+    def _ops(self):
+        a, m = self.self_attn, self.mlp
+        return _BlockOps(_ln_ops(self.layer_norm1), _ln_ops(self.layer_norm2), a.fused_qkv(), _lin_ops(a.out_proj),
+                         _lin_ops(m.fc1), _lin_ops(m.fc2), a.heads)
+
+
+class _HFClipEncoder(nn.Module):
+    def __init__(self, depth, dim, heads, mlp, hidden_act):
+        super().__init__()
+        self.layers = nn.ModuleList([_HFClipLayer(dim, heads, mlp, hidden_act) for _ in range(depth)])
+
+    def forward(self, x, hip=False):
+        for layer in self.layers:                    # through __call__: the hooks on layers[i] fire
+            x = layer(x, hip)
+        return x
+
+
+class _HFClipVisionTransformer(nn.Module):
+    """CLIPVisionTransformer: embeddings, pre_layrnorm (transformers' spelling), encoder, post_layernorm.  forward returns
+    last_hidden_state [B, T, D], which has NOT gone through post_layernorm.  transformers applies that module to the class
+    token for pooler_output, and CLIPForImageClassification discards the result; here it holds its parameters and is not
+    computed at all, so a hook on vision_model.post_layernorm fires in transformers and never here."""
+
+    def __init__(self, dim, image_size, patch, depth, heads, mlp, hidden_act):
+        super().__init__()
+        self.embeddings = _HFClipEmbeddings(dim, image_size, patch)
+        self.pre_layrnorm = nn.LayerNorm(dim, eps=1e-5)
+        self.encoder = _HFClipEncoder(depth, dim, heads, mlp, hidden_act)
+        self.post_layernorm = nn.LayerNorm(dim, eps=1e-5)
+
+    def forward(self, x, hip=False):
+        if not hip:
+            return self.encoder(self.pre_layrnorm(self.embeddings(x)))
+        emb, ln = self.embeddings, self.pre_layrnorm
+        unhooked = not (_nn_module._global_forward_hooks or _nn_module._global_forward_pre_hooks)
+        if unhooked and not _hooked(emb):
+            # K11 + one GEMM without a bias term, the position table with class_embedding + its row 0 as the residual operand
+            w = emb.patch_embedding.weight
+            t = core.linear_residual(self._embed_residual(x.shape[0]), core.patchify(x, emb.patch_size), w.view(w.shape[0], -1))
+        else:
+            t = emb(x)
+        t = core.layer_norm(t, ln.weight, ln.bias, ln.eps) if unhooked and not _hooked(ln) else ln(t)       # K10
+        return self.encoder(t, True)
+
+    def _embed_residual(self, B):
+        # (a copy of the table goes in: for B = 1 _class_pos_residual's expand(1, ..).contiguous() is a view of its operand,
+        # and row 0 is then written in place)
+        return _folded(self.embeddings, ("position_embedding", "class_embedding"), lambda m: _class_pos_residual(
+            m.position_embedding.weight.detach().clone(), m.class_embedding, None, B), extra=(B,))
+
+
+def hf_clip_config(sd, heads=None):
+    """HFClip's constructor arguments read from the shapes of a CLIPForImageClassification state dict: the width from
+    class_embedding, the patch from patch_embedding.weight, the grid (and with it the resolution) from the position rows,
+    the depth by counting layers, the MLP width from fc1, num_labels from classifier.weight when the file has one (else the
+    key is absent: the caller decides).  The state dict does not carry the head count: every OpenAI vision tower has
+    64-wide heads, so heads = width // 64 unless `heads` says otherwise."""
+    def shape(key):
+        if key not in sd:
+            raise RuntimeError("not a CLIPForImageClassification state dict: it lacks %r" % (key,))
+        return tuple(sd[key].shape)
+    hidden = shape(HF_CLIP_KEY)[0]
+    patch = shape("vision_model.embeddings.patch_embedding.weight")[2]
+    rows = shape("vision_model.embeddings.position_embedding.weight")[0]
+    grid = round((rows - 1) ** 0.5)
+    if grid * grid + 1 != rows:
+        raise RuntimeError("vision_model.embeddings.position_embedding.weight has %d rows: not a square grid plus one" % rows)
+    layers = len([k for k in sd if k.startswith("vision_model.encoder.layers.") and k.endswith(".self_attn.q_proj.weight")])
+    cfg = dict(image_size=grid * patch, patch=patch, hidden=hidden, layers=layers, heads=heads or hidden // 64,
+               mlp=shape("vision_model.encoder.layers.0.mlp.fc1.weight")[0] if layers else 4 * hidden)
+    if "classifier.weight" in sd:
+        cfg["num_labels"] = shape("classifier.weight")[0]
+    return cfg
+
+
+class HFClip(nn.Module):
+    """transformers' CLIPForImageClassification under transformers' own module and parameter names, so that a real state
+    dict loads strictly: vision_model.embeddings.{class_embedding, patch_embedding (no bias), position_embedding},
+    vision_model.pre_layrnorm, vision_model.encoder.layers[i].{layer_norm1, self_attn.{q,k,v,out}_proj, layer_norm2,
+    mlp.{fc1, fc2}}, vision_model.post_layernorm, classifier.  The defaults are openai/clip-vit-base-patch16's.
+
+    forward(images) -> the logits tensor [B, num_labels] (encode_image is the same call): the patch convolution, the class
+    embedding in front, + the position table, pre_layrnorm, the pre-norm layers (QuickGELU for hidden_act 'quick_gelu', erf
+    GELU for 'gelu'; LayerNorm eps 1e-5), then the mean of last_hidden_state[:, 1:] -- last_hidden_state does not pass
+    post_layernorm, whose parameters are loaded and whose result nothing reads (transformers computes it for pooler_output
+    and this class discards it; here it is not computed) -- and the classifier.
+    Hook points: vision_model.encoder.layers[i] and every module under it.  A layer returns its hidden-state tensor
+    [B, T, D]: so does transformers 5.x; transformers 4.41.1, the reference's pin, returns a 1-tuple, which the reference's
+    'avg' hook unwraps (utils.get_activation does the same), so both read the same rows.
+
+    The HIP route (HIP_HF_CLIP, clip_tower_route): K11 + one GEMM, K10, per layer _block_hip on the concatenated q / k / v
+    projection with K9 / K9L and K25, K26 for the mean, one GEMM for the classifier.  The head reads every token, so the
+    last layer always runs whole.  A layer with a hook on a module inside it runs its ATen modules for that call."""
+
+    def __init__(self, num_labels=2, image_size=224, patch=16, hidden=768, layers=12, heads=12, mlp=3072,
+                 hidden_act="quick_gelu"):
+        super().__init__()
+        if hidden_act not in ("quick_gelu", "gelu"):
+            raise ValueError("hidden_act must be 'quick_gelu' or 'gelu', got %r" % (hidden_act,))
+        if not isinstance(image_size, int):
+            raise ValueError("HFClip: image_size must be an int (the position table is a square grid), got %r" % (image_size,))
+        self.heads = heads
+        self.vision_model = _HFClipVisionTransformer(hidden, image_size, patch, layers, heads, mlp, hidden_act)
+        self.classifier = nn.Linear(hidden, num_labels)
+
+    @classmethod
+    def from_state_dict(cls, sd, n_class=None, heads=None, hidden_act="quick_gelu"):
+        """The model of a CLIPForImageClassification (or hub CLIPModel) state dict: sized by hf_clip_config, fp16 tensors
+        upcast, everything under vision_model. and classifier. loaded STRICTLY -- a missing or an unexpected key is an
+        error, never a tower of random weights.  The names of _HF_CLIP_IGNORED are dropped, as from_pretrained drops them
+        for this class.  A file without classifier.* keeps the freshly initialised head with n_class outputs (2 when
+        None, transformers' default): what from_pretrained of the base checkpoint gives."""
+        sd = {k: (v.float() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in sd.items()
+              if not k.startswith(_HF_CLIP_IGNORED)}
+        cfg = hf_clip_config(sd, heads)
+        cfg.setdefault("num_labels", 2 if n_class is None else n_class)
+        model = cls(hidden_act=hidden_act, **cfg)
+        want = set(model.state_dict())
+        if not any(k.startswith("classifier.") for k in sd):
+            want -= {"classifier.weight", "classifier.bias"}
+        missing, unexpected = sorted(want - set(sd)), sorted(set(sd) - want)
+        if missing or unexpected:
+            raise RuntimeError("the checkpoint does not match CLIPForImageClassification: %d missing key(s) %s, %d unexpected "
+                               "key(s) %s" % (len(missing), missing[:4], len(unexpected), unexpected[:4]))
+        model.load_state_dict(sd, strict=False)          # (the key sets were compared above; shapes are checked here)
+        return model
+
+    def route(self, x):
+        emb = self.vision_model.embeddings
+        n = emb.position_embedding.weight.shape[0]
+        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and x.is_contiguous()
+                and embed_gate(emb.patch_size, x.shape[2], x.shape[3], n)):
+            return "aten"
+        return clip_tower_route(HIP_HF_CLIP, x.is_cuda, x.dtype, torch.is_grad_enabled(), self.training, x.shape[0], n,
+                                emb.patch_embedding.out_channels, self.heads, _fused_residual_ok(x))
+
+    def forward(self, images):
+        self.vision_model.embeddings.check(images)
+        x = images.to(self.classifier.weight.dtype)
+        hip = self.route(x) == "hip"
+        t = self.vision_model(x, hip)
+        if not hip:
+            return self.classifier(torch.mean(t[:, 1:, :], dim=1))
+        pooled = core.token_mean(t, 1)                                                               # K26
+        if _hooked(self.classifier) or _nn_module._global_forward_hooks or _nn_module._global_forward_pre_hooks:
+            return self.classifier(pooled)
+        return _linear(self.classifier, pooled)
+
+    def encode_image(self, image):
+        return self(image)
+
+
+# target name -> a LOCAL checkpoint of that target, like register_clip_checkpoint for the dissector
+TARGET_CHECKPOINTS = {}
+_TARGET_TABLE = {}       # the parsed MCD_TARGET_CKPTS file and its (path, mtime, size)
+
+
+class RegisteredCheckpoint(str):
+    """The path of a checkpoint that was registered for a target: a model built for that target must take at least one of
+    the file's keys (_load_local), or the registration names a wrong file."""
+
+
+def register_target_checkpoint(name, path):
+    """Where the checkpoint of --target_model `name` lives (a state dict file or {'model': state dict}; local paths
+    only, and the file must exist now).  The drivers then build that target from it: for `clip` an HFClip sized from the
+    file; for every other target that is not a breastclip* one, the file in place of the Mammo-CLIP checkpoint.  The
+    environment variable MCD_TARGET_CKPTS names a JSON file {name: path} that does the same for a process that registers
+    nothing."""
+    if not isinstance(path, str) or not os.path.isfile(path):
+        raise FileNotFoundError("register_target_checkpoint(%r): %r is not an existing local file" % (name, path))
+    TARGET_CHECKPOINTS[name] = path
+
+
+def target_checkpoint(name):
+    """The registered checkpoint path of target `name` (a RegisteredCheckpoint), or None."""
+    path = TARGET_CHECKPOINTS.get(name)
+    table = os.environ.get("MCD_TARGET_CKPTS", "")
+    if path is None and table:
+        stamp = (table, os.path.getmtime(table), os.path.getsize(table))
+        if _TARGET_TABLE.get("stamp") != stamp:          # parsed once per file, again when the file changes
+            import json
+            with open(table, "r", encoding="utf-8") as f:
+                entries = json.load(f)
+            if not isinstance(entries, dict):
+                raise ValueError("MCD_TARGET_CKPTS=%r: the file must hold one JSON object {target name: path}" % (table,))
+            _TARGET_TABLE.update(stamp=stamp, entries=entries)
+        path = _TARGET_TABLE["entries"].get(name)
+        if path is not None and not (isinstance(path, str) and os.path.isfile(path)):
+            raise FileNotFoundError("MCD_TARGET_CKPTS=%r: %r -> %r is not an existing local file" % (table, name, path))
+    return None if path is None else RegisteredCheckpoint(path)
+
+
+def target_ckpt_or(target_name, ckpt):
+    """What the drivers pass to get_target_model as `ckpt`: the checkpoint registered for the target when there is one and
+    the target is not a breastclip* model (those take the Mammo-CLIP checkpoint), else `ckpt`, as before."""
+    if target_name.startswith("breastclip"):
+        return ckpt
+    return target_checkpoint(target_name) or ckpt
+
+
+# ------------------------------------------------------------------------------------------------------
 # factories
 # ------------------------------------------------------------------------------------------------------
 BERT_PREFIX = "text_encoder.text_encoder."
@@ -2338,6 +2632,9 @@ def _load_local(model, ckpt, text_strict=False):
     if text_strict:
         sd = {k: v for k, v in sd.items() if not k.startswith(_BERT_IGNORED)}
     result = model.load_state_dict(sd, strict=False)
+    if isinstance(ckpt, RegisteredCheckpoint) and len(result.unexpected_keys) == len(sd):
+        raise RuntimeError("the checkpoint registered for this target, %r, has no key that %s takes (its first keys: %s): a "
+                           "wrong file, or a wrong target name" % (str(ckpt), type(model).__name__, sorted(sd)[:4]))
     if text_strict:
         missing = [k for k in result.missing_keys if k.startswith("text_encoder.")]
         unexpected = [k for k in result.unexpected_keys if k.startswith("text_encoder.")]
@@ -2369,7 +2666,7 @@ def _load_places(model, ckpt):
 
 
 def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, finetuned_ckpt=None, seed=0, image_size=224,
-                     text_tower=None):
+                     text_tower=None, use_registered=True):
     """Returns (target model in eval mode, preprocess) -- reference data_utils.py:38-93.  Weights are
     random-init under `seed` unless a local checkpoint is given; nothing is downloaded.
     image_size: input resolution of the ViT towers, an int (square) or (H, W) (position embeddings are sized for it;
@@ -2378,7 +2675,9 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
     every resolution: K9 up to 256 tokens, K9L beyond (attention_route).
     text_tower (breastclip, breastclip_vit): 'stand-in', 'bert', or None = 'bert' exactly when the checkpoint's state dict
     has keys starting text_encoder.text_encoder. (a Mammo-CLIP checkpoint), else the stand-in.  The BERT tower's hidden
-    size, depth, intermediate size, vocabulary and position rows are read from the checkpoint's shapes."""
+    size, depth, intermediate size, vocabulary and position rows are read from the checkpoint's shapes.
+    use_registered (clip): False keeps the checkpoint registered for the `clip` TARGET out of this call -- the drivers build
+    their stand-in DISSECTOR under the same name (og_utils._clip_dissector)."""
     if text_tower not in (None, "stand-in", "bert"):
         raise ValueError("text_tower must be None, 'stand-in' or 'bert', got %r" % (text_tower,))
     if target_name == "openai_clip":
@@ -2388,6 +2687,26 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
             torch.manual_seed(seed)
             model = OpenAIClip(**VIT_B16) if ckpt is None else OpenAIClip.from_state_dict(openai_clip_state_dict(ckpt))
         return model.to(device).eval(), None
+    if target_name == "clip":
+        # transformers' CLIPForImageClassification when a checkpoint of it is at hand: `ckpt` itself when it carries the
+        # vision tower's keys, else the one registered for `clip`.  Sized from the shapes (a fine-tuned clip-cub /
+        # clip-bloodmnist file is this target with that file) and loaded strictly.  Without either, the stand-in below.
+        sd = None
+        if ckpt is not None:
+            loaded = _state_dict_of(ckpt)
+            if HF_CLIP_KEY in loaded or isinstance(ckpt, RegisteredCheckpoint):
+                sd = loaded
+            else:
+                ckpt = loaded                    # read once: the stand-in below loads from the state dict
+        if sd is None and use_registered:
+            registered = target_checkpoint("clip")
+            sd = None if registered is None else _state_dict_of(registered)
+        if sd is not None:
+            with torch.random.fork_rng(devices=[]):
+                torch.manual_seed(seed)
+                model = HFClip.from_state_dict(sd, n_class=n_class)
+            _load_local(model, finetuned_ckpt)
+            return model.to(device).eval(), None
     text_kw = {}
     if target_name.startswith("breastclip") and target_name != "breastclip_classifier" and (ckpt is not None or text_tower):
         if ckpt is not None:

@@ -42,7 +42,8 @@ def _clip_dissector(device, clip_name="ViT-B/16"):
     if ckpt is not None:
         model, _ = data_utils.get_target_model("openai_clip", device, ckpt=ckpt)
         return model, model.tokenize
-    model, _ = data_utils.get_target_model(CLIP_DISSECTORS.get(clip_name, "clip"), device)
+    # (use_registered=False: a checkpoint registered for the `clip` TARGET is a classifier without a text side, never the dissector)
+    model, _ = data_utils.get_target_model(CLIP_DISSECTORS.get(clip_name, "clip"), device, use_registered=False)
     tok = data_utils.HashTokenizer()
     return model, (lambda texts: tok(texts, max_length=77))
 
@@ -53,7 +54,10 @@ def save_activations(clip_name, target_name, target_layers, d_probe,
     """reference og_utils.py:374-471.  Returns the Extraction left on the device (None when every cache file existed)."""
     clip_model, tokenize = _clip_dissector(device, clip_name)
     if target_name == "clip":
-        target_model = clip_model
+        # a checkpoint registered for `clip` (data_utils.register_target_checkpoint): transformers'
+        # CLIPForImageClassification from it, a model of its own (data_utils.HFClip); without one the dissector itself
+        registered = data_utils.target_checkpoint("clip")
+        target_model = clip_model if registered is None else data_utils.get_target_model("clip", device, ckpt=registered)[0]
         encode_target = target_model                      # reference :464-469 -> target_model(images), :127
     elif target_name == "breastclip_classifier":
         target_model, _ = data_utils.get_target_model(target_name, device, args=args, ckpt=breast_clip_ckh,
@@ -61,7 +65,8 @@ def save_activations(clip_name, target_name, target_layers, d_probe,
                                                       finetuned_ckpt=fine_tuned_ckh)
         encode_target = target_model.encode_image
     else:
-        target_model, _ = data_utils.get_target_model(target_name, device, ckpt=breast_clip_ckh)
+        target_model, _ = data_utils.get_target_model(target_name, device,
+                                                      ckpt=data_utils.target_ckpt_or(target_name, breast_clip_ckh))
         encode_target = target_model.encode_image         # reference :93
     # reference :410-430: the dissector gets the set's own transform (clip_preprocess = None), the target its own
     data = _u._probe_data(d_probe, device, data_utils.target_preset(target_name), "default")

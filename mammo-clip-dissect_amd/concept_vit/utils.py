@@ -339,8 +339,9 @@ def build_mammo_models(target_name, device, breast_clip_ckh=None, fine_tuned_ckh
     elif target_name == "breastclip_classifier":
         target_model, _ = data_utils.get_target_model(target_name, device, args=args, ckpt=breast_clip_ckh,
                                                       n_class=getattr(args, "num_class", 1), finetuned_ckpt=finetuned)
-    else:
-        target_model, _ = data_utils.get_target_model(target_name, device, ckpt=breast_clip_ckh)
+    else:       # a checkpoint registered for the target (data_utils.register_target_checkpoint) takes the Mammo-CLIP file's place
+        target_model, _ = data_utils.get_target_model(target_name, device,
+                                                      ckpt=data_utils.target_ckpt_or(target_name, breast_clip_ckh))
     return clip_model, target_model
 
 

@@ -493,6 +493,26 @@ def quick_gelu(x, out=None):
     return out
 
 
+# ---- K26 -----------------------------------------------------------------------------------------
+@_on_device
+def token_mean(x, t0=1, out=None):
+    """The mean of the tokens t0 .. T-1 of every image in one launch (K26, include/mcd_tokens.h): x a float32 [B, T, D]
+    tensor with a unit inner stride -- contiguous, or a view whose tokens and images lie further apart -- -> [B, D];
+    out None (a new tensor) or a float32 [B, D] tensor with a unit inner stride (a row-strided view too).  t0 = 1 is
+    x[:, 1:].mean(dim=1), the mean of a ViT's patch tokens.  The entry checks widths, strides, alignment and overlap."""
+    _need_gpu(x, out)
+    if x.dtype != torch.float32 or x.dim() != 3 or x.stride(2) != 1:
+        raise TypeError("x must be a float32 [B, T, D] tensor with a unit inner stride")
+    B, T, D = x.shape
+    if out is None:
+        out = torch.empty((B, D), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, D) or out.stride(1) != 1:
+        raise TypeError("out must be a float32 [B, D] tensor with a unit inner stride")
+    check(_lib.load().mcd_token_mean(x.data_ptr(), B, T, D, x.stride(0), x.stride(1), t0, out.data_ptr(), out.stride(0),
+                                     _stream()))
+    return out
+
+
 # ---- K9C -----------------------------------------------------------------------------------------
 VIT_ATTENTION_CLS_MAX_T = 32768
 
