@@ -73,6 +73,16 @@ CLIP_SIGNATURES = {
 TOKEN_SIGNATURES = {
     "mcd_token_mean": (_int, [_p, _int, _int, _int, _i64, _i64, _int, _p, _i64, _p]),
 }
+# the activation-cache streaming entries of the same library, declared in include/mcd_cache.h (additive to ABI version 9)
+_pp = ctypes.POINTER(_p)
+CACHE_SIGNATURES = {
+    "mcd_hook_pool_rows": (_int, [_p, _i64, _i64, _i64, _int, _p, _i64, _i64, _i64, _i64, _p, _i64, _p]),
+    "mcd_cache_stream_open": (_int, [_int, _pp, ctypes.POINTER(_i64), _p, _int, _sz, _pp]),
+    "mcd_cache_stream_reserve": (_int, [_p, _int, _p]),
+    "mcd_cache_stream_push": (_int, [_p, _int, _p, _i64, _i64, _p]),
+    "mcd_cache_stream_close": (_int, [_p]),
+    "mcd_cache_stream_abort": (_int, [_p]),
+}
 
 MCD_E_ARG = -1
 MCD_E_RANGE = -2
@@ -100,7 +110,7 @@ def load():
                 "g.build()'` or `make -C mammo-clip-dissect_amd/csrc`. There is no CPU fallback." % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(CLIP_SIGNATURES.items())
-                                  + list(TOKEN_SIGNATURES.items())):
+                                  + list(TOKEN_SIGNATURES.items()) + list(CACHE_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
@@ -143,3 +153,43 @@ def load_blaslt():
         except (OSError, AttributeError):
             _blaslt = False
     return _blaslt or None
+
+
+# ---- libmcd_host.so: the container half of include/mcd_cache.h (plain C, no GPU) ---------------------------------
+HOST_PATH = os.path.join(_HERE, "csrc", "libmcd_host.so")
+CACHE_HOST_SIGNATURES = {
+    "mcd_zip_crc32": (ctypes.c_uint32, [ctypes.c_uint32, _p, _sz]),
+    "mcd_cachefile_open": (_int, [ctypes.c_char_p, ctypes.c_char_p, _i64, _i64, _i64, _i64, _i64, _pp]),
+    "mcd_cachefile_append": (_int, [_p, _p, _i64, _i64]),
+    "mcd_cachefile_close": (_int, [_p]),
+    "mcd_cachefile_abort": (None, [_p]),
+    "mcd_cachefile_last_error": (ctypes.c_char_p, []),
+}
+_cache_host = None
+
+
+class CacheIO(ctypes.Structure):
+    """mcd_cache_io_t: the container's entry points as mcd_cache_stream_open takes them."""
+    _fields_ = [("append", _p), ("close", _p), ("abort", _p), ("last_error", _p)]
+
+
+def load_cache_host():
+    """libmcd_host.so with the container entries, or None when it has not been built (the cache files are then written by the
+    Python writer thread, concept_vit/utils.py)."""
+    global _cache_host
+    if _cache_host is None:
+        try:
+            L = ctypes.CDLL(HOST_PATH)
+            for name, (res, args) in CACHE_HOST_SIGNATURES.items():
+                fn = getattr(L, name)
+                fn.restype = res
+                fn.argtypes = args
+            _cache_host = L
+        except (OSError, AttributeError):
+            _cache_host = False
+    return _cache_host or None
+
+
+def cache_io(H):
+    """The mcd_cache_io_t of the container in libmcd_host.so (H = load_cache_host())."""
+    return CacheIO(*[ctypes.cast(getattr(H, "mcd_cachefile_" + n), _p) for n in ("append", "close", "abort", "last_error")])

@@ -132,22 +132,198 @@ class Extraction:
     (Dissector.finish) instead of re-loading the cache files layer by layer; the cache files are still written, by a
     background thread, as the reference's side output."""
 
-    def __init__(self, dis, E_txt, target_layers, writer=None):
+    def __init__(self, dis, E_txt, target_layers, writer=None, stream=None):
         self.dis, self.E_txt, self.target_layers, self.writer = dis, E_txt, list(target_layers), writer
+        self.stream = stream      # CacheStream: the files were streamed out during the pass, only their finalisation is left
 
     def start_writer(self):
         """Start the cache-file writer (idempotent).  The drivers call it once the scoring kernels are queued, so the
-        writer's device -> host copies run beside the CSV writing on the host, not beside the scoring kernels."""
+        writer's device -> host copies run beside the CSV writing on the host, not beside the scoring kernels.
+        Nothing to start on the streaming route."""
         if self.writer is not None and not self.writer.is_alive() and not self.writer.started:
             self.writer.begin()
 
     def wait(self):
+        if self.stream is not None:
+            stream, self.stream = self.stream, None
+            stream.close()        # raises the first error of the pass's copies, appends and finalisations
         if self.writer is not None:
             self.start_writer()
             self.writer.join()
             if self.writer.error is not None:
                 raise self.writer.error
             self.writer = None
+
+
+# ---- the streaming route of the cache files (include/mcd_cache.h) --------------------------------------------------
+CACHE_STREAM_SLOTS = 8     # pinned slots of the ring (one holds a batch of one layer); tests shrink it to meet the back-pressure
+
+
+def _placeholder_archive(part_path, n_rows, width):
+    """torch.save of an UNINITIALISED float32 [n_rows, width] tensor as `part_path`: the complete archive of the cache file,
+    with placeholder bytes where the rows will go.  Returns (data offset, CRC field offset a, CRC field offset b) of the
+    tensor's record, read back from the zip structures: the central-directory entry's CRC-32, and the local header's or -- when
+    the writer set general-purpose bit 3, as torch's does -- the data descriptor's behind the data.  (The archive's
+    .data/serialization_id record is a hash that torch derives from the record names and CRCs at save time; it stays the
+    placeholder's.  Nothing reads it back.)"""
+    import struct
+    import zipfile
+    torch.save(torch.empty((n_rows, width), dtype=torch.float32), part_path)
+    nbytes = n_rows * width * 4
+    with zipfile.ZipFile(part_path) as z:
+        recs = [i for i in z.infolist() if i.filename.endswith("/data/0")]
+        start_dir = z.start_dir
+    with open(part_path, "rb") as f:
+        def at(off, n):
+            f.seek(off)
+            return f.read(n)
+        ok = len(recs) == 1 and recs[0].compress_type == zipfile.ZIP_STORED and recs[0].file_size == nbytes
+        if ok:
+            zi = recs[0]
+            head = at(zi.header_offset, 30)
+            ok = head[:4] == b"PK\x03\x04"
+        if ok:
+            n_name, n_extra = struct.unpack("<HH", head[26:30])
+            data_off = zi.header_offset + 30 + n_name + n_extra
+            if zi.flag_bits & 0x8:
+                crc_b = data_off + nbytes + (4 if at(data_off + nbytes, 4) == b"PK\x07\x08" else 0)
+            else:
+                crc_b = zi.header_offset + 14
+            crc_a, pos = None, start_dir
+            while crc_a is None:
+                ent = at(pos, 46)
+                if len(ent) < 46 or ent[:4] != b"PK\x01\x02":
+                    break
+                n_name, n_extra, n_comment = struct.unpack("<HHH", ent[28:34])
+                if at(pos + 46, n_name) == zi.orig_filename.encode("utf-8"):
+                    crc_a = pos + 16
+                pos += 46 + n_name + n_extra + n_comment
+            want = struct.pack("<I", zi.CRC)
+            ok = crc_a is not None and at(crc_a, 4) == want and at(crc_b, 4) == want
+    if not ok:
+        os.unlink(part_path)
+        raise RuntimeError("torch.save wrote an archive whose tensor record was not found where the zip format puts it: %s "
+                           "(MCD_CACHE_STREAM=0 writes the cache files without the streaming route)" % part_path)
+    return data_off, crc_a, crc_b
+
+
+class CacheStream:
+    """The cache files of one extraction pass, written while it runs: every (batch, layer) block leaves the device as soon as
+    its K0 hook has run and a native worker thread appends it to the layer's file (mcd_cache_stream_*, libmcd_hip.so, with the
+    container of libmcd_host.so); close() only waits for the last blocks and finalises.  Files are `<name>.part` until they are
+    complete.
+    The archives themselves are laid out by torch.save (_placeholder_archive), once the first batch's kernels are queued, so
+    that the host time of it lies behind that batch's GPU time: the pushes of the first batch wait in `pending` until begin()."""
+
+    def __init__(self, device, n_rows, files, batch_rows, slots=None):
+        """files: [(path, width)], pushed to by index.  batch_rows: the largest number of rows of one push."""
+        d = torch.device(device)
+        self.device = torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
+        self.n_rows, self.files = int(n_rows), list(files)
+        self.slots = int(slots if slots is not None else CACHE_STREAM_SLOTS)
+        self.slot_bytes = max(4, int(batch_rows) * max(w for _, w in self.files) * 4)
+        self.handle, self.pending, self.closed, self.keep = None, [], False, {}
+        self.L, self.H = core._lib.load(), core._lib.load_cache_host()
+
+    def begin(self):
+        if self.handle is not None or self.closed:
+            return
+        import ctypes
+        H, n = self.H, len(self.files)
+        handles = (ctypes.c_void_p * n)()
+        try:
+            for i, (path, width) in enumerate(self.files):
+                part = path + ".part"
+                data_off, crc_a, crc_b = _placeholder_archive(part, self.n_rows, width)
+                h = ctypes.c_void_p()
+                if H.mcd_cachefile_open(os.fsencode(part), os.fsencode(path), self.n_rows, width, data_off, crc_a, crc_b,
+                                        ctypes.byref(h)) != 0:
+                    raise OSError(H.mcd_cachefile_last_error().decode("utf-8", "replace"))
+                handles[i] = h
+        except BaseException:
+            self.closed = True
+            for h in handles:
+                if h:
+                    H.mcd_cachefile_abort(h)
+            raise
+        widths = (ctypes.c_int64 * n)(*[w for _, w in self.files])
+        io = core._lib.cache_io(H)
+        out = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            rc = self.L.mcd_cache_stream_open(n, handles, widths, ctypes.byref(io), self.slots, self.slot_bytes, ctypes.byref(out))
+        if rc != 0:            # (the native side has removed the .part files)
+            self.closed = True
+            core.check(rc)
+        self.handle = out
+        # The first batch's blocks: each is ready at the event its hook recorded, not only now that the whole batch is queued.
+        # A side stream that waits for that event stands in for the launch stream, so the copies of the early layers start at
+        # once and their slots come back while the GPU is still inside the batch (pushed from the launch stream, all of them
+        # would wait for the end of the batch and the launch thread would sit in the back-pressure until then).
+        pending, self.pending = self.pending, []
+        if pending:
+            with torch.cuda.device(self.device):
+                self._side = torch.cuda.Stream(device=self.device)
+                for file, block, row0, n, ready in pending:
+                    self._side.wait_event(ready)
+                    with torch.cuda.stream(self._side):
+                        self.push(file, block, row0, n)
+
+    def reserve(self, file):
+        """Before the kernel that rewrites the staging block of `file`: the current stream waits until the copy of the block's
+        previous content has been taken."""
+        if self.handle is not None:
+            with torch.cuda.device(self.device):
+                core.check(self.L.mcd_cache_stream_reserve(self.handle, file, core._stream()))
+
+    def push(self, file, block, row0, n):
+        """`block`: contiguous float32 device rows [>= n, width of the file], final once the current stream's queued work has run."""
+        if self.closed:
+            raise RuntimeError("CacheStream is closed")
+        if block.dtype != torch.float32 or not block.is_contiguous() or block.dim() != 2 or block.shape[0] < n \
+                or block.shape[1] != self.files[file][1] or block.device != self.device:
+            raise TypeError("CacheStream.push: block must be contiguous float32 [>= %d, %d] on %s" % (n, self.files[file][1], self.device))
+        if self.handle is None:
+            with torch.cuda.device(self.device):
+                ready = torch.cuda.Event()
+                ready.record()
+            self.pending.append((file, block, row0, n, ready))
+            return
+        # the copy stream reads the block behind torch's back: it stays referenced (not handed back to the caching allocator)
+        # until close() or abort() has drained the copies
+        self.keep[file] = block
+        with torch.cuda.device(self.device):
+            core.check(self.L.mcd_cache_stream_push(self.handle, file, block.data_ptr(), int(row0), int(n), core._stream()))
+
+    def _end(self, entry):
+        if self.closed:
+            return
+        self.closed = True
+        self.pending = []
+        if self.handle is not None:
+            handle, self.handle = self.handle, None
+            try:
+                core.check(entry(handle))
+            finally:
+                self.keep = {}
+
+    def close(self):
+        """Wait for the last blocks, finalise every file and rename it into place; raises the first error."""
+        if not self.closed and self.handle is None:
+            self.begin()          # a pass of no complete batch: the native close then reports the missing rows
+        self._end(self.L.mcd_cache_stream_close)
+
+    def abort(self):
+        """Drop the pass: no file appears under its final name."""
+        try:
+            self._end(self.L.mcd_cache_stream_abort)
+        except core._lib.McdError:
+            pass
+
+    def __del__(self):
+        try:
+            self.abort()
+        except Exception:
+            pass
 
 
 class _CacheWriter(threading.Thread):
@@ -264,6 +440,17 @@ def extract_and_save(clip_model, target_model, encode_target, target_layers, dat
         dis = Dissector(N, list(target_layers), widths, len(words), E_txt.shape[1], device,
                         pool_mode=pool_mode, gather=gather)
         handles = [m.register_forward_hook(dis.hook(i)) for i, m in enumerate(layers)] if need_target else []
+        # the streaming route of the cache files: a GPU pass that computes the activations, with the native container built.
+        # Everything else -- a non-GPU device, activations loaded from existing files, no libmcd_host.so, MCD_CACHE_STREAM=0
+        # (the A/B knob) -- keeps the writer thread below.
+        stream = None
+        if write_caches and need_target and N > 0 and torch.device(device).type == "cuda" \
+                and os.environ.get("MCD_CACHE_STREAM", "1") != "0" and core._lib.load_cache_host() is not None:
+            files = [(layer_files[l], w) for l, w in zip(target_layers, widths)]
+            if need_clip:
+                files.append((clip_save_name, int(E_txt.shape[1])))
+            stream = CacheStream(dis.device, N, files, batch_size)
+            dis.attach_cache_stream(stream, batch_size, image_file=len(files) - 1 if need_clip else None)
         try:
             for batch in batches:
                 if not on_device:
@@ -283,9 +470,14 @@ def extract_and_save(clip_model, target_model, encode_target, target_layers, dat
                         f = clip_model.image_projection(f)
                     dis.add_image_features(f.float())
                 dis.advance(images.shape[0])
+        except BaseException:
+            if stream is not None:
+                stream.abort()       # no half-written file is left under a name a later run would take for a cache
+            raise
         finally:
             for h in handles:
                 h.remove()
+            dis.cache_stream = None
         if not need_clip:
             dis.E_img.copy_(_load_feats(clip_save_name, device))
         if not need_target:   # the layers' cache files exist, the dissector embeddings did not: load the activations
@@ -293,6 +485,8 @@ def extract_and_save(clip_model, target_model, encode_target, target_layers, dat
                 A = torch.load(layer_files[l], map_location='cpu', weights_only=True).float().to(device)
                 core.transpose(A, out=dis.At[dis.offsets[i]:dis.offsets[i + 1], :N])
         writer = None
+        if stream is not None:
+            return Extraction(dis, E_txt, target_layers, stream=stream)
         if write_caches:
             jobs = []
             if need_clip:

@@ -952,14 +952,18 @@ def linear_residual(res, h, weight, bias=None, out=None, relu=False):
 
 # ---- K0 ------------------------------------------------------------------------------------------
 @_on_device
-def hook_pool(x, mode, dst, row0, col0, neuron_major):
+def hook_pool(x, mode, dst, row0, col0, neuron_major, rows=None):
     """Pool a hooked tensor (utils.py:27-52) and write it into the activation matrix `dst`.
 
     mode: "avg"/"max" for 4-D [B,Cout,H,W]; 3-D [B,T,F] takes token 0; 2-D [B,F] is copied.
     dst: [U_total, N] when neuron_major else [N, U_total]; rows row0.. / columns col0.. are written.
+    rows: optional contiguous float32 [>= B, Cout] staging block that receives the same block image-major, the layout of the
+    layer's activation-cache file (mcd_hook_pool_rows, include/mcd_cache.h: one kernel, two stores).
     Returns the number of neurons written.
     """
     _need_gpu(x, dst)
+    if rows is not None:
+        _need_gpu(rows)
     if x.dtype != torch.float32:
         x = x.float()
     # a channels-last 4-D output (the B5 tower's HIP route) is pooled where it lies by K0n: the same bits as K0 on the
@@ -989,9 +993,21 @@ def hook_pool(x, mode, dst, row0, col0, neuron_major):
         sn, su = 1, dst.stride(0)
     else:
         sn, su = dst.stride(0), 1
+    if rows is not None and (rows.dtype != torch.float32 or rows.dim() != 2 or not rows.is_contiguous()
+                             or rows.shape[0] < B or rows.shape[1] != Cout):
+        raise TypeError("rows must be a contiguous float32 [>= %d, %d] block" % (B, Cout))
     L = _lib.load()
     if nhwc:
         check(L.mcd_hook_pool_nhwc(x.data_ptr(), B, Cout, HW, m, dst.data_ptr(), int(row0), int(col0), sn, su, _stream()))
+        if rows is not None:      # K0n has no second store: the block just written, transposed by the HIP transpose kernel
+            if not neuron_major:
+                raise TypeError("hook_pool: rows with a channels-last input needs a neuron-major dst")
+            if B > 0:
+                transpose(dst[col0:col0 + Cout, row0:row0 + B], out=rows[:B])
+        return Cout
+    if rows is not None:
+        check(L.mcd_hook_pool_rows(x.data_ptr(), B, Cout, HW, m, dst.data_ptr(), int(row0), int(col0), sn, su, rows.data_ptr(),
+                                   Cout, _stream()))
         return Cout
     check(L.mcd_hook_pool(x.data_ptr(), B, Cout, HW, m, dst.data_ptr(), int(row0), int(col0), sn, su, _stream()))
     return Cout

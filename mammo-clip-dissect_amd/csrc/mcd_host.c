@@ -9,10 +9,19 @@
  * are exact doubles (<= 44 significant bits), so Dragon4's stopping rule -- stop at the first digit position where
  * the truncated or the incremented digit string lies strictly inside the interval, then round as it does -- is a few
  * comparisons.  Rows outside the regime return -1 and are formatted by numpy itself.
- * tests/test_host_logic_cpu.py compares the two character for character on random rows. */
+ * tests/test_host_logic_cpu.py compares the two character for character on random rows.
+ *
+ * Further down: the container half of include/mcd_cache.h (the activation-cache files written in pieces, with the zip CRC-32),
+ * tested by tests/test_cache_stream_cpu.py. */
+#define _POSIX_C_SOURCE 200809L   /* pwrite */
+#include <errno.h>
+#include <fcntl.h>
 #include <math.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
+#include <unistd.h>
 
 static const double P10[9] = {1.0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8};
 static const uint64_t I10[9] = {1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull, 10000000ull, 100000000ull};
@@ -215,4 +224,174 @@ int64_t mcd_csv_og_rows(const char* layer, int layer_len, int64_t nrows, const i
         *o++ = '\n';
     }
     return (int64_t)(o - out);
+}
+
+/* ---- the activation-cache container (include/mcd_cache.h, host half) ------------------------------------------
+ * A cache file is torch.save's zip archive of ONE float32 tensor [n_rows, width]: the tensor's bytes are the stored
+ * (uncompressed) record <name>/data/0.  The Python side writes the archive once with placeholder data
+ * (concept_vit/utils.py) and hands over the byte offset of the record's data and of the two places where the zip
+ * format keeps its CRC-32.  Here the rows are written over the placeholder as they arrive, the CRC runs along, and
+ * mcd_cachefile_close puts the CRC in place and renames <name>.part to <name>: a file under its final name is always
+ * complete. */
+static _Thread_local char g_cache_err[512];
+
+const char* mcd_cachefile_last_error(void) { return g_cache_err; }
+
+static int cache_fail(const char* what, const char* path, int err) {
+    if (err)
+        snprintf(g_cache_err, sizeof g_cache_err, "%s: %s: %s", what, path ? path : "", strerror(err));
+    else
+        snprintf(g_cache_err, sizeof g_cache_err, "%s: %s", what, path ? path : "");
+    return -1;
+}
+
+/* CRC-32 of zip / zlib (IEEE 802.3, reflected polynomial 0xEDB88320), slicing by 8.  mcd_zip_crc32(0, NULL, 0) == 0;
+ * feeding the pieces of a buffer in order gives the CRC of the whole, as zlib.crc32(piece, crc) does. */
+static uint32_t g_crc_tab[8][256];
+static int g_crc_ready;
+
+static void crc_init(void) {
+    /* idempotent: threads that race here write the same values; the flag is set last */
+    for (uint32_t i = 0; i < 256; ++i) {
+        uint32_t c = i;
+        for (int k = 0; k < 8; ++k) c = (c & 1u) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
+        g_crc_tab[0][i] = c;
+    }
+    for (uint32_t i = 0; i < 256; ++i)
+        for (int t = 1; t < 8; ++t) g_crc_tab[t][i] = (g_crc_tab[t - 1][i] >> 8) ^ g_crc_tab[0][g_crc_tab[t - 1][i] & 0xffu];
+    __atomic_store_n(&g_crc_ready, 1, __ATOMIC_RELEASE);
+}
+
+uint32_t mcd_zip_crc32(uint32_t crc, const void* buf, size_t n) {
+    const unsigned char* p = (const unsigned char*)buf;
+    if (!__atomic_load_n(&g_crc_ready, __ATOMIC_ACQUIRE)) crc_init();
+    uint32_t c = ~crc;
+    while (n && ((uintptr_t)p & 7u)) { c = g_crc_tab[0][(c ^ *p++) & 0xffu] ^ (c >> 8); --n; }
+    while (n >= 8) {
+        uint32_t lo, hi;
+        memcpy(&lo, p, 4);
+        memcpy(&hi, p + 4, 4);
+        lo ^= c;                     /* little-endian hosts only (x86-64, aarch64): the zip fields below assume it too */
+        c = g_crc_tab[7][lo & 0xffu] ^ g_crc_tab[6][(lo >> 8) & 0xffu] ^ g_crc_tab[5][(lo >> 16) & 0xffu] ^ g_crc_tab[4][lo >> 24] ^
+            g_crc_tab[3][hi & 0xffu] ^ g_crc_tab[2][(hi >> 8) & 0xffu] ^ g_crc_tab[1][(hi >> 16) & 0xffu] ^ g_crc_tab[0][hi >> 24];
+        p += 8;
+        n -= 8;
+    }
+    while (n--) c = g_crc_tab[0][(c ^ *p++) & 0xffu] ^ (c >> 8);
+    return ~c;
+}
+
+typedef struct {
+    int fd;
+    int64_t n_rows, width, rows_done, data_off, crc_off[2];
+    uint32_t crc;
+    char *part, *final;
+} mcd_cachefile;
+
+static int write_all(int fd, const void* buf, size_t n, int64_t off) {
+    const char* p = (const char*)buf;
+    while (n) {
+        const ssize_t w = pwrite(fd, p, n, (off_t)off);
+        if (w < 0) {
+            if (errno == EINTR) continue;
+            return -1;
+        }
+        p += w;
+        off += w;
+        n -= (size_t)w;
+    }
+    return 0;
+}
+
+static void cachefile_drop(mcd_cachefile* f, int unlink_part) {
+    if (f->fd >= 0) close(f->fd);
+    if (unlink_part && f->part) unlink(f->part);
+    free(f->part);
+    free(f->final);
+    free(f);
+}
+
+/* Opens the placeholder archive `part_path` (it must exist and reach past the data record) for writing in place.
+ * crc_off_a / crc_off_b: byte offsets of the record's CRC-32 fields (central-directory entry; local header or, where the
+ * writer used one, the data descriptor behind the data); pass the same offset twice if the archive has one. */
+int mcd_cachefile_open(const char* part_path, const char* final_path, int64_t n_rows, int64_t width, int64_t data_off,
+                       int64_t crc_off_a, int64_t crc_off_b, void** out) {
+    if (!part_path || !final_path || !out) return cache_fail("mcd_cachefile_open", "NULL argument", 0);
+    *out = NULL;
+    if (n_rows < 0 || width <= 0 || data_off < 0 || crc_off_a < 0 || crc_off_b < 0 || n_rows > (INT64_MAX >> 3) / width)
+        return cache_fail("mcd_cachefile_open: bad shape or offset", part_path, 0);
+    const int64_t bytes = n_rows * width * 4, end = data_off + bytes;
+    const int64_t c[2] = {crc_off_a, crc_off_b};
+    for (int i = 0; i < 2; ++i)
+        if (c[i] + 4 > data_off && c[i] < end)
+            return cache_fail("mcd_cachefile_open: a CRC field lies inside the data record", part_path, 0);
+    mcd_cachefile* f = (mcd_cachefile*)calloc(1, sizeof *f);
+    if (!f) return cache_fail("mcd_cachefile_open: out of memory", part_path, 0);
+    f->fd = -1;
+    f->part = strdup(part_path);
+    f->final = strdup(final_path);
+    if (!f->part || !f->final) {
+        cachefile_drop(f, 0);
+        return cache_fail("mcd_cachefile_open: out of memory", part_path, 0);
+    }
+    f->fd = open(part_path, O_WRONLY | O_CLOEXEC);
+    if (f->fd < 0) {
+        const int e = errno;
+        cachefile_drop(f, 0);
+        return cache_fail("mcd_cachefile_open", part_path, e);
+    }
+    const off_t size = lseek(f->fd, 0, SEEK_END);
+    if (size < 0 || (int64_t)size < end || (int64_t)size < crc_off_a + 4 || (int64_t)size < crc_off_b + 4) {
+        cachefile_drop(f, 1);
+        return cache_fail("mcd_cachefile_open: the placeholder archive is shorter than its record", part_path, 0);
+    }
+    f->n_rows = n_rows;
+    f->width = width;
+    f->data_off = data_off;
+    f->crc_off[0] = crc_off_a;
+    f->crc_off[1] = crc_off_b;
+    *out = f;
+    return 0;
+}
+
+/* rows row0 .. row0 + n - 1; the pieces must arrive in order (row0 == the rows written so far) */
+int mcd_cachefile_append(void* h, const float* rows, int64_t row0, int64_t n) {
+    mcd_cachefile* f = (mcd_cachefile*)h;
+    if (!f || n < 0 || (n > 0 && !rows)) return cache_fail("mcd_cachefile_append", "bad argument", 0);
+    if (row0 != f->rows_done) return cache_fail("mcd_cachefile_append: rows out of order", f->part, 0);
+    if (n > f->n_rows - f->rows_done) return cache_fail("mcd_cachefile_append: more rows than the file was opened for", f->part, 0);
+    const size_t bytes = (size_t)n * (size_t)f->width * 4;
+    if (write_all(f->fd, rows, bytes, f->data_off + f->rows_done * f->width * 4) != 0) return cache_fail("mcd_cachefile_append", f->part, errno);
+    f->crc = mcd_zip_crc32(f->crc, rows, bytes);
+    f->rows_done += n;
+    return 0;
+}
+
+/* Removes the .part file; nothing appears under the final name. */
+void mcd_cachefile_abort(void* h) {
+    if (h) cachefile_drop((mcd_cachefile*)h, 1);
+}
+
+/* Finalises: CRC fields, close, rename to the final name.  With rows missing it is an error and acts as abort.  The handle is
+ * gone either way. */
+int mcd_cachefile_close(void* h) {
+    mcd_cachefile* f = (mcd_cachefile*)h;
+    if (!f) return cache_fail("mcd_cachefile_close", "NULL handle", 0);
+    int rc = 0;
+    if (f->rows_done != f->n_rows) {
+        snprintf(g_cache_err, sizeof g_cache_err, "mcd_cachefile_close: %s holds %lld of %lld rows", f->part,
+                 (long long)f->rows_done, (long long)f->n_rows);
+        rc = -1;
+    }
+    unsigned char le[4] = {(unsigned char)f->crc, (unsigned char)(f->crc >> 8), (unsigned char)(f->crc >> 16), (unsigned char)(f->crc >> 24)};
+    for (int i = 0; i < 2 && rc == 0; ++i)
+        if (write_all(f->fd, le, 4, f->crc_off[i]) != 0) rc = cache_fail("mcd_cachefile_close", f->part, errno);
+    if (rc == 0) {
+        const int fd = f->fd;
+        f->fd = -1;
+        if (close(fd) != 0) rc = cache_fail("mcd_cachefile_close", f->part, errno);
+    }
+    if (rc == 0 && rename(f->part, f->final) != 0) rc = cache_fail("mcd_cachefile_close: rename", f->final, errno);
+    cachefile_drop(f, rc != 0);
+    return rc;
 }

@@ -165,6 +165,17 @@ class Dissector:
         self.At = torch.zeros((self.U, self.ldA), dtype=torch.float32, device=self.device)  # neuron-major
         self.E_img = torch.zeros((self.n_local, self.D), dtype=torch.float32, device=self.device)
         self.cursor = 0
+        self.cache_stream = None
+
+    def attach_cache_stream(self, stream, batch_rows, image_file=None):
+        """Stream the activation-cache files out during the pass (concept_vit.utils.CacheStream): file i of `stream` is layer i's
+        [N, U_i]; image_file, if not None, the index of the image embeddings' [N, D].  Each hook then runs the two-store K0
+        (mcd_hook_pool_rows): the block goes into the activation matrix as always and, image-major, into the layer's staging
+        block of batch_rows rows, which is pushed to the stream.  Single-rank only (the cache files are)."""
+        if self.world != 1:
+            raise RuntimeError("the activation-cache files are a single-process feature")
+        self.cache_stream, self._image_file = stream, image_file
+        self._stage = [torch.empty((int(batch_rows), w), dtype=torch.float32, device=self.device) for w in self.layer_widths]
 
     def set_scoring(self, similarity_fn="soft_wpmi", top_k=None, a=None, lam=None, min_prob=1e-7, p_start=0.998,
                     p_end=0.97, p=3, top_fraction=0.05, scale_p=0.5, min_norm=1e-3):
@@ -213,7 +224,17 @@ class Dissector:
         def _hook(module, inputs, output):
             if type(output) is tuple:
                 output = output[0]
-            n = self.ops.hook_pool(output.detach(), self.pool_mode, self.At, self.cursor, col0, True)
+            out = output.detach()
+            if self.cache_stream is None:
+                n = self.ops.hook_pool(out, self.pool_mode, self.At, self.cursor, col0, True)
+            else:
+                stage, B = self._stage[layer_index], out.shape[0]
+                if B > stage.shape[0]:
+                    raise RuntimeError("layer %s handed the hook %d rows, the cache stream was sized for batches of %d"
+                                       % (self.layer_names[layer_index], B, stage.shape[0]))
+                self.cache_stream.reserve(layer_index)      # the copy of the previous batch's rows has left the staging block
+                n = self.ops.hook_pool(out, self.pool_mode, self.At, self.cursor, col0, True, rows=stage)
+                self.cache_stream.push(layer_index, stage, self.cursor, B)
             if n != width:
                 raise RuntimeError("layer %s produced %d neurons, expected %d" % (self.layer_names[layer_index], n, width))
         # of a 3-D [B, T, D] output hook_pool takes token 0: a ViT tower may hand this hook [B, 1, D] (data_utils.cls_tail_route)
@@ -224,11 +245,16 @@ class Dissector:
         """dissector image embeddings of the current batch (utils.py:329-331), rows cursor..cursor+B."""
         B = feats.shape[0]
         self.E_img[self.cursor:self.cursor + B].copy_(feats)
+        if self.cache_stream is not None and self._image_file is not None:
+            # these rows of E_img are final and nothing overwrites them: pushed from where they lie, no staging block
+            self.cache_stream.push(self._image_file, self.E_img[self.cursor:self.cursor + B], self.cursor, B)
 
     def advance(self, batch):
         self.cursor += int(batch)
         if self.cursor > self.n_local:
             raise RuntimeError("more images than the dissector was sized for")
+        if self.cache_stream is not None:
+            self.cache_stream.begin()       # first batch: its kernels are queued, now the files are laid out and its pushes sent
 
     # ---- collectives ---------------------------------------------------------------------------
     def _all_gather_rows(self, t):
