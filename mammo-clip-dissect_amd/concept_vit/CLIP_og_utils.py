@@ -9,7 +9,7 @@ import torch
 from . import data_utils
 from . import utils as _u
 from .og_utils import _clip_dissector
-from .utils import get_activation, get_save_names, _all_saved, _make_save_dir  # noqa: F401
+from .utils import get_activation, get_save_names, get_cos_similarity, _all_saved, _make_save_dir  # noqa: F401
 
 PM_SUFFIX = _u.PM_SUFFIX
 

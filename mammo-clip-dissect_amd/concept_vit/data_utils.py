@@ -196,8 +196,9 @@ def _class_pos_residual(pos, cls, bias, B):
 def _attend(qkv, heads, choice, arg=None):
     """The concatenated head outputs [B, T, D] of the fused projection's output qkv [B, T, 3 D] -- attention before the
     output projection -- on the kernel `choice` names: 'k9' (K9), 'long' (K9L: one workgroup per 256 queries of a head, no
-    T x T buffer), 'causal' (K9A), 'keylen' (K9M, arg: the int32 [B] key counts or None) or 'sdpa' (PyTorch's, arg: the
-    mask or None).  The HIP kernels (csrc/k_attn.hip) read the projection's layout and write the proj input's."""
+    T x T buffer), 'causal' (K9A), 'keylen' (K9M, arg: the int32 [B] key counts or None), 'relbias' (K9B, arg: the key
+    counts and the [heads, 2T-1] bias table) or 'sdpa' (PyTorch's, arg: the mask or None).  The HIP kernels
+    (csrc/k_attn.hip) read the projection's layout and write the proj input's."""
     B, T, D = qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3
     if choice == "k9":
         global _attention_calls
@@ -217,6 +218,8 @@ def _attend(qkv, heads, choice, arg=None):
         return core.vit_attention_causal(qkv, heads)
     if choice == "keylen":
         return core.vit_attention_keylen(qkv, heads, arg)
+    if choice == "relbias":
+        return core.vit_attention_relbias(qkv, heads, *arg)
     q, k, v = qkv.view(B, T, 3, heads, D // heads).permute(2, 0, 3, 1, 4)
     o = F.scaled_dot_product_attention(q, k, v, attn_mask=arg)
     return o.transpose(1, 2).reshape(B, T, D)
@@ -955,6 +958,10 @@ def _is_punct(ch):
     return unicodedata.category(ch).startswith("P")
 
 
+BERT_SPECIALS = ("[PAD]", "[UNK]", "[CLS]", "[SEP]")       # padding, unknown, first, last
+MPNET_SPECIALS = ("<pad>", "<unk>", "<s>", "</s>")
+
+
 class WordPieceTokenizer:
     """BertTokenizerFast restated in pure Python (no transformers import): what the reference's tokenize() runs
     (model/clip.py:81-101 on AutoTokenizer('emilyalsentzer/Bio_ClinicalBERT')), from a local vocab.txt.
@@ -971,9 +978,12 @@ class WordPieceTokenizer:
     do_lower_case=True is BertTokenizerFast's own default, and by our reading of its hub repository -- which ships no
     tokenizer configuration -- it is what the reference gets for Bio_ClinicalBERT, a cased vocabulary notwithstanding.
     That reading cannot be checked offline.  Not restated: special-token strings such as '[SEP]' inside the text (the
-    fast tokenizer maps them to the special ids; here they are split like any other text)."""
+    fast tokenizer maps them to the special ids; here they are split like any other text).
 
-    def __init__(self, vocab_file, do_lower_case=True, max_chars_per_word=100):
+    specials names the padding, unknown, first and last token in that order: BERT's by default, MPNET_SPECIALS for the
+    lower-cased WordPiece vocabulary of MPNet (MPNetTokenizer: <s> ids </s>, padded with <pad>), the same steps otherwise."""
+
+    def __init__(self, vocab_file, do_lower_case=True, max_chars_per_word=100, specials=BERT_SPECIALS):
         with open(vocab_file, encoding="utf-8") as f:
             tokens = [line.rstrip("\n") for line in f]
         while tokens and tokens[-1] == "":
@@ -984,10 +994,10 @@ class WordPieceTokenizer:
         self.vocab_size = len(tokens)
         self.do_lower_case = do_lower_case
         self.max_chars = max_chars_per_word
-        missing = [t for t in ("[PAD]", "[UNK]", "[CLS]", "[SEP]") if t not in self.vocab]
+        missing = [t for t in specials if t not in self.vocab]
         if missing:
             raise ValueError("%s lacks the special tokens %s" % (vocab_file, missing))
-        self.pad_id, self.unk_id, self.cls_id, self.sep_id = (self.vocab[t] for t in ("[PAD]", "[UNK]", "[CLS]", "[SEP]"))
+        self.pad_id, self.unk_id, self.cls_id, self.sep_id = (self.vocab[t] for t in specials)
 
     def words(self, text):
         out = []
@@ -1064,13 +1074,14 @@ TOKENIZER_VOCABS = {}
 
 
 def register_tokenizer(name, vocab_path, do_lower_case=True):
-    """Where a text tower's vocabulary lives (like register_dataset for probe sets): name 'bert', a LOCAL vocab.txt, or
+    """Where a text tower's vocabulary lives (like register_dataset for probe sets): name 'bert' or 'mpnet' (the sentence
+    encoder's lower-cased WordPiece vocabulary, MCD_MPNET_VOCAB), a LOCAL vocab.txt, or
     name 'clip', a LOCAL BPE merges file in bpe_simple_vocab_16e6.txt format, plain or gzipped (do_lower_case does not
     apply: CLIP's tokenizer always lower-cases).  The environment variables MCD_BERT_VOCAB=/path/vocab.txt and
     MCD_CLIP_BPE=/path/bpe_simple_vocab_16e6.txt.gz do the same for a process that registers nothing.  A 'clip' file is
     read here, once: one that is no merges file is refused at registration."""
-    if name not in ("bert", "clip"):
-        raise ValueError("register_tokenizer: %r is not a tokenizer of this package ('bert', 'clip')" % (name,))
+    if name not in ("bert", "clip", "mpnet"):
+        raise ValueError("register_tokenizer: %r is not a tokenizer of this package ('bert', 'clip', 'mpnet')" % (name,))
     if name == "clip":
         try:
             ClipBPETokenizer(vocab_path)
@@ -2552,6 +2563,330 @@ class HFClip(nn.Module):
 
     def encode_image(self, image):
         return self(image)
+
+
+# ------------------------------------------------------------------------------------------------------
+# The sentence encoder of get_cos_similarity (reference concept_vit/utils.py:618-646: SentenceTransformer
+# 'all-mpnet-base-v2'.encode): transformers.MPNetModel under its own names + sentence-transformers' Pooling(mean) + Normalize
+# ------------------------------------------------------------------------------------------------------
+# MPNetSentenceEncoder's inference route (sentence_route): the embedding rows on K24, per layer the fused qkv GEMM, K9B (K9M
+# with the relative-position bias), the two residual GEMMs and K10 behind each (_block_hip, post-norm), then K27 (masked mean
+# + L2 norm).  MCD_NO_HIP_SENTENCE=1 (or setting this to False) keeps the ATen route: SDPA under bias + key mask.
+HIP_SENTENCE = os.environ.get("MCD_NO_HIP_SENTENCE", "0") != "1"
+MPNET_MAX_TOKENS = 256            # encode() truncates here (K9B's limit; all-mpnet-base-v2's own max_seq_length is 384)
+MPNET_PAD_ID = 1                  # MPNetEmbeddings.padding_idx: <pad>, and the base of the position ids
+_MPNET_IGNORED = ("pooler.", "embeddings.position_ids")
+_MPNET_EMB_SKIPPED = ("word_embeddings", "position_embeddings", "LayerNorm")
+_MPNET_LAYER_SKIPPED = ("attention", "intermediate", "output")
+
+
+def relative_position_bucket(relative_position, num_buckets=32, max_distance=128):
+    """MPNetEncoder.relative_position_bucket (bidirectional T5 buckets) on an int64 tensor of key-minus-query distances,
+    with transformers' own torch operations: half the buckets per sign, the first half of each exact, the rest
+    logarithmic up to max_distance."""
+    n = -relative_position
+    num_buckets //= 2
+    ret = (n < 0).to(torch.long) * num_buckets
+    n = torch.abs(n)
+    max_exact = num_buckets // 2
+    is_small = n < max_exact
+    val_if_large = max_exact + (
+        torch.log(n.float() / max_exact) / math.log(max_distance / max_exact) * (num_buckets - max_exact)
+    ).to(torch.long)
+    val_if_large = torch.min(val_if_large, torch.full_like(val_if_large, num_buckets - 1))
+    return ret + torch.where(is_small, n, val_if_large)
+
+
+def mpnet_position_ids(ids, padding_idx=MPNET_PAD_ID):
+    """transformers' create_position_ids_from_input_ids: the k-th non-padding token of a row gets padding_idx + k (k from
+    1), a padding token padding_idx.  Valid token t of a right-padded row: t + 2."""
+    mask = ids.ne(padding_idx).int()
+    return (torch.cumsum(mask, dim=1).type_as(mask) * mask).long() + padding_idx
+
+
+def sentence_route(flag, on_gpu, dtype, grad, training, B, T, D, heads, pos_rows, fused_ok, prefix_mask):
+    """'hip' when an MPNetSentenceEncoder call may leave ATen: HIP_SENTENCE (`flag`), fp32 weights and ids on the GPU without
+    autograd (_hip_eligible), eval mode, D = 64 * heads (K9B's head width), 1 <= T <= core.VIT_ATTENTION_MAX_T with the
+    T + 2 position rows K24 reads in the table, a width K10 / K24 / K27 take, the fused-residual library loaded
+    (`fused_ok`), and `prefix_mask`: a right-padded attention mask (prefix_mask_lengths gave key counts), or no mask and
+    no <pad> among the ids.  Only a prefix mask is a key count; and MPNet takes its position ids from ids != <pad>, not
+    from the mask, so only in these two cases is the position row of every token a key attends to t + 2, which is what
+    K24 is given.  Otherwise 'aten'.  A pure function."""
+    ok = (flag and _hip_eligible(on_gpu, dtype, grad) and not training and D == 64 * heads
+          and 1 <= T <= core.VIT_ATTENTION_MAX_T and T + MPNET_PAD_ID + 1 <= pos_rows and D % 4 == 0 and D <= 2048
+          and 1 <= B <= MAX_BATCH and fused_ok and prefix_mask)
+    return "hip" if ok else "aten"
+
+
+class _MPNetEmbeddings(nn.Module):
+    def __init__(self, vocab, hidden, max_pos, eps):
+        super().__init__()
+        self.word_embeddings = nn.Embedding(vocab, hidden, padding_idx=MPNET_PAD_ID)
+        self.position_embeddings = nn.Embedding(max_pos, hidden, padding_idx=MPNET_PAD_ID)
+        self.LayerNorm = nn.LayerNorm(hidden, eps=eps)
+
+    def forward(self, ids, hip=False):
+        if hip and not _hooks_on(self, _MPNET_EMB_SKIPPED):
+            # K24 with the position table entered two rows down and one zero type row: LayerNorm((word + 0) + pos[t + 2]).
+            # A padded position gets row t + 2 where MPNetEmbeddings takes row 1 -- such rows are masked as keys and left
+            # out of the mean, nothing reads them.
+            n = self.LayerNorm
+            zero = _folded(self, ("LayerNorm",), lambda m: torch.zeros_like(m.LayerNorm.weight)[None])
+            return core.text_embed_ln(ids, None, self.word_embeddings.weight, self.position_embeddings.weight[MPNET_PAD_ID + 1:],
+                                      zero, n.weight, n.bias, n.eps)
+        return self.LayerNorm(self.word_embeddings(ids) + self.position_embeddings(mpnet_position_ids(ids)))
+
+
+class _MPNetSelfAttention(nn.Module):
+    """MPNetSelfAttention: q, k, v and the output projection o; the scores take an additive bias."""
+
+    def __init__(self, hidden, heads):
+        super().__init__()
+        self.heads = heads
+        self.q = nn.Linear(hidden, hidden)
+        self.k = nn.Linear(hidden, hidden)
+        self.v = nn.Linear(hidden, hidden)
+        self.o = nn.Linear(hidden, hidden)
+
+    def forward(self, x, bias=None):
+        B, T, D = x.shape
+        q, k, v = (m(x).view(B, T, self.heads, D // self.heads).transpose(1, 2) for m in (self.q, self.k, self.v))
+        return self.o(F.scaled_dot_product_attention(q, k, v, attn_mask=bias).transpose(1, 2).reshape(B, T, D))
+
+    def fused_qkv(self):
+        """(weight [3 D, D], bias [3 D]) of q | k | v as ONE projection, the [B, T, 3, heads, 64] operand K9B reads."""
+        return _folded(self, ("q", "k", "v"),
+                       lambda m: (torch.cat([m.q.weight, m.k.weight, m.v.weight]).contiguous(),
+                                  torch.cat([m.q.bias, m.k.bias, m.v.bias]).contiguous()))
+
+
+class _MPNetAttention(nn.Module):
+    def __init__(self, hidden, heads, eps):
+        super().__init__()
+        self.attn = _MPNetSelfAttention(hidden, heads)
+        self.LayerNorm = nn.LayerNorm(hidden, eps=eps)
+
+    def forward(self, x, bias=None):
+        return self.LayerNorm(self.attn(x, bias) + x)
+
+
+class _MPNetLayer(nn.Module):
+    """MPNetLayer, post-norm like BertLayer: x1 = LN(x + o(attention(x))), out = LN(x1 + fc2(gelu(fc1(x1))))."""
+
+    def __init__(self, hidden, heads, mlp, eps):
+        super().__init__()
+        self.attention = _MPNetAttention(hidden, heads, eps)
+        self.intermediate = _BertIntermediate(hidden, mlp)
+        self.output = _BertAddNorm(mlp, hidden, eps)
+
+    def forward(self, x, bias=None, lens=None, rel=None, hip=False):
+        """bias: a callable that gives the additive [B or 1, heads, T, T] SDPA mask (position bias + key mask), built
+        only if some layer takes ATen; hip (the encoder has checked sentence_route): K9B with lens (int32 [B] key counts,
+        None = all T) and rel ([heads, 2T-1]) -- unless a hook sits inside this layer."""
+        if hip and not _hooks_on(self, _MPNET_LAYER_SKIPPED):
+            return _block_hip(self._ops(), x, "relbias", (lens, rel), post=True)                             # K9B
+        x1 = self.attention(x, bias())
+        return self.output(self.intermediate(x1), x1)
+
+    def _ops(self):
+        a, o = self.attention, self.output
+        return _BlockOps(_ln_ops(a.LayerNorm), _ln_ops(o.LayerNorm), a.attn.fused_qkv(), _lin_ops(a.attn.o),
+                         _lin_ops(self.intermediate.dense), _lin_ops(o.dense), a.attn.heads)
+
+
+class _MPNetEncoder(nn.Module):
+    def __init__(self, depth, hidden, heads, mlp, eps, buckets=32):
+        super().__init__()
+        self.layer = nn.ModuleList([_MPNetLayer(hidden, heads, mlp, eps) for _ in range(depth)])
+        self.relative_attention_bias = nn.Embedding(buckets, heads)
+
+    def rel_table(self, T):
+        """[heads, 2T-1] on the weights' device: rel[h, d + T - 1] = relative_attention_bias[bucket(d), h] for the
+        key-minus-query distances d = -(T-1) .. T-1 -- every diagonal of compute_position_bias's [heads, T, T] matrix,
+        once.  Built once per T and kept on the module (again when the embedding's storage or version changes)."""
+        w = self.relative_attention_bias.weight
+        key = (w._version, w.data_ptr(), w.device, w.dtype)
+        cache = self.__dict__.setdefault("_rel_cache", {})
+        if cache.get("key") != key:
+            cache.clear()
+            cache["key"] = key
+        if T not in cache:
+            with torch.no_grad():
+                d = torch.arange(-(T - 1), T, dtype=torch.long)
+                bucket = relative_position_bucket(d, num_buckets=w.shape[0]).to(w.device)
+                cache[T] = w.detach()[bucket].t().contiguous()
+        return cache[T]
+
+    def position_bias(self, T):
+        """compute_position_bias as MPNetEncoder writes it: the buckets of the [T, T] distances on the host, the
+        embedding lookup, [1, heads, T, T].  Entry (t, j) is rel_table(T)[:, (j - t) + T - 1]."""
+        t = torch.arange(T, dtype=torch.long)
+        bucket = relative_position_bucket(t[None, :] - t[:, None], num_buckets=self.relative_attention_bias.num_embeddings)
+        return self.relative_attention_bias(bucket.to(self.relative_attention_bias.weight.device)).permute(2, 0, 1)[None]
+
+    def forward(self, x, mask=None, lens=None, hip=False):
+        T = x.shape[1]
+        rel = self.rel_table(T) if hip else None
+        made = []
+
+        def bias():
+            if not made:
+                b = self.position_bias(T).to(x.dtype)
+                if mask is not None:
+                    b = b.masked_fill(~mask.to(b.device)[:, None, None, :].bool(), float("-inf"))
+                made.append(b)
+            return made[0]
+        for layer in self.layer:
+            x = layer(x, bias, lens, rel, hip)
+        return x
+
+
+class MPNetSentenceEncoder(nn.Module):
+    """transformers.MPNetModel without its pooler, under MPNetModel's module tree and key names, with
+    sentence-transformers' Pooling(mean) + Normalize behind it: what SentenceTransformer('all-mpnet-base-v2') runs.
+    forward(tokens) -> last_hidden_state [B, T, hidden] for {input_ids, attention_mask (optional)};
+    embed(tokens) -> the unit sentence vectors [B, hidden]; encode(sentences) -> the same as a float32 numpy array, from
+    strings.  heads need not be hidden / 64, but only that width takes the HIP route.  fp32 only on the HIP route.
+    layer_norm_eps is not in a state dict: eps defaults to all-mpnet-base-v2's 1e-5."""
+
+    def __init__(self, vocab=30527, hidden=768, depth=12, heads=12, mlp=3072, max_pos=514, eps=1e-5, buckets=32):
+        super().__init__()
+        if hidden % heads:
+            raise ValueError("MPNetSentenceEncoder: hidden %d is not a multiple of %d heads" % (hidden, heads))
+        self.out_dim = hidden
+        self.heads = heads
+        self.embeddings = _MPNetEmbeddings(vocab, hidden, max_pos, eps)
+        self.encoder = _MPNetEncoder(depth, hidden, heads, mlp, eps, buckets)
+        self.tokenizer = None
+
+    @classmethod
+    def from_state_dict(cls, sd, eps=1e-5):
+        """The model of an MPNetModel state dict: sized from its shapes (heads = the columns of relative_attention_bias,
+        depth from the keys, vocabulary and position rows from the tables), pooler.* and embeddings.position_ids ignored
+        by name, floating tensors upcast to fp32, and a STRICT load: a missing or an unexpected key is an error."""
+        sd = {k: (v.float() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in sd.items()
+              if not k.startswith(_MPNET_IGNORED)}
+
+        def shape(key):
+            if key not in sd:
+                raise RuntimeError("not an MPNetModel state dict: it lacks %r (its first keys: %s)" % (key, sorted(sd)[:4]))
+            return tuple(sd[key].shape)
+        vocab, hidden = shape("embeddings.word_embeddings.weight")
+        buckets, heads = shape("encoder.relative_attention_bias.weight")
+        layer = "encoder.layer."
+        depth = 1 + max([int(k[len(layer):].split(".")[0]) for k in sd if k.startswith(layer)], default=-1)
+        if depth < 1:
+            raise RuntimeError("the state dict has no %s* keys" % layer)
+        model = cls(vocab=vocab, hidden=hidden, depth=depth, heads=heads, mlp=shape("encoder.layer.0.intermediate.dense.weight")[0],
+                    max_pos=shape("embeddings.position_embeddings.weight")[0], eps=eps, buckets=buckets)
+        model.load_state_dict(sd, strict=True)
+        return model
+
+    def route(self, ids, mask=None):
+        """(sentence_route's answer, the int32 [B] key counts on the weights' device or None) for the ids [B, T] and the
+        attention mask.  The mask is looked at where it lies: a host mask (the tokenizer's) costs no device sync.  Without
+        a mask every token is a key, <pad> tokens included, and those take position row 1, not t + 2: such ids go to ATen
+        (looking for them is one sync when the ids are on the GPU)."""
+        w = self.embeddings.word_embeddings.weight
+        B, T = ids.shape
+        lens = None if mask is None else prefix_mask_lengths(mask)
+        prefix = lens is not None if mask is not None else not bool((ids == MPNET_PAD_ID).any())
+        route = sentence_route(HIP_SENTENCE, w.is_cuda and ids.is_cuda, w.dtype, torch.is_grad_enabled(), self.training, B, T,
+                               w.shape[1], self.heads, self.embeddings.position_embeddings.num_embeddings,
+                               FUSED_RESIDUAL and core.linear_residual_available(), prefix)
+        return route, (None if lens is None or route != "hip" else lens.to(w.device))
+
+    def _hidden(self, tokens):
+        ids, mask = tokens["input_ids"], tokens.get("attention_mask")
+        route, lens = self.route(ids, mask)
+        hip = route == "hip"
+        x = self.embeddings(ids, hip)
+        if mask is not None and not hip:
+            mask = mask.to(x.device)
+        return self.encoder(x, mask, lens, hip), mask, lens, hip
+
+    def forward(self, tokens):
+        return self._hidden(tokens)[0]
+
+    def embed(self, tokens):
+        """Pooling(mean) + Normalize on forward(tokens): m = sum(x * mask) / clamp(sum(mask), 1e-9), m / max(||m||, 1e-12)."""
+        x, mask, lens, hip = self._hidden(tokens)
+        if hip:
+            return core.masked_mean_l2(x.contiguous(), lens)                                               # K27
+        m = torch.ones(x.shape[:2], device=x.device) if mask is None else mask
+        m = m.unsqueeze(-1).expand(x.size()).to(x.dtype)
+        return F.normalize(torch.sum(x * m, 1) / torch.clamp(m.sum(1), min=1e-9), p=2, dim=1)
+
+    def encode(self, sentences, batch_size=32):
+        """SentenceTransformer.encode's default: the unit sentence vectors of `sentences` as a float32 numpy array [n, hidden]
+        in input order.  Batches are taken in input order, each padded to its own longest sequence (no length-sorted
+        batching: a row's result does not depend on its batch); sequences over MPNET_MAX_TOKENS tokens are truncated
+        there, with a warning.  The tokenizer is self.tokenizer, or the registered 'mpnet' vocabulary (mpnet_tokenizer)."""
+        if isinstance(sentences, str):
+            sentences = [sentences]
+        if self.tokenizer is None:
+            self.tokenizer = mpnet_tokenizer()
+        tok = self.tokenizer
+        device = self.embeddings.word_embeddings.weight.device
+        rows = [tok.encode(s, None) for s in sentences]
+        long = sum(len(r) > MPNET_MAX_TOKENS for r in rows)
+        if long:
+            import warnings
+            warnings.warn("MPNetSentenceEncoder.encode: %d of %d sentences are over %d tokens and were truncated"
+                          % (long, len(rows), MPNET_MAX_TOKENS))
+            rows = [r if len(r) <= MPNET_MAX_TOKENS else r[:MPNET_MAX_TOKENS - 1] + [tok.sep_id] for r in rows]
+        out = torch.empty(len(rows), self.out_dim, dtype=torch.float32)
+        with torch.no_grad():
+            for i in range(0, len(rows), batch_size):
+                batch = rows[i:i + batch_size]
+                T = max(len(r) for r in batch)
+                ids = torch.full((len(batch), T), tok.pad_id, dtype=torch.long)
+                mask = torch.zeros(len(batch), T, dtype=torch.long)
+                for j, r in enumerate(batch):
+                    ids[j, :len(r)] = torch.tensor(r, dtype=torch.long)
+                    mask[j, :len(r)] = 1
+                out[i:i + len(batch)] = self.embed({"input_ids": ids.to(device), "attention_mask": mask}).float().cpu()
+        return out.numpy()
+
+
+def mpnet_tokenizer():
+    """The WordPieceTokenizer of the registered MPNet vocabulary (register_tokenizer('mpnet', path) or MCD_MPNET_VOCAB) with
+    MPNet's special tokens; without one an error -- never the hashing stand-in."""
+    entry = TOKENIZER_VOCABS.get("mpnet")
+    if entry is None and os.environ.get("MCD_MPNET_VOCAB"):
+        entry = (os.environ["MCD_MPNET_VOCAB"], True)
+    if entry is None:
+        raise RuntimeError("the MPNet sentence encoder needs its WordPiece vocabulary: call data_utils.register_tokenizer("
+                           "'mpnet', '/path/vocab.txt') or set MCD_MPNET_VOCAB=/path/vocab.txt (all-mpnet-base-v2's "
+                           "vocab.txt); there is no fallback to the hashing tokenizer")
+    try:      # MPNetTokenizer's unknown token is '[UNK]' (its default, and all-mpnet-base-v2's configuration), which that
+        #       vocabulary holds beside '<unk>'; a vocabulary without it takes '<unk>'
+        return WordPieceTokenizer(entry[0], do_lower_case=entry[1], specials=MPNET_SPECIALS[:1] + ("[UNK]",) + MPNET_SPECIALS[2:])
+    except ValueError:
+        return WordPieceTokenizer(entry[0], do_lower_case=entry[1], specials=MPNET_SPECIALS)
+
+
+SENTENCE_CHECKPOINT = {}
+
+
+def register_sentence_checkpoint(path):
+    """Where the sentence encoder's checkpoint lives: a LOCAL file holding an MPNetModel state dict (all-mpnet-base-v2's
+    pytorch_model.bin), which must exist now.  The environment variable MCD_MPNET_CKPT does the same for a process that
+    registers nothing."""
+    if not isinstance(path, str) or not os.path.isfile(path):
+        raise FileNotFoundError("register_sentence_checkpoint: %r is not an existing local file" % (path,))
+    SENTENCE_CHECKPOINT["path"] = path
+
+
+def sentence_encoder(device, ckpt=None):
+    """The MPNetSentenceEncoder of get_cos_similarity's mpnet_model argument, in eval mode on `device`: from ckpt (a state
+    dict or a LOCAL path), else from the registered checkpoint (register_sentence_checkpoint / MCD_MPNET_CKPT).  Files are
+    read with weights_only=True; the load is strict.  Nothing is downloaded: without a checkpoint this is an error."""
+    ckpt = ckpt if ckpt is not None else SENTENCE_CHECKPOINT.get("path") or os.environ.get("MCD_MPNET_CKPT")
+    if ckpt is None:
+        raise RuntimeError("the sentence encoder needs a local MPNetModel checkpoint: pass ckpt=, call "
+                           "data_utils.register_sentence_checkpoint('/path/pytorch_model.bin') or set MCD_MPNET_CKPT")
+    return MPNetSentenceEncoder.from_state_dict(_state_dict_of(ckpt)).to(device).eval()
 
 
 # target name -> a LOCAL checkpoint of that target, like register_clip_checkpoint for the dissector

@@ -9,6 +9,7 @@ Kept names and contracts (reference concept_vit/utils.py):
                                     return_target_feats=True, device="cuda", d_probe="vindr", top_k=100)  :566-612
     get_clip_feats(clip_save_name, text_save_name, device="cuda", d_probe="vindr")                    :670-702
     _all_saved / _make_save_dir                                                                       :648-668
+    get_cos_similarity(preds, gt, clip_model, mpnet_model, device="cuda", batch_size=200)             :618-646
 
 What differs, deliberately:
   * models and probe data come from the offline factory (data_utils): nothing is downloaded;
@@ -24,6 +25,7 @@ import os
 import re
 import threading
 
+import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
@@ -589,3 +591,30 @@ def get_similarity_from_activations(target_save_name, clip_save_name, text_save_
     if return_target_feats:
         return similarity, target_feats
     return similarity
+
+
+def _unit_text_rows(clip_model, tokenizer, strings, context, device, batch_size):
+    """[n, embed_dim]: clip_model.encode_text of `strings`, batch_size rows a call, every row divided by its L2 norm."""
+    ids = tokenizer(strings, context_length=context).to(device)
+    with torch.no_grad():
+        rows = torch.cat([clip_model.encode_text(chunk) for chunk in ids.split(batch_size)])
+    return rows / rows.norm(dim=-1, keepdim=True)
+
+
+def get_cos_similarity(preds, gt, clip_model, mpnet_model, device="cuda", batch_size=200):
+    """reference :618-646: the mean cosine between predicted and ground-truth concept strings (two lists of one length) in
+    CLIP text space and in sentence space, as two Python floats.  clip_model: anything with encode_text (OpenAIClip: K9A,
+    K25); the ids come from the registered CLIP merges file at the model's context length (data_utils.clip_tokenizer --
+    without one an error that names register_tokenizer('clip', ...), never the hashing tokenizer), and a string over that
+    length is an error, as in clip.tokenize.  mpnet_model: anything with SentenceTransformer's encode
+    (data_utils.sentence_encoder: K9B, K27), which returns unit rows.  The row norms and the row-wise dot products are
+    torch's and numpy's: n x 512 numbers."""
+    preds, gt = list(preds), list(gt)
+    if len(preds) != len(gt):
+        raise ValueError("get_cos_similarity: %d predictions for %d ground-truth strings" % (len(preds), len(gt)))
+    tokenizer = data_utils.clip_tokenizer()
+    context = getattr(clip_model, "context_length", 77)
+    in_clip = (_unit_text_rows(clip_model, tokenizer, preds, context, device, batch_size)
+               * _unit_text_rows(clip_model, tokenizer, gt, context, device, batch_size)).sum(dim=1).mean()
+    in_mpnet = (np.asarray(mpnet_model.encode(preds)) * np.asarray(mpnet_model.encode(gt))).sum(axis=1).mean()
+    return float(in_clip), float(in_mpnet)

@@ -469,6 +469,56 @@ def vit_attention_keylen(qkv, heads, lens, out=None):
     return out
 
 
+# ---- K9B -----------------------------------------------------------------------------------------
+@_on_device
+def vit_attention_relbias(qkv, heads, lens, rel, out=None):
+    """vit_attention_keylen with a bias per head and key-minus-query distance added to the scores (K9B,
+    include/mcd_sentence.h): rel a contiguous float32 [heads, 2T-1] tensor, rel[h, (j - t) + T - 1] the bias of key j for
+    query t, or None (vit_attention_keylen's bits).  Valid rows t < L attend to the L valid keys; the padded query rows are
+    written but carry a clamped bias -- nothing may read them.  Of rel only the distances |d| < L of a sequence are read."""
+    _need_gpu(qkv, lens, rel)
+    if qkv.dtype != torch.float32 or qkv.dim() != 3 or not qkv.is_contiguous():
+        raise TypeError("qkv must be a contiguous float32 [B, T, 3*heads*64] tensor")
+    B, T, W = qkv.shape
+    if W != 3 * heads * 64:
+        raise ValueError("qkv last dimension %d is not 3 * %d heads * 64" % (W, heads))
+    if lens is not None and (lens.dtype != torch.int32 or tuple(lens.shape) != (B,) or not lens.is_contiguous()
+                             or lens.device != qkv.device):
+        raise TypeError("lens must be a contiguous int32 [B] tensor on qkv's device (or None)")
+    if rel is not None and (rel.dtype != torch.float32 or tuple(rel.shape) != (heads, 2 * T - 1) or not rel.is_contiguous()
+                            or rel.device != qkv.device):
+        raise TypeError("rel must be a contiguous float32 [heads, 2T-1] tensor on qkv's device (or None)")
+    if out is None:
+        out = torch.empty((B, T, heads * 64), dtype=torch.float32, device=qkv.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, T, heads * 64) or not out.is_contiguous():
+        raise TypeError("out must be a contiguous float32 [B, T, heads*64] tensor")
+    check(_lib.load().mcd_vit_attention_relbias(qkv.data_ptr(), B, T, heads, None if lens is None else lens.data_ptr(),
+                                                None if rel is None else rel.data_ptr(), out.data_ptr(), _stream()))
+    return out
+
+
+# ---- K27 -----------------------------------------------------------------------------------------
+@_on_device
+def masked_mean_l2(x, lens, normalize=True, out=None):
+    """The mean of the first L = clamp(lens[b], 1, T) token rows of every sequence, L2-normalised unless normalize is
+    False, in one launch (K27, include/mcd_sentence.h): x a contiguous float32 [B, T, D] tensor, lens a contiguous int32
+    [B] tensor on x's device or None (L = T) -> [B, D].  sentence-transformers' Pooling(mean) + Normalize."""
+    _need_gpu(x, lens, out)
+    if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous():
+        raise TypeError("x must be a contiguous float32 [B, T, D] tensor")
+    B, T, D = x.shape
+    if lens is not None and (lens.dtype != torch.int32 or tuple(lens.shape) != (B,) or not lens.is_contiguous()
+                             or lens.device != x.device):
+        raise TypeError("lens must be a contiguous int32 [B] tensor on x's device (or None)")
+    if out is None:
+        out = torch.empty((B, D), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, D) or not out.is_contiguous():
+        raise TypeError("out must be a contiguous float32 [B, D] tensor")
+    check(_lib.load().mcd_masked_mean_l2(x.data_ptr(), B, T, D, None if lens is None else lens.data_ptr(),
+                                         1 if normalize else 0, out.data_ptr(), _stream()))
+    return out
+
+
 # ---- K9A -----------------------------------------------------------------------------------------
 @_on_device
 def vit_attention_causal(qkv, heads, out=None):

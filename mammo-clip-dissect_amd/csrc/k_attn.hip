@@ -61,6 +61,7 @@
 #include "mcd_common.h"
 #include "../../include/mcd_text.h"
 #include "../../include/mcd_clip.h"
+#include "../../include/mcd_sentence.h"
 
 namespace {
 
@@ -72,6 +73,7 @@ constexpr int AT_LONG_MAX_T = 32768;   // the long form (2048 x 2048 at patch 16
 constexpr int AT_HALF = 32 * 256;  // bytes of a K (or V) tile
 constexpr int AT_STAGE = 2 * AT_HALF;
 constexpr int AT_NSTAGE = 4;       // ring of tiles: two pairs
+constexpr int AT_REL = 2 * AT_MAX_T + 32;   // K9B's staged biases: 2T-1 distances + the masked keys of a short last tile
 
 // The workgroup body of both forms: queries q0 .. q0 + 32 * ncw - 1 of head h of image b, one compute wave per 32 of
 // them (waves 0 .. ncw-1), wave ncw the loader; all ntile key tiles of (b, h) go through the LDS ring.  Which block a
@@ -81,10 +83,26 @@ constexpr int AT_NSTAGE = 4;       // ring of tiles: two pairs
 // row strides and the query count.  Without KEYLEN the key count IS T (L is not looked at): K9 and K9L as they were.
 // CAUSAL (K9A): query q sees keys 0 .. q.  The loader stages every tile as always; compute wave w walks tiles
 // 0 .. (q0 / 32) + w, masks the keys above each lane's query in the last of them, and idles through the pair barriers left.
-template <bool KEYLEN, bool CAUSAL = false>
+// BIAS (K9B): rel points at this head's 2T-1 biases, one per key-minus-query distance d = -(T-1) .. T-1.  All waves stage
+// them once, times log2(e) (the scores live in the log2 domain), into at_rel[d + T - 1], and the tile loop adds
+// at_rel[key - q + T - 1] to every score in front of the mask.  Only the distances |d| <= L-1 of the sequence's own L keys
+// are read from global memory: a padded query row t >= L takes the bias of d = -(L-1) for the distances below it, and the
+// slots that only masked keys of the last tile address (d up to L + 30) hold zero.  A query lane past T works on row T-1,
+// as its q fragment does.  Lanes 0 .. 31 of a read address 32 consecutive floats: no bank conflict.
+template <bool KEYLEN, bool CAUSAL = false, bool BIAS = false>
 __device__ __forceinline__ void attn_block(const float* __restrict__ qkv, int T, int H, int64_t b, int h, int q0, int ncw,
-                                           int L, float* __restrict__ out) {
+                                           int L, float* __restrict__ out, const float* __restrict__ rel = nullptr) {
     __shared__ __attribute__((aligned(1024))) char at_lds[AT_NSTAGE * AT_STAGE];   // [stage][K | V][32 rows x 256 B]
+    const float* rel_s = nullptr;
+    if constexpr (BIAS) {
+        __shared__ float at_rel[AT_REL];
+        for (int i = threadIdx.x; i < AT_REL; i += blockDim.x) {
+            const int d = i - (T - 1);
+            at_rel[i] = d < L ? rel[max(d, 1 - L) + T - 1] * 1.44269504088896340736f : 0.f;
+        }
+        rel_s = at_rel;
+        __syncthreads();
+    }
     const int TK = KEYLEN ? L : T;     // keys
     const int ntile = (TK + 31) >> 5;
     const int64_t row_stride = (int64_t)3 * H * AT_D;                 // floats between two tokens of qkv
@@ -158,6 +176,7 @@ __device__ __forceinline__ void attn_block(const float* __restrict__ qkv, int T,
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
     float m = -INFINITY, l = 0.f;
+    const int rel_q = T - 1 - (q < T ? q : T - 1) + 4 * half;   // BIAS: at_rel index of this lane's key 0 of tile 0
 
     // CAUSAL: the diagonal tile is this wave's last (it exists: wave < ncw and q0 + 32 * wave < T for every launched wave)
     const int ntile_w = CAUSAL ? min(ntile, (q0 >> 5) + wave + 1) : ntile;
@@ -184,6 +203,11 @@ __device__ __forceinline__ void attn_block(const float* __restrict__ qkv, int T,
             c = __builtin_amdgcn_mfma_f32_32x32x2f32(ka.y, Qr[4 * j + 1], c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_32x32x2f32(ka.z, Qr[4 * j + 2], c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_32x32x2f32(ka.w, Qr[4 * j + 3], c, 0, 0, 0);
+        }
+        if constexpr (BIAS) {
+            const float* rb = rel_s + rel_q + kt * 32;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) c[r] += rb[(r & 3) + 8 * (r >> 2)];
         }
         if constexpr (CAUSAL) {
             // the diagonal tile: key 32 kt + j is above query 32 kt + ql when j > ql.  That covers the keys past T of a
@@ -282,6 +306,23 @@ __global__ __launch_bounds__(576, 4) void vit_attention_keylen_kernel(const floa
     int L = T;
     if (lens) L = min(max(lens[b], 1), T);
     attn_block<true>(qkv, T, H, b, h, 0, ncw, __builtin_amdgcn_readfirstlane(L), out);
+}
+
+// K9B: K9M with the per-head relative-position bias of MPNet's attention added to every score (include/mcd_sentence.h).
+//     transformers MPNetSelfAttention.forward: attention_scores / 8 + position_bias (+ the key mask)
+// The bias of MPNetEncoder.compute_position_bias is a function of head and key - query alone -- a Toeplitz matrix per head,
+// the same in every layer and for every sequence -- so the operand is the [H, 2T-1] table of its diagonals, never [H, T, T].
+__global__ __launch_bounds__(576, 4) void vit_attention_relbias_kernel(const float* __restrict__ qkv, int T, int H,
+                                                                        const int32_t* __restrict__ lens,
+                                                                        const float* __restrict__ rel,
+                                                                        float* __restrict__ out) {
+    const int ncw = (T + 31) >> 5;
+    const int h = blockIdx.x;
+    const int64_t b = blockIdx.y;
+    int L = T;
+    if (lens) L = min(max(lens[b], 1), T);
+    attn_block<true, false, true>(qkv, T, H, b, h, 0, ncw, __builtin_amdgcn_readfirstlane(L), out,
+                                  rel + (int64_t)h * (2 * T - 1));
 }
 
 // K9A: K9's grid and waves under the causal mask.
@@ -454,6 +495,31 @@ extern "C" int mcd_vit_attention_keylen(const float* qkv, int64_t B, int64_t T, 
     hipLaunchKernelGGL(vit_attention_keylen_kernel, dim3((unsigned)H, (unsigned)B), dim3(64 * nwaves), 0, (hipStream_t)stream,
                        qkv, (int)T, (int)H, lens, out);
     MCD_LAUNCH_CHECK("vit_attention_keylen_kernel");
+    return MCD_OK;
+}
+
+extern "C" int mcd_vit_attention_relbias(const float* qkv, int64_t B, int64_t T, int64_t H, const int32_t* lens,
+                                         const float* rel, float* out, mcd_stream_t stream) {
+    MCD_REQUIRE(qkv && out, MCD_E_ARG, "mcd_vit_attention_relbias: NULL pointer");
+    MCD_REQUIRE(B >= 0 && T >= 1 && H >= 1, MCD_E_ARG, "mcd_vit_attention_relbias: bad shape B=%lld T=%lld H=%lld",
+                (long long)B, (long long)T, (long long)H);
+    MCD_REQUIRE(T <= AT_MAX_T, MCD_E_UNSUPPORTED,
+                "mcd_vit_attention_relbias: T=%lld tokens, at most %d (one wave per 32 queries, 8 waves)", (long long)T, AT_MAX_T);
+    MCD_REQUIRE(B <= 65535 && H <= 65535, MCD_E_UNSUPPORTED, "mcd_vit_attention_relbias: B and H must be <= 65535");
+    MCD_REQUIRE(((uintptr_t)qkv) % 16 == 0 && ((uintptr_t)out) % 16 == 0 && ((uintptr_t)lens) % 4 == 0 &&
+                    ((uintptr_t)rel) % 16 == 0,
+                MCD_E_ARG, "mcd_vit_attention_relbias: qkv, out and rel must be 16-byte aligned, lens 4-byte aligned");
+    if (B == 0) return MCD_OK;
+    const int nwaves = (int)((T + 31) / 32) + 1;   // one per 32 queries + the loader
+    if (!rel) {                                    // no bias: K9M's own kernel, K9M's bits
+        hipLaunchKernelGGL(vit_attention_keylen_kernel, dim3((unsigned)H, (unsigned)B), dim3(64 * nwaves), 0,
+                           (hipStream_t)stream, qkv, (int)T, (int)H, lens, out);
+        MCD_LAUNCH_CHECK("vit_attention_keylen_kernel");
+        return MCD_OK;
+    }
+    hipLaunchKernelGGL(vit_attention_relbias_kernel, dim3((unsigned)H, (unsigned)B), dim3(64 * nwaves), 0, (hipStream_t)stream,
+                       qkv, (int)T, (int)H, lens, rel, out);
+    MCD_LAUNCH_CHECK("vit_attention_relbias_kernel");
     return MCD_OK;
 }
 
