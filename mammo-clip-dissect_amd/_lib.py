@@ -78,6 +78,11 @@ SENTENCE_SIGNATURES = {
     "mcd_vit_attention_relbias": (_int, [_p, _i64, _i64, _i64, _p, _p, _p, _p]),
     "mcd_masked_mean_l2": (_int, [_p, _int, _int, _int, _p, _int, _p, _p]),
 }
+# the masked-autoencoder entries of the same library, declared in include/mcd_mask.h (additive to ABI version 9)
+MASK_SIGNATURES = {
+    "mcd_patchify_kept": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p]),
+    "mcd_token_restore": (_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p]),
+}
 # the activation-cache streaming entries of the same library, declared in include/mcd_cache.h (additive to ABI version 9)
 _pp = ctypes.POINTER(_p)
 CACHE_SIGNATURES = {
@@ -116,7 +121,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(CLIP_SIGNATURES.items())
                                   + list(TOKEN_SIGNATURES.items()) + list(SENTENCE_SIGNATURES.items())
-                                  + list(CACHE_SIGNATURES.items())):
+                                  + list(MASK_SIGNATURES.items()) + list(CACHE_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

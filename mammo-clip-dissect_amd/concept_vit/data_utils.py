@@ -21,6 +21,8 @@ dissection core they feed is the HIP library.
     openai_clip            visual.transformer.resblocks[i], transformer.resblocks[i]   OpenAI CLIP under its own keys (ckpt=)
     vit / -cub / -bloodmnist   vit.encoder.layer[0..11]                HF ViT-B/16 classifier: 12 x 768
     dino / -cub / -bloodmnist  dinov2.encoder.layer[0..11]             HF DINOv2-base classifier (patch 14): 12 x 768
+    mae                    vit.encoder.layer[0..11]                    HF ViT-MAE-base (with a checkpoint, ckpt= or registered:
+                                                                       HFMae = ViTMAEForPreTraining): 12 x 768
 """
 import collections
 import math
@@ -1275,9 +1277,9 @@ class HFTower(ViTTower):
             m.position_embeddings.detach(), P, H, W), extra=(H, W))
 
 
-def _hf_layer_map(prefix, i, dino):
-    """transformers-4.41.1 module names of encoder layer i -> this mirror's (q / k / v are handled apart)."""
-    base = "%s.encoder.layer.%d." % (prefix, i)
+def _hf_layer_map(prefix, i, dino, stem="encoder.layer"):
+    """transformers-4.41.1 module names of layer i of the list prefix.stem -> this mirror's (q / k / v are handled apart)."""
+    base = "%s.%s.%d." % (prefix, stem, i)
     names = {"attention.output.dense": "attn.proj"}
     if dino:                                         # norm1 / norm2 / layer_scale1 / layer_scale2 keep their names
         names.update({"mlp.fc1": "fc1", "mlp.fc2": "fc2"})
@@ -1287,24 +1289,25 @@ def _hf_layer_map(prefix, i, dino):
     return {base + a + "." + leaf: base + b + "." + leaf for a, b in names.items() for leaf in ("weight", "bias")}
 
 
-def hf_state_dict(sd, prefix, depth):
+def hf_state_dict(sd, prefix, depth, stem="encoder.layer"):
     """A ViTForImageClassification / Dinov2ForImageClassification state dict with transformers-4.41.1 key names (the
     reference's pin) -> the mirror's: the query / key / value projections of a layer concatenated into attn.qkv, the
     other modules renamed, DINOv2's mask_token dropped (it only enters masked-image pre-training).  Keys that are the
-    mirror's already pass through, so a dict saved from the mirror loads as well."""
+    mirror's already pass through, so a dict saved from the mirror loads as well.  stem: the layer list under `prefix`
+    (ViTMAEForPreTraining's decoder keeps the same layers in decoder.decoder_layers)."""
     dino = prefix == "dinov2"
     sd = dict(sd)
     sd.pop(prefix + ".embeddings.mask_token", None)
     out = {}
     for i in range(depth):
-        base = "%s.encoder.layer.%d." % (prefix, i)
+        base = "%s.%s.%d." % (prefix, stem, i)
         for leaf in ("weight", "bias"):
             parts = [sd.pop(base + "attention.attention.%s.%s" % (n, leaf), None) for n in ("query", "key", "value")]
             if all(t is not None for t in parts):
                 out[base + "attn.qkv." + leaf] = torch.cat(parts, dim=0)
             elif any(t is not None for t in parts):
                 raise KeyError("%sattention.attention: query, key and value %s must come together" % (base, leaf))
-        for old, new in _hf_layer_map(prefix, i, dino).items():
+        for old, new in _hf_layer_map(prefix, i, dino, stem).items():
             if old in sd:
                 out[new] = sd.pop(old)
     out.update(sd)
@@ -2566,6 +2569,248 @@ class HFClip(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------------
+# ViT-MAE (the `mae` row of the reference's MODELS table, data_utils.py:21-36 and :65-66: facebook/vit-mae-base behind
+# AutoModelForPreTraining = transformers' ViTMAEForPreTraining)
+# ------------------------------------------------------------------------------------------------------
+# HFMae's inference route (HFMae.route): K28 (the kept patches' pixel rows) + one GEMM whose residual operand K29 gathers from
+# the position table, _block_hip for every encoder layer, K10, the decoder_embed GEMM, K29 (mask-token fill, un-shuffle,
+# position add), _block_hip for the decoder layers (SDPA inside at 32-wide heads), K10, the decoder_pred GEMM; the loss on
+# ATen.  MCD_NO_HIP_MAE=1 (or setting this to False) keeps the modules' own forward: the convolution over all patches,
+# gather, cat, repeat and the unfused blocks (whose LayerNorm and attention stay under HIP_LAYER_NORM / HIP_ATTENTION, as in
+# HFViT).
+HIP_MAE = os.environ.get("MCD_NO_HIP_MAE", "0") != "1"
+MAE_KEYS = ("vit.embeddings.cls_token", "decoder.mask_token")      # what tells a ViTMAEForPreTraining state dict
+MaeOutput = collections.namedtuple("MaeOutput", "loss logits mask ids_restore")
+
+
+def _plain_call(mod, x):
+    """mod(x) for an nn.Linear on the HIP route: through __call__ when a hook (the module's or a global one) must fire."""
+    if _hooked(mod) or _nn_module._global_forward_hooks or _nn_module._global_forward_pre_hooks:
+        return mod(x)
+    return _linear(mod, x)
+
+
+class _MaeLayer(_Block):
+    """ViTMAELayer: _Block (pre-norm, LayerNorm eps 1e-12, exact GELU) whose caller decides the route.  hip=True: _Block's
+    own choice (_block_hip unless a hook sits inside); hip=False: the submodules one by one."""
+
+    def forward(self, x, hip=True):
+        if hip:
+            return super().forward(x)
+        x = x + self.attn(self.norm1(x))
+        return x + self.fc2(F.gelu(self.fc1(self.norm2(x))))
+
+
+class _MaeEncoder(nn.Module):
+    def __init__(self, depth, dim, heads, mlp):
+        super().__init__()
+        self.layer = nn.ModuleList([_MaeLayer(dim, heads, mlp, eps=1e-12) for _ in range(depth)])
+
+    def forward(self, x, hip=False):
+        for layer in self.layer:                     # through __call__: the hooks on layer[i] fire
+            x = layer(x, hip)
+        return x
+
+
+class _MaeViT(nn.Module):
+    """ViTMAEModel: embeddings (cls_token, position_embeddings, patch_embeddings.projection), encoder.layer[i], layernorm.
+    forward(x, ids_keep) embeds the patches ids_keep [B, Lk] names, puts the class token in front and returns
+    layernorm(encoder(.)) as [B, 1 + Lk, D]."""
+
+    def __init__(self, dim, image_size, patch, depth, heads, mlp):
+        super().__init__()
+        self.image_size, self.patch = image_size, patch
+        self.embeddings = _HFEmbeddings(dim, patch, (image_size // patch) ** 2)
+        self.encoder = _MaeEncoder(depth, dim, heads, mlp)
+        self.layernorm = _LayerNorm(dim, eps=1e-12)
+
+    def embed(self, x, ids_keep, hip=False):
+        emb = self.embeddings
+        conv, pos = emb.patch_embeddings.projection, emb.position_embeddings
+        if hip and not _hooks_on(self, ("embeddings",)):
+            # K28: the pixel rows of the kept patches alone (a zero row in the class-token slot); K29: their position rows
+            # (and cls_token + position 0 - bias in row 0) out of one table; one GEMM with the bias and that residual operand
+            keep = ids_keep.to(torch.int32).contiguous()
+            res = core.token_restore(self._class_pos_table(), keep)
+            return core.linear_residual(res, core.patchify_kept(x, self.patch, keep), conv.weight.view(conv.out_channels, -1),
+                                        conv.bias, out=res)
+        t = conv(x).flatten(2).transpose(1, 2) + pos[:, 1:]
+        t = torch.gather(t, 1, ids_keep.unsqueeze(-1).expand(-1, -1, t.shape[2]))
+        return torch.cat([(emb.cls_token + pos[:, :1]).expand(t.shape[0], -1, -1), t], dim=1)
+
+    def _class_pos_table(self):
+        """[1 + L, D]: a COPY of the position table with cls_token + its row 0 - bias in row 0 (the GEMM adds the bias
+        back): the class/position trick of _class_pos_residual on one table for all images, which K29 then gathers."""
+        def build(m):
+            table = m.position_embeddings.detach()[0].clone()
+            table[0] += m.cls_token.detach()[0, 0] - m.patch_embeddings.projection.bias.detach()
+            return table
+        return _folded(self.embeddings, ("position_embeddings", "cls_token", "patch_embeddings"), build)
+
+    def forward(self, x, ids_keep, hip=False):
+        return self.layernorm(self.encoder(self.embed(x, ids_keep, hip), hip))
+
+
+class _MaeDecoder(nn.Module):
+    """ViTMAEDecoder: decoder_embed, mask_token, decoder_pos_embed, decoder_layers[i], decoder_norm, decoder_pred.
+    forward(latent [B, 1 + Lk, D], ids_restore [B, L]) -> the pixel predictions [B, L, patch^2 * 3] (the class row dropped)."""
+
+    def __init__(self, dim, num_patches, width, depth, heads, mlp, out_dim):
+        super().__init__()
+        self.mask_token = nn.Parameter(torch.zeros(1, 1, width))
+        self.decoder_pos_embed = nn.Parameter(torch.zeros(1, num_patches + 1, width), requires_grad=False)
+        self.decoder_embed = nn.Linear(dim, width)
+        self.decoder_layers = nn.ModuleList([_MaeLayer(width, heads, mlp, eps=1e-12) for _ in range(depth)])
+        self.decoder_norm = _LayerNorm(width, eps=1e-12)
+        self.decoder_pred = nn.Linear(width, out_dim)
+
+    def forward(self, latent, ids_restore, hip=False):
+        if hip:
+            # K29: mask tokens behind the kept rows, the un-shuffle, the class row in front and + decoder_pos_embed, one launch
+            h = core.token_restore(_plain_call(self.decoder_embed, latent), ids_restore.to(torch.int32).contiguous(),
+                                   self.mask_token.detach().view(-1), self.decoder_pos_embed.detach()[0])
+        else:
+            h = self.decoder_embed(latent)
+            B, L = ids_restore.shape
+            tokens = torch.cat([h[:, 1:], self.mask_token.repeat(B, L + 1 - h.shape[1], 1)], dim=1)
+            tokens = torch.gather(tokens, 1, ids_restore.unsqueeze(-1).repeat(1, 1, h.shape[2]))
+            h = torch.cat([h[:, :1], tokens], dim=1) + self.decoder_pos_embed
+        for layer in self.decoder_layers:
+            h = layer(h, hip)
+        h = self.decoder_norm(h)
+        return (_plain_call(self.decoder_pred, h) if hip else self.decoder_pred(h))[:, 1:]
+
+
+def mae_config(sd, heads=None, decoder_heads=None):
+    """HFMae's constructor arguments read from the shapes of a ViTMAEForPreTraining state dict (transformers-4.41.1 key
+    names, or the mirror's own): the width from cls_token, the patch from the projection, the grid (and with it the
+    resolution) from the position rows, the depths by counting layers, the MLP widths from the first layer, the decoder's
+    width from mask_token.  The state dict does not carry the head counts: width // 64 for the encoder (every ViT-MAE
+    encoder has 64-wide heads) and width // 32 for the decoder (facebook/vit-mae-base, -large and -huge: 16 heads on 512)
+    unless `heads` / `decoder_heads` say otherwise."""
+    def shape(*keys):
+        for key in keys:
+            if key in sd:
+                return tuple(sd[key].shape)
+        raise RuntimeError("not a ViTMAEForPreTraining state dict: it lacks %r" % (keys[0],))
+
+    def depth(stem):
+        return len([k for k in sd if k.startswith(stem) and k.endswith((".layernorm_before.weight", ".norm1.weight"))])
+    hidden = shape(MAE_KEYS[0])[2]
+    patch = shape("vit.embeddings.patch_embeddings.projection.weight")[2]
+    rows = shape("vit.embeddings.position_embeddings")[1]
+    grid = round((rows - 1) ** 0.5)
+    if grid * grid + 1 != rows:
+        raise RuntimeError("vit.embeddings.position_embeddings has %d rows: not a square grid plus one" % rows)
+    if shape("decoder.decoder_pos_embed")[1] != rows:
+        raise RuntimeError("decoder.decoder_pos_embed has %d rows, vit.embeddings.position_embeddings %d"
+                           % (shape("decoder.decoder_pos_embed")[1], rows))
+    width = shape(MAE_KEYS[1])[2]
+    layers, dlayers = depth("vit.encoder.layer."), depth("decoder.decoder_layers.")
+    return dict(image_size=grid * patch, patch=patch, hidden=hidden, layers=layers, heads=heads or max(1, hidden // 64),
+                mlp=shape("vit.encoder.layer.0.intermediate.dense.weight", "vit.encoder.layer.0.fc1.weight")[0] if layers
+                else 4 * hidden,
+                decoder_hidden=width, decoder_layers=dlayers, decoder_heads=decoder_heads or max(1, width // 32),
+                decoder_mlp=shape("decoder.decoder_layers.0.intermediate.dense.weight", "decoder.decoder_layers.0.fc1.weight")[0]
+                if dlayers else 4 * width)
+
+
+class HFMae(nn.Module):
+    """transformers' ViTMAEForPreTraining (the reference's `mae` target, facebook/vit-mae-base; the defaults are its
+    configuration).  Module tree: vit.embeddings.{cls_token, position_embeddings, patch_embeddings.projection},
+    vit.encoder.layer[i], vit.layernorm, decoder.{mask_token, decoder_pos_embed, decoder_embed, decoder_layers[i],
+    decoder_norm, decoder_pred}.  A layer is a _Block (attn.qkv, attn.proj, norm1, norm2, fc1, fc2); convert_state_dict maps
+    the transformers-4.41.1 names of a real checkpoint (attention.attention.{query,key,value}, attention.output.dense,
+    layernorm_before / after, intermediate.dense, output.dense) onto them and from_state_dict loads STRICTLY.  The two
+    position tables are the fixed sin-cos tables the checkpoint stores; they are loaded, never regenerated.
+
+    forward(pixel_values, noise=None) -> MaeOutput(loss, logits, mask, ids_restore), transformers' steps: the patch embedding
+    + position_embeddings[:, 1:]; len_keep = int(L * (1 - mask_ratio)); ids_shuffle = argsort(noise), ids_restore =
+    argsort(ids_shuffle); the first len_keep patches of the shuffle are kept; mask [B, L] is 0 on kept patches and 1 on
+    removed ones, in patch order; cls_token + position_embeddings[:, :1] in front; the encoder layers; vit.layernorm;
+    decoder_embed; L - len_keep mask tokens appended behind the kept rows and gathered by ids_restore; the class row back in
+    front; + decoder_pos_embed; the decoder layers; decoder_norm; decoder_pred; the class row dropped; loss = the mean
+    squared error per patch against patchify(pixel_values) ((dy, dx, c) order; per-patch normalised under norm_pix_loss),
+    averaged over the removed patches.  noise=None draws torch.rand(B, L, device=...) from torch's global generator, as
+    transformers does: the mask of a dissection run is random unless the caller seeds torch.
+    Hook points: vit.encoder.layer[i]; an output is [B, 1 + len_keep, D] and a dissection hook reads token 0.  vit.layernorm
+    and the decoder read every row: the last block always runs whole.  encode_image is forward."""
+
+    def __init__(self, image_size=224, patch=16, hidden=768, layers=12, heads=12, mlp=3072, decoder_hidden=512,
+                 decoder_layers=8, decoder_heads=16, decoder_mlp=2048, mask_ratio=0.75, norm_pix_loss=False):
+        super().__init__()
+        if not isinstance(image_size, int):
+            raise ValueError("HFMae: image_size must be an int (the position table is a square grid), got %r" % (image_size,))
+        self.mask_ratio, self.norm_pix_loss = float(mask_ratio), bool(norm_pix_loss)
+        self.num_patches = (image_size // patch) ** 2
+        self.vit = _MaeViT(hidden, image_size, patch, layers, heads, mlp)
+        self.decoder = _MaeDecoder(hidden, self.num_patches, decoder_hidden, decoder_layers, decoder_heads, decoder_mlp,
+                                   patch * patch * 3)
+
+    def convert_state_dict(self, sd):
+        sd = hf_state_dict(sd, "vit", len(self.vit.encoder.layer))
+        return hf_state_dict(sd, "decoder", len(self.decoder.decoder_layers), stem="decoder_layers")
+
+    @classmethod
+    def from_state_dict(cls, sd, heads=None, decoder_heads=None, mask_ratio=0.75, norm_pix_loss=False):
+        """The model of a ViTMAEForPreTraining state dict: sized by mae_config, fp16 tensors upcast, loaded STRICTLY -- a
+        missing or an unexpected key is an error, never a tower of random weights."""
+        sd = {k: (v.float() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in sd.items()}
+        model = cls(mask_ratio=mask_ratio, norm_pix_loss=norm_pix_loss, **mae_config(sd, heads, decoder_heads))
+        sd = model.convert_state_dict(sd)
+        want = set(model.state_dict())
+        missing, unexpected = sorted(want - set(sd)), sorted(set(sd) - want)
+        if missing or unexpected:
+            raise RuntimeError("the checkpoint does not match ViTMAEForPreTraining: %d missing key(s) %s, %d unexpected "
+                               "key(s) %s" % (len(missing), missing[:4], len(unexpected), unexpected[:4]))
+        model.load_state_dict(sd, strict=True)
+        return model
+
+    def patchify(self, x):
+        """[B, 3, H, W] -> [B, L, patch^2 * 3], a patch's pixels in transformers' (dy, dx, c) order."""
+        B, C, P = x.shape[0], x.shape[1], self.vit.patch
+        g = x.shape[2] // P
+        return x.reshape(B, C, g, P, g, P).permute(0, 2, 4, 3, 5, 1).reshape(B, g * g, P * P * C)
+
+    def route(self, x):
+        v, d = self.vit, self.decoder
+        conv = v.embeddings.patch_embeddings.projection
+        ok = (_tower_gate(HIP_MAE, self, x) and x.shape[0] >= 1 and x.is_contiguous() and x.shape[1] == conv.in_channels
+              and conv.bias is not None
+              and embed_gate(v.patch, x.shape[2], x.shape[3], v.embeddings.position_embeddings.shape[1])
+              and conv.out_channels % 4 == 0 and d.decoder_embed.out_features % 4 == 0
+              and _under_2g(x.shape[1] * x.shape[2] * x.shape[3],
+                            (1 + self.num_patches) * max(conv.out_channels, d.decoder_embed.out_features,
+                                                         conv.weight[0].numel())))
+        return "hip" if ok else "aten"
+
+    def forward(self, pixel_values, noise=None):
+        size = self.vit.image_size
+        if pixel_values.dim() != 4 or tuple(pixel_values.shape[2:]) != (size, size):
+            raise ValueError("Input image size (%s) doesn't match model (%d*%d)."
+                             % ("*".join(str(s) for s in pixel_values.shape[2:]), size, size))
+        x = pixel_values.to(self.vit.embeddings.cls_token.dtype)
+        B, L = x.shape[0], self.num_patches
+        len_keep = int(L * (1 - self.mask_ratio))
+        if noise is None:
+            noise = torch.rand(B, L, device=x.device)
+        ids_shuffle = torch.argsort(noise, dim=1).to(x.device)
+        ids_restore = torch.argsort(ids_shuffle, dim=1)
+        mask = (ids_restore >= len_keep).to(torch.get_default_dtype())      # the 0 / 1 row of the shuffle, gathered by ids_restore
+        hip = self.route(x) == "hip"
+        latent = self.vit(x, ids_shuffle[:, :len_keep], hip)
+        logits = self.decoder(latent, ids_restore, hip)
+        target = self.patchify(x)
+        if self.norm_pix_loss:
+            target = (target - target.mean(dim=-1, keepdim=True)) / (target.var(dim=-1, keepdim=True) + 1.0e-6) ** 0.5
+        loss = ((logits - target) ** 2).mean(dim=-1)
+        return MaeOutput((loss * mask).sum() / mask.sum(), logits, mask, ids_restore)
+
+    def encode_image(self, image, noise=None):
+        return self(image, noise)
+
+
+# ------------------------------------------------------------------------------------------------------
 # The sentence encoder of get_cos_similarity (reference concept_vit/utils.py:618-646: SentenceTransformer
 # 'all-mpnet-base-v2'.encode): transformers.MPNetModel under its own names + sentence-transformers' Pooling(mean) + Normalize
 # ------------------------------------------------------------------------------------------------------
@@ -2962,7 +3207,7 @@ def _load_local(model, ckpt, text_strict=False):
     if ckpt is None:
         return model
     sd = _state_dict_of(ckpt)
-    if isinstance(model, _HFClassifier):             # transformers' key names -> the mirror's
+    if isinstance(model, (_HFClassifier, HFMae)):    # transformers' key names -> the mirror's
         sd = model.convert_state_dict(sd)
     if text_strict:
         sd = {k: v for k, v in sd.items() if not k.startswith(_BERT_IGNORED)}
@@ -3012,7 +3257,8 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
     has keys starting text_encoder.text_encoder. (a Mammo-CLIP checkpoint), else the stand-in.  The BERT tower's hidden
     size, depth, intermediate size, vocabulary and position rows are read from the checkpoint's shapes.
     use_registered (clip): False keeps the checkpoint registered for the `clip` TARGET out of this call -- the drivers build
-    their stand-in DISSECTOR under the same name (og_utils._clip_dissector)."""
+    their stand-in DISSECTOR under the same name (og_utils._clip_dissector).
+    `mae` exists only with a checkpoint (ckpt= holding MAE_KEYS, or one registered for `mae`): HFMae sized from it."""
     if text_tower not in (None, "stand-in", "bert"):
         raise ValueError("text_tower must be None, 'stand-in' or 'bert', got %r" % (text_tower,))
     if target_name == "openai_clip":
@@ -3040,6 +3286,23 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
             with torch.random.fork_rng(devices=[]):
                 torch.manual_seed(seed)
                 model = HFClip.from_state_dict(sd, n_class=n_class)
+            _load_local(model, finetuned_ckpt)
+            return model.to(device).eval(), None
+    if target_name == "mae":
+        # transformers' ViTMAEForPreTraining, and only from a checkpoint of it: `ckpt` itself when it carries MAE_KEYS (or is
+        # the registered file), else the one registered for `mae`.  Sized from the shapes and loaded strictly; n_class is
+        # ignored (the model has no classifier).  Without either the name stays unknown (the ValueError below): a seeded
+        # stand-in of a pre-training model would dissect nothing anybody trained.
+        sd = None
+        if ckpt is not None:
+            loaded = _state_dict_of(ckpt)
+            if isinstance(ckpt, RegisteredCheckpoint) or (isinstance(loaded, dict) and all(k in loaded for k in MAE_KEYS)):
+                sd = loaded
+        if sd is None and use_registered:
+            registered = target_checkpoint("mae")
+            sd = None if registered is None else _state_dict_of(registered)
+        if sd is not None:
+            model = HFMae.from_state_dict(sd)
             _load_local(model, finetuned_ckpt)
             return model.to(device).eval(), None
     text_kw = {}
@@ -3087,7 +3350,8 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
             raise ValueError("unknown target model %r (offline build: breastclip, breastclip_vit, "
                              "breastclip_classifier, clip, openai_clip, clip_rn50, clip_rn101, resnet18, resnet18_places, resnet34, "
                              "resnet50, resnet101, resnet152, vit, vit-cub, vit-bloodmnist, dino, dino-cub, "
-                             "dino-bloodmnist)" % (target_name,))
+                             "dino-bloodmnist).  mae is built from a ViTMAEForPreTraining checkpoint only: pass ckpt= or "
+                             "register one (register_target_checkpoint('mae', path))" % (target_name,))
     if target_name == "resnet18_places":
         _load_places(model, ckpt)
     else:

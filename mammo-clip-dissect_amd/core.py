@@ -662,6 +662,61 @@ def patchify(x, patch):
     return out
 
 
+# ---- K28 -----------------------------------------------------------------------------------------
+def _index_rows(t, B, name):
+    """A contiguous int32 [B, n] index list on the GPU (K28's keep, K29's restore)."""
+    _need_gpu(t)
+    if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != B or not t.is_contiguous():
+        raise TypeError("%s must be a contiguous int32 [B, n] tensor" % name)
+    return t
+
+
+@_on_device
+def patchify_kept(x, patch, keep):
+    """patchify for the patches keep [B, Lk] names (int32 patch numbers, row-major over the patch grid) and no others, in
+    one launch (K28, include/mcd_mask.h): [B, Cin, H, W] -> [B, 1 + Lk, Cin*patch*patch], row 0 of every image zero, row
+    1 + j patch keep[b, j] in (c, dy, dx) order.  The kernel clamps an index into the grid."""
+    B, Cin, H, W = _nchw_image(x, "patchify_kept: contiguous float32 [B, Cin, H, W]").shape
+    if H % patch or W % patch:
+        raise ValueError("patchify_kept: %dx%d is not a multiple of the %d-pixel patch" % (H, W, patch))
+    Lk = _index_rows(keep, B, "keep").shape[1]
+    out = torch.empty((B, 1 + Lk, Cin * patch * patch), dtype=torch.float32, device=x.device)
+    check(_lib.load().mcd_patchify_kept(x.data_ptr(), keep.data_ptr(), B, Cin, H, W, patch, Lk, out.data_ptr(), _stream()))
+    return out
+
+
+# ---- K29 -----------------------------------------------------------------------------------------
+@_on_device
+def token_restore(src, restore, fill=None, add=None, out=None):
+    """Rows gathered through an index list, a fill row past the source, a table added, in one launch (K29,
+    include/mcd_mask.h).  src: contiguous float32 [B, 1 + Lk, D], or [1 + Lk, D] -- one table shared by all images;
+    restore: contiguous int32 [B, L]; fill: [D] or None; add: [1 + L, D] or None -> [B, 1 + L, D] with
+    out[b, 0] = src[b, 0] + add[0] and out[b, t] = (r < Lk ? src[b, 1 + r] : fill) + add[t], r = restore[b, t - 1].
+    fill None: r is clamped to Lk - 1 and no row is filled.  The decoder of a masked autoencoder (fill = the mask token,
+    add = its position table), and, with a shared table, fill = add = None, the position rows of the kept patches."""
+    _need_gpu(src, restore, fill, add, out)
+    if src.dtype != torch.float32 or src.dim() not in (2, 3) or not src.is_contiguous():
+        raise TypeError("src must be a contiguous float32 [B, 1 + Lk, D] or [1 + Lk, D] tensor")
+    B = restore.shape[0] if restore.dim() == 2 else -1
+    if src.dim() == 3 and src.shape[0] != B:
+        raise ValueError("token_restore: src has %d images, restore %s" % (src.shape[0], tuple(restore.shape)))
+    L = _index_rows(restore, B, "restore").shape[1]
+    rows, D = src.shape[-2], src.shape[-1]
+    if rows < 1:
+        raise ValueError("token_restore: src has no row 0")
+    for name, t, shape in (("fill", fill, (D,)), ("add", add, (1 + L, D))):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise TypeError("%s must be a contiguous float32 tensor of shape %s" % (name, shape))
+    if out is None:
+        out = torch.empty((B, 1 + L, D), dtype=torch.float32, device=src.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, 1 + L, D) or not out.is_contiguous():
+        raise TypeError("out must be a contiguous float32 [B, 1 + L, D] tensor")
+    check(_lib.load().mcd_token_restore(src.data_ptr(), rows * D if src.dim() == 3 else 0, restore.data_ptr(),
+                                        None if fill is None else fill.data_ptr(), None if add is None else add.data_ptr(),
+                                        B, L, rows - 1, D, out.data_ptr(), _stream()))
+    return out
+
+
 # ---- K12 - K15: the EfficientNet-B5 tower on channels-last activations (csrc/k_mbconv.hip) ----------------------
 DWCONV_TILE = 8      # K13's SE partial sums: one per 8 x 8 tile of output pixels
 
