@@ -93,6 +93,11 @@ CACHE_SIGNATURES = {
     "mcd_cache_stream_close": (_int, [_p]),
     "mcd_cache_stream_abort": (_int, [_p]),
 }
+# the class-token fold entries of the same library, declared in include/mcd_clsfold.h (additive to ABI version 9)
+CLSFOLD_SIGNATURES = {
+    "mcd_cls_token_mix": (_int, [_p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _i64, _p]),
+    "mcd_cls_token_mix_max_t": (_i64, [_i64, _i64]),
+}
 
 MCD_E_ARG = -1
 MCD_E_RANGE = -2
@@ -121,7 +126,8 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(CLIP_SIGNATURES.items())
                                   + list(TOKEN_SIGNATURES.items()) + list(SENTENCE_SIGNATURES.items())
-                                  + list(MASK_SIGNATURES.items()) + list(CACHE_SIGNATURES.items())):
+                                  + list(MASK_SIGNATURES.items()) + list(CACHE_SIGNATURES.items())
+                                  + list(CLSFOLD_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -55,6 +55,15 @@ FUSED_RESIDUAL = os.environ.get("MCD_NO_FUSED_RESIDUAL", "0") != "1"
 # K and V for all tokens and everything else (q, attention on K9C, proj, the MLP, the final LayerNorm) for the class
 # token alone and returns [B, 1, D] (cls_tail_route).  MCD_NO_CLS_ONLY_TAIL=1 (or False here) keeps the full block.
 CLS_ONLY_TAIL = os.environ.get("MCD_NO_CLS_ONLY_TAIL", "0") != "1"
+# The class-token tail without its K|V projection (cls_fold_route, _attend_cls_folded): the one query row needs
+# q_h . k_t = (W_k,h^T q_h) . n_t and sum_t p_t v_t = W_v,h (sum_t p_t n_t) + b_v,h, so W_k and W_v are applied to one
+# row per image and K30 (core.cls_token_mix) does the rest on LN1(x).  MCD_NO_CLS_FOLD=1 (or False here) keeps the K|V
+# GEMM + K9C.  The fold trades one GEMM of B*T rows for 2 * heads + 1 launches that do not shrink with the batch, so it is
+# taken from CLS_FOLD_MIN_ROWS token rows (B*T) up.  Measured on the ViT-B/16 tail block (scripts/cls_fold_timing.py,
+# profiles/cls_fold_timing.txt): the folded tail takes 0.73 ms at any small batch (its launches), the K|V GEMM + K9C
+# 0.59 ms at 25 216 rows and 1.10 ms at 50 432; the two cross near 32 000 rows.  At 492 500 rows: 1.74 against 9.31 ms.
+CLS_FOLD = os.environ.get("MCD_NO_CLS_FOLD", "0") != "1"
+CLS_FOLD_MIN_ROWS = 32768
 
 
 # nn.LayerNorm of the towers on the HIP kernel K10 (csrc/k_ln.hip); MCD_NO_HIP_LAYER_NORM=1 keeps ATen's.
@@ -159,6 +168,14 @@ def cls_tail_route(flag, fused_ok, masked, training, T, D, heads, depth, hooks_c
                 and 1 <= T <= core.VIT_ATTENTION_CLS_MAX_T and depth >= 1 and hooks_clear and last_hooks_token0)
 
 
+def cls_fold_route(flag, B, T, D, heads, min_rows):
+    """Whether a class-token tail that cls_tail_route has opened also folds its K|V projection away: CLS_FOLD (`flag`),
+    at least `min_rows` token rows in the call (CLS_FOLD_MIN_ROWS) and K30's limits -- D = 64 * heads <= 2 048, T within
+    its LDS budget, B within its grid."""
+    return bool(flag and B * T >= min_rows and D == 64 * heads and D <= 2048 and 1 <= B <= core.CLS_TOKEN_MIX_MAX_B
+                and 1 <= T <= core.cls_token_mix_max_t(heads, D))
+
+
 def embed_gate(P, H, W, table_rows):
     """Whether ViTTower.embed may write the patch embedding as K11 + one GEMM: an even patch size (K11 reads 16-byte
     pieces of a patch row at P % 4 == 0, 8-byte pieces at any other even P, and nothing narrower), an image of whole
@@ -232,9 +249,33 @@ def _attend_cls(q, kv):
     return core.vit_attention_cls(q, kv[:, :, 0], kv[:, :, 1])
 
 
+_LOG2E = 1.4426950408889634
+
+
+def _attend_cls_folded(owner, qkv, heads, q, n):
+    """_attend_cls without K and V (CLS_FOLD): q [B, D] the class token's query, n [B, T, D] = LN1(x) -> [B, D].
+    u[:, h] = q_h W_k,h * log2(e)/8 and o_h = W_v,h m_h + b_v,h are `heads` GEMMs of B rows each (K = 64, then N = 64),
+    K30 between them turns u and n into m.  W_k is read through a transposed copy [heads, D, 64] with the scale folded in,
+    built once per weight (_folded on `owner`, the module that holds the qkv parameters)."""
+    w, b = qkv
+    B, T, D = n.shape
+    wkt = _folded(owner, (), lambda m: (w.detach()[D:2 * D].view(heads, 64, D).transpose(1, 2) * (_LOG2E / 8.0)).contiguous(),
+                  own=True)
+    u = torch.empty((B, heads, D), dtype=n.dtype, device=n.device)
+    for h in range(heads):
+        core.linear_residual(None, q[:, 64 * h:64 * h + 64], wkt[h], None, out=u[:, h])
+    m = core.cls_token_mix(u, n)
+    o = torch.empty((B, D), dtype=n.dtype, device=n.device)
+    for h in range(heads):
+        r = slice(2 * D + 64 * h, 2 * D + 64 * h + 64)
+        core.linear_residual(None, m[:, h], w[r], None if b is None else b[r], out=o[:, 64 * h:64 * h + 64])
+    return o
+
+
 # The operands of one transformer block on the HIP route (_block_hip): ln1 / ln2 as (weight, bias, eps), qkv / proj / fc1 /
-# fc2 as (weight, bias), the head count.  Each block class builds it from its own parameters (its _ops()).
-_BlockOps = collections.namedtuple("_BlockOps", "ln1 ln2 qkv proj fc1 fc2 heads")
+# fc2 as (weight, bias), the head count; owner: the module whose parameters the qkv pair is (the cache of the folded tail's
+# derived weight hangs on it; None: no fold).  Each block class builds it from its own parameters (its _ops()).
+_BlockOps = collections.namedtuple("_BlockOps", "ln1 ln2 qkv proj fc1 fc2 heads owner", defaults=(None,))
 
 
 def _ln_ops(ln):
@@ -267,12 +308,16 @@ def _block_hip(p, x, attn, attn_arg=None, post=False, act=_gelu, cls_only=False,
     cls_only (pre-norm; the caller has checked cls_tail_route): the class-token row of the same block, as [B, 1, D].  K and
     V need every token -- ln1 and the K|V two thirds of the qkv projection run on all rows -- everything after them is
     computed for row 0 of each image only.  The weight slices are contiguous views, x[:, 0] and ln1(x)[:, 0] go into the
-    GEMMs as row-strided operands: no copies."""
+    GEMMs as row-strided operands: no copies.  Where cls_fold_route agrees, the K|V projection is folded out as well
+    (_attend_cls_folded): ln1 on all rows, K30 on its output, and every GEMM of the block has B rows."""
     B, T, D = x.shape
     x = x.contiguous()
     n = x if post else _norm(x, p.ln1, k10)
     w, b = p.qkv
-    if cls_only:
+    if cls_only and p.owner is not None and cls_fold_route(CLS_FOLD, B, T, D, p.heads, CLS_FOLD_MIN_ROWS):
+        o = _attend_cls_folded(p.owner, p.qkv, p.heads, core.linear_residual(None, n[:, 0], w[:D], None if b is None else b[:D]), n)
+        x = x[:, 0]
+    elif cls_only:
         kv = core.linear_residual(None, n, w[D:], None if b is None else b[D:]).view(B, T, 2, p.heads, D // p.heads)
         o = _attend_cls(core.linear_residual(None, n[:, 0], w[:D], None if b is None else b[:D]), kv)
         x = x[:, 0]
@@ -354,7 +399,7 @@ class _Block(nn.Module):
     def _ops(self):
         wp, bp, w2, b2 = self._residual_weights()
         return _BlockOps(_ln_ops(self.norm1), _ln_ops(self.norm2), _lin_ops(self.attn.qkv), (wp, bp), _lin_ops(self.fc1),
-                         (w2, b2), self.attn.heads)
+                         (w2, b2), self.attn.heads, self.attn)
 
     def _residual_weights(self):
         """(proj weight, proj bias, fc2 weight, fc2 bias) of the two fused residual GEMMs.  With LayerScale,
@@ -1916,7 +1961,7 @@ class _ClipResBlock(nn.Module):
     def _ops(self):
         a, m = self.attn, self.mlp
         return _BlockOps(_ln_ops(self.ln_1), _ln_ops(self.ln_2), (a.in_proj_weight, a.in_proj_bias), _lin_ops(a.out_proj),
-                         _lin_ops(m.c_fc), _lin_ops(m.c_proj), a.heads)
+                         _lin_ops(m.c_fc), _lin_ops(m.c_proj), a.heads, a)
 
 
 class _ClipTransformer(nn.Module):

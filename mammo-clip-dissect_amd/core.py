@@ -597,6 +597,45 @@ def vit_attention_cls(q, k, v, out=None):
     return out
 
 
+# ---- K30 -----------------------------------------------------------------------------------------
+CLS_TOKEN_MIX_MAX_B = 65535
+
+
+def cls_token_mix_max_t(heads, D):
+    """The most tokens cls_token_mix takes for `heads` score vectors of width D (its scores stay in LDS); 0 when heads and
+    D themselves are refused (D a multiple of 64 * heads, at most 2 048)."""
+    return int(_lib.load().mcd_cls_token_mix_max_t(int(heads), int(D)))
+
+
+@_on_device
+def cls_token_mix(u, n, out=None):
+    """m[b, h] = sum_t softmax_t(u[b, h] . n[b, t]) n[b, t] in one launch (K30, include/mcd_clsfold.h): u [B, heads, D], the
+    score vectors already scaled by log2(e)/8, n [B, T, D] -> [B, heads, D].  fp32; the operands are read where they lie:
+    u and out with any image stride (an image's heads*D floats adjacent), n with any token and image strides (a view of
+    a larger tensor).  D a multiple of 64 * heads and at most 2 048, 1 <= T <= cls_token_mix_max_t(heads, D),
+    B <= CLS_TOKEN_MIX_MAX_B."""
+    _need_gpu(u, n, out)
+    if u.dtype != torch.float32 or n.dtype != torch.float32 or u.dim() != 3 or n.dim() != 3:
+        raise TypeError("cls_token_mix: float32 u [B, heads, D] and n [B, T, D]")
+    B, H, D = u.shape
+    T = n.shape[1]
+    if n.shape[0] != B or n.shape[2] != D:
+        raise ValueError("cls_token_mix: u has shape %s, n %s" % (tuple(u.shape), tuple(n.shape)))
+    if u.stride(2) != 1 or n.stride(2) != 1 or (H > 1 and u.stride(1) != D):
+        raise ValueError("cls_token_mix: the D floats of a row, and the heads of an image in u, must be adjacent")
+    if out is None:
+        out = torch.empty((B, H, D), dtype=torch.float32, device=n.device)
+    elif (out.dtype != torch.float32 or tuple(out.shape) != (B, H, D) or out.stride(2) != 1
+          or (H > 1 and out.stride(1) != D)):
+        raise TypeError("out must be a float32 [B, heads, D] tensor with an image's heads*D floats adjacent")
+    u_img, m_img = (t.stride(0) if B > 1 else H * D for t in (u, out))
+    n_row = n.stride(1) if T > 1 else D
+    n_img = n.stride(0) if B > 1 else max(T * n_row, D)
+    check(_lib.load().mcd_cls_token_mix(u.data_ptr(), u_img, n.data_ptr(), n_row, n_img, B, T, H, D, out.data_ptr(), m_img,
+                                        _stream()))
+    return out
+
+
 # ---- K10 -----------------------------------------------------------------------------------------
 @_on_device
 def layer_norm(x, weight, bias, eps):
@@ -1014,8 +1053,9 @@ def linear_residual(res, h, weight, bias=None, out=None, relu=False):
     """out = res + h @ weight.T + bias in ONE hipBLASLt GEMM (bias epilogue + beta*C), instead of nn.Linear followed
     by an elementwise add over the whole residual stream.  res, h: [..., N] / [..., K] contiguous fp32 with the same
     leading shape; weight [N, K]; out defaults to a new tensor (pass out=res for in place).  res may be None.
-    A 2-D h or res may also be row-strided (unit inner stride, rows at least their width apart, e.g. x[:, 0] of a
-    [B, T, K] tensor): the GEMM reads the rows where they lie, with the true leading dimension.
+    A 2-D h, res or out may also be row-strided (unit inner stride, rows at least their width apart, e.g. x[:, 0] of a
+    [B, T, K] tensor, or a column block o[:, 64:128] to write): the GEMM reads and writes the rows where they lie, with
+    the true leading dimension.
     relu=True: out = relu(res + h @ weight.T + bias), the library's ReLU epilogue (mcd_linear_residual_relu; its plans
     and picks are kept apart from the plain entry's)."""
     L = _lib.load_blaslt()
@@ -1028,11 +1068,13 @@ def linear_residual(res, h, weight, bias=None, out=None, relu=False):
         raise ValueError("linear_residual: shapes h %s, weight %s, res %s do not match"
                          % (tuple(h.shape), tuple(weight.shape), None if res is None else tuple(res.shape)))
     for t in (h, weight, bias, res, out):
-        if t is not None and (t.dtype != torch.float32 or not (t.is_contiguous() or (t is h or t is res) and _row_strided(t))):
-            raise TypeError("linear_residual: contiguous float32 tensors only (h and res: or 2-D row-strided)")
+        if t is not None and (t.dtype != torch.float32
+                              or not (t.is_contiguous() or (t is h or t is res or t is out) and _row_strided(t))):
+            raise TypeError("linear_residual: contiguous float32 tensors only (h, res and out: or 2-D row-strided)")
     M = h.numel() // K
     ldh = K if h.is_contiguous() else h.stride(0)
     ldr = N if res is None or res.is_contiguous() else res.stride(0)
+    ldo = N if out is None or out.is_contiguous() else out.stride(0)
     if out is None:
         out = torch.empty(h.shape[:-1] + (N,), dtype=torch.float32, device=h.device)
     elif tuple(out.shape) != tuple(h.shape[:-1]) + (N,):
@@ -1046,7 +1088,7 @@ def linear_residual(res, h, weight, bias=None, out=None, relu=False):
         e0.record()
     fn = L.mcd_linear_residual_relu if relu else L.mcd_linear_residual
     rc = fn(h.data_ptr(), ldh, weight.data_ptr(), K, bias.data_ptr() if bias is not None else None,
-            res.data_ptr() if res is not None else None, ldr, out.data_ptr(), N, M, N, K, ws.data_ptr(), ws.numel(), _stream())
+            res.data_ptr() if res is not None else None, ldr, out.data_ptr(), ldo, M, N, K, ws.data_ptr(), ws.numel(), _stream())
     if ev is not None:
         e1.record()
         ev.append((e0, e1, M, N, K))
