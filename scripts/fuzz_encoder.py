@@ -1,0 +1,34 @@
+"""Randomised differential test of the encoder-side entries -- the attention family (K9, K9L, K9M, K9A, K9B), the one-row entries
+(K9C, K30) and the token / row operations (K10, K24, K25, K26, K27, K28, K29) -- with tests/encoder_fuzz.py: stratified case lists
+of consecutive seeds, float64 references from the headers, the headers' bit relations and read sets, every operand in a frame.
+argv: [cases per entry] [seed] [--entries K9 K9M ...]"""
+import argparse
+import os
+import sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import torch
+import mammo_clip_dissect_amd as mcd
+import encoder_fuzz as E
+
+ap = argparse.ArgumentParser()
+ap.add_argument("cases", nargs="?", type=int, default=600)
+ap.add_argument("seed", nargs="?", type=int, default=0)
+ap.add_argument("--entries", nargs="+", default=list(E.ENTRIES), choices=E.ENTRIES)
+args = ap.parse_args()
+dev = torch.device("cuda:0")
+call = E.gpu_call(mcd._lib.load())
+bad, top, done = 0, {}, 0
+for entry in args.entries:
+    top[entry] = 0.0
+    for case in E.random_cases(entry, args.cases, args.seed):
+        findings, ratio = E.check(entry, case, call, dev)
+        for f in findings:
+            print("MISMATCH " + f, flush=True)
+        bad += len(findings)
+        top[entry] = max(top[entry], ratio)
+        done += 1
+        if done % 50 == 0:
+            print("%d cases, %d mismatches; max err / bound: %s" % (done, bad, " ".join("%s %.3f" % kv for kv in top.items())), flush=True)
+print("done: %d cases, %d mismatches; max err / bound: %s" % (done, bad, " ".join("%s %.3f" % kv for kv in top.items())))
+sys.exit(1 if bad else 0)

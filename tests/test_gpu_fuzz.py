@@ -69,3 +69,40 @@ def test_similarity_functions_fuzz(dev):
         assert e.value.code == 0
     finally:
         sys.argv = argv
+
+
+# ---- the encoder side: tests/encoder_fuzz.py on the library, every operand in a frame -------------------------------------
+import encoder_fuzz as E  # noqa: E402  (touches no GPU on import)
+
+
+@pytest.fixture(scope="module")
+def encoder_call(mcd, dev):
+    return E.gpu_call(mcd._lib.load())
+
+
+def _encoder_fuzz(entry, call, dev):
+    """The committed case list of one entry (E.SEEDS): float64 and the headers' bit relations, read sets and frames."""
+    case_list = E.cases(entry, E.SEEDS[entry])
+    findings, ratio = E.run(entry, case_list, call, dev)
+    print("%s: %d cases, %d findings, max err / bound %.3f" % (entry, len(case_list), len(findings), ratio))
+    assert not findings, "\n".join(findings[:20])
+
+
+@pytest.mark.parametrize("entry", E.ATTENTION)
+def test_attention_family_fuzz(encoder_call, dev, entry):
+    """K9, K9L, K9M, K9A, K9B over every (query wave, key tile, last-tile fill) class, lens at tile edges and clamped, rel NULL /
+    zero / random, under every value regime (rising and falling scores, a dominant last-tile key, a zero K row, V = 100 + randn)."""
+    _encoder_fuzz(entry, encoder_call, dev)
+
+
+@pytest.mark.parametrize("entry", E.CLS_ROW)
+def test_cls_row_fuzz(encoder_call, dev, entry):
+    """K9C under random strides up to the four-wave split; K30 over every (H, D) instance, padded strides, and just above every
+    token count at which its heads per pass fall (B = 1 there)."""
+    _encoder_fuzz(entry, encoder_call, dev)
+
+
+@pytest.mark.parametrize("entry", E.TOKEN_OPS)
+def test_token_ops_fuzz(encoder_call, dev, entry):
+    """K10 / K25 against float64 at their own tests' tolerances; K24, K26, K27, K28, K29 on the bits their headers spell out."""
+    _encoder_fuzz(entry, encoder_call, dev)
