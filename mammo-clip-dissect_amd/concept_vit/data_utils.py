@@ -9,9 +9,14 @@ LOCAL checkpoint path.  These modules are host-side PyTorch plumbing (the encode
 dissection core they feed is the HIP library.
 
     target_name            hook points (target_layers)                 neurons
-    breastclip             image_encoder._blocks[0..38]                EfficientNet-B5: 6992
+    breastclip             image_encoder._blocks[0..38]                EfficientNet-B5: 6992 (with a checkpoint: the tower
+                                                                       its keys name -- EfficientNet b0 .. b7, B2 = the
+                                                                       second released Mammo-CLIP, 23 blocks; or Swin)
     breastclip_vit         image_encoder.encoder.layer[0..11]          ViT-B/16: 12 x 768
-    breastclip_classifier  image_encoder._blocks[0..38]                + linear head (n_class)
+    breastclip_swin        image_encoder.image_encoder.encoder.layers[0..3] (and .blocks[j])   Swin-T: 192/384/768/768
+                                                                       (sized from a checkpoint's shapes when one is given)
+    breastclip_classifier  image_encoder._blocks[0..38]                + linear head (n_class); the tower follows the
+                                                                       checkpoint as for breastclip
     clip                   vision_model.encoder.layers[0..11]          CLIP ViT-B/16: 12 x 768 (with a checkpoint, ckpt= or
                                                                        registered: HFClip = CLIPForImageClassification)
     resnet50 / 101 / 152   conv1, layer1..layer4                       64/256/512/1024/2048
@@ -216,7 +221,8 @@ def _attend(qkv, heads, choice, arg=None):
     """The concatenated head outputs [B, T, D] of the fused projection's output qkv [B, T, 3 D] -- attention before the
     output projection -- on the kernel `choice` names: 'k9' (K9), 'long' (K9L: one workgroup per 256 queries of a head, no
     T x T buffer), 'causal' (K9A), 'keylen' (K9M, arg: the int32 [B] key counts or None), 'relbias' (K9B, arg: the key
-    counts and the [heads, 2T-1] bias table) or 'sdpa' (PyTorch's, arg: the mask or None).  The HIP kernels
+    counts and the [heads, 2T-1] bias table), 'window' / 'window-aten' (Swin's shifted windows on K31 / on ATen, arg: the
+    grid, window, shift, bias table and a padded token's qkv) or 'sdpa' (PyTorch's, arg: the mask or None).  The HIP kernels
     (csrc/k_attn.hip) read the projection's layout and write the proj input's."""
     B, T, D = qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3
     if choice == "k9":
@@ -239,6 +245,10 @@ def _attend(qkv, heads, choice, arg=None):
         return core.vit_attention_keylen(qkv, heads, arg)
     if choice == "relbias":
         return core.vit_attention_relbias(qkv, heads, *arg)
+    if choice == "window":                                   # K31, arg: (grid, window, shift, table, pad_qkv)
+        return core.window_attention(qkv, *arg)
+    if choice == "window-aten":                              # the same operands through ATen (windows K31 does not take)
+        return _window_attend_aten(qkv, heads, *arg)
     q, k, v = qkv.view(B, T, 3, heads, D // heads).permute(2, 0, 3, 1, 4)
     o = F.scaled_dot_product_attention(q, k, v, attn_mask=arg)
     return o.transpose(1, 2).reshape(B, T, D)
@@ -749,6 +759,9 @@ class EfficientNetB5Tower(nn.Module):
         return f
 
 
+EfficientNetTower = EfficientNetB5Tower       # the class at any compound scaling (width, depth): B5 is its default only
+
+
 # ------------------------------------------------------------------------------------------------------
 # text tower (BERT-base shaped) + offline tokenizer
 # ------------------------------------------------------------------------------------------------------
@@ -1168,14 +1181,19 @@ class BreastClip(nn.Module):
     'vit' = ViT-B/16 (reference model/modules/image_encoder.py:14-52, CLS token model/clip.py:49-52).
     text tower: 'stand-in' (the default) = TextTower + HashTokenizer; 'bert' = the reference's own, HFTextEncoder around
     BertTextTower (bert_config: its constructor arguments) with the WordPiece tokenizer of the registered vocabulary.
-    text_pooling: 'eos' (the default), 'bos' or 'mean' (model/clip.py:66-77)."""
+    text_pooling: 'eos' (the default), 'bos' or 'mean' (model/clip.py:66-77).
+    'swin' = HFImageEncoder around a SwinTower (swin_config: its constructor arguments, swin-tiny's by default), token 0 of
+    its last_hidden_state as the image feature (model/clip.py:49-52).  width / depth: the EfficientNet's compound-scaling
+    coefficients ('cnn' only; B5's by default, 1.1 / 1.2 give B2, out_dim 1408)."""
 
     def __init__(self, image_tower="cnn", image_size=224, text_depth=12, text_tower="stand-in", bert_config=None,
-                 text_pooling="eos"):
+                 text_pooling="eos", swin_config=None, width=1.6, depth=2.2):
         super().__init__()
         self.model_type = image_tower
         if image_tower == "cnn":
-            self.image_encoder = EfficientNetB5Tower()
+            self.image_encoder = EfficientNetTower(width, depth)
+        elif image_tower == "swin":
+            self.image_encoder = HFImageEncoder(SwinTower(**(swin_config or SWIN_TINY)))
         else:
             self.image_encoder = ViTTower(image_size=image_size)
         if text_tower not in ("stand-in", "bert"):
@@ -1191,6 +1209,8 @@ class BreastClip(nn.Module):
     def encode_image(self, image):
         if self.model_type == "cnn":
             return self.image_encoder(image)
+        if self.model_type == "swin":
+            return self.image_encoder(image)[:, 0]
         return self.image_encoder(image, cls_only=True)[:, 0]
 
     def encode_text(self, text_tokens):
@@ -1223,18 +1243,27 @@ class BreastClip(nn.Module):
 
 class BreastClipClassifier(nn.Module):
     """Fine-tuned classifier target (reference Classifiers/models/breast_clip_classifier.py:6-81):
-    EfficientNet-B5 image encoder + linear head; forward(images) -> logits [B, n_class]."""
+    EfficientNet-B5 image encoder + linear head; forward(images) -> logits [B, n_class].
+    width / depth: the EfficientNet's compound-scaling coefficients (1.1 / 1.2: B2, out_dim 1408).  image_tower='swin': the
+    reference's other branch, HFImageEncoder around a SwinTower (swin_config) and token 0 of its output; the images are
+    [B, 3, H, W] like everywhere in this package (the reference's forward permutes its dataset's channels-last batch)."""
 
-    def __init__(self, n_class=1):
+    def __init__(self, n_class=1, image_tower="cnn", swin_config=None, width=1.6, depth=2.2):
         super().__init__()
-        self.image_encoder = EfficientNetB5Tower()
+        self.model_type = image_tower
+        if image_tower == "swin":
+            self.image_encoder = HFImageEncoder(SwinTower(**(swin_config or SWIN_TINY)))
+        else:
+            self.image_encoder = EfficientNetTower(width, depth)
         self.classifier = nn.Linear(self.image_encoder.out_dim, n_class)
 
     def encode_image(self, image):
+        if self.model_type == "swin":
+            return self.image_encoder(image)[:, 0]
         return self.image_encoder(image)
 
     def forward(self, images):
-        return self.classifier(self.image_encoder(images))
+        return self.classifier(self.encode_image(images))
 
 
 class ClipViT(nn.Module):
@@ -2856,6 +2885,408 @@ class HFMae(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------------
+# The Swin image tower (reference model/modules/image_encoder.py:27-28, :50-52: `source: huggingface, model_type: swin`,
+# transformers.SwinModel, last_hidden_state) under transformers-4.41.1's names, pooler excluded (nothing reads it)
+# ------------------------------------------------------------------------------------------------------
+# SwinTower's inference route (swin_route): per block K10, the fused q|k|v GEMM, K31 (the attention inside shifted windows:
+# padding, roll, partition, bias, mask, softmax, P.V, reverse in one launch), the two residual GEMMs and ATen's erf GELU
+# (_block_hip with the 'window' attention); per stage end K32 (the 2x2 gather under LayerNorm) and the reduction GEMM.  A
+# block whose window holds more than 64 tokens or whose heads are not 32 wide keeps ATen for its attention alone; a merge
+# wider than K32 takes (4C > 2048: Swin-L's last) is ATen's.  The 4x4 patch convolution stays ATen's.  MCD_NO_HIP_SWIN=1
+# (or setting this to False) keeps the ATen route of the same modules: pad, roll, view / permute, bmm, softmax, bmm.
+HIP_SWIN = os.environ.get("MCD_NO_HIP_SWIN", "0") != "1"
+SWIN_KEY = "embeddings.patch_embeddings.projection.weight"     # what tells a SwinModel state dict (under its prefix)
+SWIN_MASK = -100.0                                             # transformers' shift-mask value: not -inf
+SWIN_TINY = dict(patch=4, width=96, depths=(2, 2, 6, 2), heads=(3, 6, 12, 24), window=7, mlp_ratio=4.0)   # microsoft/swin-tiny-patch4-window7-224
+_SWIN_LAYER_SKIPPED = ("layernorm_before", "attention", "layernorm_after", "intermediate", "output")
+_SWIN_MERGE_SKIPPED = ("norm", "reduction")
+_SWIN_IGNORED = "attention.self.relative_position_index"       # a buffer of index arithmetic: recomputed, never loaded
+
+
+def swin_route(flag, on_gpu, dtype, grad, training, fused_ok, B):
+    """'hip' when a SwinTower forward may leave ATen: HIP_SWIN (`flag`), the base gate (fp32 on the GPU, no autograd), eval
+    mode, the fused-residual path available for the call (`fused_ok`) and a batch K31's grid takes; 'aten' otherwise."""
+    ok = flag and _hip_eligible(on_gpu, dtype, grad) and not training and fused_ok and 1 <= B <= MAX_BATCH
+    return "hip" if ok else "aten"
+
+
+def swin_attention_route(window, dim, heads, tokens):
+    """Which attention a block on the HIP route takes: 'window' (K31) for a window of at most 64 tokens, heads 32 wide and
+    one image's qkv under 2^31 bytes; 'window-aten' (the same operands through ATen) otherwise."""
+    ok = (1 <= window <= core.WINDOW_ATTENTION_MAX_W and dim == core.WINDOW_ATTENTION_HEAD * heads and heads <= MAX_BATCH
+          and _under_2g(tokens * 3 * dim))
+    return "window" if ok else "window-aten"
+
+
+def swin_merge_route(dim, tokens):
+    """'k32' when a stage's patch merging fits K32 (C a multiple of 4, 4C within K10's 2 048, an image under 2^31 bytes);
+    'aten' otherwise (Swin-L's last merge)."""
+    return "k32" if dim % 4 == 0 and dim <= core.PATCH_MERGE_MAX_C and _under_2g(tokens * dim) else "aten"
+
+
+def swin_window_shift(H, W, window, shift):
+    """(window, shift) of a block on an H x W grid: transformers' set_shift_and_window_size -- a grid whose smaller side is
+    no larger than the window takes that side as its window and no shift.  The bias table has (2 * window - 1)^2 rows for
+    the checkpoint's window, so a grid under it cannot be served: ValueError."""
+    if min(H, W) < window:
+        raise ValueError("SwinTower: a %dx%d token grid is smaller than the window %d its relative-position table was "
+                         "built for" % (H, W, window))
+    return (window, 0) if min(H, W) == window else (window, shift)
+
+
+def swin_bias_index(window, device=None):
+    """[w^2, w^2] int64: the row of relative_position_bias_table for query (i, j) and key (i', j'),
+    (i - i' + w - 1)(2w - 1) + (j - j' + w - 1) -- transformers' relative_position_index."""
+    c = torch.arange(window, device=device)
+    i, j = (t.reshape(-1) for t in torch.meshgrid(c, c, indexing="ij"))
+    return (i[:, None] - i[None, :] + window - 1) * (2 * window - 1) + (j[:, None] - j[None, :] + window - 1)
+
+
+def swin_shift_mask(Hp, Wp, window, shift, dtype, device=None):
+    """None without a shift, else [nW, w^2, w^2]: SWIN_MASK where two tokens of a window lie in different regions of the
+    rolled Hp x Wp grid -- rows (and columns) fall in region 0, 1 or 2 below Hp - w, below Hp - s, or past it -- else 0."""
+    if shift <= 0:
+        return None
+    r, c = torch.arange(Hp, device=device), torch.arange(Wp, device=device)
+    region = (3 * ((r >= Hp - window).long() + (r >= Hp - shift).long())[:, None]
+              + ((c >= Wp - window).long() + (c >= Wp - shift).long())[None, :])
+    region = _window_partition(region[None, :, :, None], window).view(-1, window * window)
+    return (region[:, None, :] != region[:, :, None]).to(dtype) * SWIN_MASK
+
+
+def _window_partition(x, w):
+    """[B, Hp, Wp, C] -> [B * nW, w * w, C], windows in row-major order, tokens of a window in row-major order."""
+    B, Hp, Wp, C = x.shape
+    return x.view(B, Hp // w, w, Wp // w, w, C).permute(0, 1, 3, 2, 4, 5).reshape(-1, w * w, C)
+
+
+def _window_reverse(x, w, Hp, Wp):
+    """_window_partition's inverse: [B * nW, w * w, C] -> [B, Hp, Wp, C]."""
+    C = x.shape[-1]
+    return x.view(-1, Hp // w, Wp // w, w, w, C).permute(0, 1, 3, 2, 4, 5).reshape(-1, Hp, Wp, C)
+
+
+def _window_softmax_pv(q, k, v, heads, table, window, mask):
+    """softmax(q k^T / sqrt(head width) + bias + mask) v for windows q, k, v [B * nW, w^2, C] -> [B * nW, w^2, C]: the
+    bias gathered from table [(2w-1)^2, heads], mask None or swin_shift_mask's [nW, w^2, w^2] (windows of one image
+    adjacent)."""
+    N, T, C = q.shape
+    q, k, v = (t.reshape(N, T, heads, C // heads).transpose(1, 2) for t in (q, k, v))
+    scores = q @ k.transpose(-1, -2) / math.sqrt(C // heads)
+    scores = scores + table[swin_bias_index(window, table.device).view(-1)].view(T, T, heads).permute(2, 0, 1)[None]
+    if mask is not None:
+        nW = mask.shape[0]
+        scores = (scores.view(N // nW, nW, heads, T, T) + mask[None, :, None]).view(N, heads, T, T)
+    return (torch.softmax(scores, dim=-1) @ v).transpose(1, 2).reshape(N, T, C)
+
+
+def _window_attend_aten(qkv, heads, grid, window, shift, table, pad_qkv):
+    """core.window_attention's operands through ATen: qkv [B, H*W, 3C] in token order -> [B, H*W, C].  The padded tokens
+    take pad_qkv, as in K31."""
+    B, T, C3 = qkv.shape
+    H, W = grid
+    Hp, Wp = -(-H // window) * window, -(-W // window) * window
+    x = qkv.view(B, H, W, C3)
+    if (Hp, Wp) != (H, W):
+        full = pad_qkv.detach().expand(B, Hp, Wp, C3).clone()
+        full[:, :H, :W] = x
+        x = full
+    if shift > 0:
+        x = torch.roll(x, (-shift, -shift), (1, 2))
+    q, k, v = _window_partition(x, window).chunk(3, dim=-1)
+    o = _window_softmax_pv(q, k, v, heads, table, window, swin_shift_mask(Hp, Wp, window, shift, qkv.dtype, qkv.device))
+    o = _window_reverse(o, window, Hp, Wp)
+    if shift > 0:
+        o = torch.roll(o, (shift, shift), (1, 2))
+    return o[:, :H, :W].reshape(B, T, C3 // 3)
+
+
+class _SwinSelfAttention(nn.Module):
+    """SwinSelfAttention: query, key, value and relative_position_bias_table [(2w-1)^2, heads]."""
+
+    def __init__(self, dim, heads, window):
+        super().__init__()
+        if dim % heads:
+            raise ValueError("SwinTower: width %d is not a multiple of %d heads" % (dim, heads))
+        self.heads, self.window = heads, window
+        self.relative_position_bias_table = nn.Parameter(torch.zeros((2 * window - 1) ** 2, heads))
+        self.query = nn.Linear(dim, dim)
+        self.key = nn.Linear(dim, dim)
+        self.value = nn.Linear(dim, dim)
+
+    def forward(self, x, mask=None):
+        """x [B * nW, w^2, C], the windows; mask None or [nW, w^2, w^2]."""
+        return _window_softmax_pv(self.query(x), self.key(x), self.value(x), self.heads, self.relative_position_bias_table,
+                                  self.window, mask)
+
+    def fused_qkv(self):
+        """(weight [3 C, C], bias [3 C]) of query | key | value as ONE projection -- the [B, T, 3, heads, 32] operand K31
+        reads, and its bias the q | k | v of a padded (zero) token -- concatenated once (_folded)."""
+        return _folded(self, ("query", "key", "value"),
+                       lambda m: (torch.cat([m.query.weight, m.key.weight, m.value.weight]).contiguous(),
+                                  torch.cat([m.query.bias, m.key.bias, m.value.bias]).contiguous()))
+
+
+class _SwinDense(nn.Module):
+    """SwinSelfOutput / SwinOutput: one Linear named dense (dropout is the identity at inference)."""
+
+    def __init__(self, in_dim, out_dim):
+        super().__init__()
+        self.dense = nn.Linear(in_dim, out_dim)
+
+    def forward(self, x):
+        return self.dense(x)
+
+
+class _SwinAttention(nn.Module):
+    def __init__(self, dim, heads, window):
+        super().__init__()
+        setattr(self, "self", _SwinSelfAttention(dim, heads, window))
+        self.output = _SwinDense(dim, dim)
+
+    def forward(self, x, mask=None):
+        return self.output(getattr(self, "self")(x, mask))
+
+
+class _SwinLayer(nn.Module):
+    """SwinLayer, pre-norm: x1 = x + proj(window attention(layernorm_before(x))), out = x1 + fc2(gelu(fc1(layernorm_after(x1)))).
+    forward(x [B, H*W, C], grid (H, W), hip) -> [B, H*W, C], a plain tensor (transformers returns a tuple around it)."""
+
+    def __init__(self, dim, heads, window, shift, mlp, eps):
+        super().__init__()
+        self.window, self.shift = window, shift
+        self.layernorm_before = _LayerNorm(dim, eps=eps)
+        self.attention = _SwinAttention(dim, heads, window)
+        self.layernorm_after = _LayerNorm(dim, eps=eps)
+        self.intermediate = _BertIntermediate(dim, mlp)
+        self.output = _SwinDense(mlp, dim)
+
+    def forward(self, x, grid, hip=False):
+        B, T, C = x.shape
+        H, W = grid
+        w, s = swin_window_shift(H, W, self.window, self.shift)
+        att = getattr(self.attention, "self")
+        if hip and not _hooks_on(self, _SWIN_LAYER_SKIPPED):
+            wqkv, bqkv = att.fused_qkv()
+            ops = _BlockOps(_ln_ops(self.layernorm_before), _ln_ops(self.layernorm_after), (wqkv, bqkv),
+                            _lin_ops(self.attention.output.dense), _lin_ops(self.intermediate.dense),
+                            _lin_ops(self.output.dense), att.heads)
+            arg = ((H, W), w, s, att.relative_position_bias_table.detach(), bqkv)
+            return _block_hip(ops, x, swin_attention_route(w, C, att.heads, T), arg,
+                              k10=HIP_LAYER_NORM and C % 4 == 0 and C <= 2048)
+        # ATen, transformers' own steps; every submodule through __call__, so that a hook inside fires
+        h = self.layernorm_before(x).view(B, H, W, C)
+        Hp, Wp = -(-H // w) * w, -(-W // w) * w
+        h = F.pad(h, (0, 0, 0, Wp - W, 0, Hp - H))         # zeros AFTER the norm: a padded token's q, k, v are the biases
+        if s > 0:
+            h = torch.roll(h, (-s, -s), (1, 2))
+        a = self.attention(_window_partition(h, w), swin_shift_mask(Hp, Wp, w, s, x.dtype, x.device))
+        a = _window_reverse(a, w, Hp, Wp)
+        if s > 0:
+            a = torch.roll(a, (s, s), (1, 2))
+        x = x + a[:, :H, :W].reshape(B, T, C)
+        return x + self.output(self.intermediate(self.layernorm_after(x)))
+
+
+class _SwinPatchMerging(nn.Module):
+    """SwinPatchMerging: the 2x2 neighbours of the (zero-padded to even sizes) grid side by side -- (0,0), (1,0), (0,1),
+    (1,1) in (row, column) offsets --, norm = LayerNorm(4C), reduction = Linear(4C, 2C) without a bias."""
+
+    def __init__(self, dim, eps):
+        super().__init__()
+        self.reduction = nn.Linear(4 * dim, 2 * dim, bias=False)
+        self.norm = _LayerNorm(4 * dim, eps=eps)
+
+    def forward(self, x, grid, hip=False):
+        B, T, C = x.shape
+        H, W = grid
+        if hip and swin_merge_route(C, T) == "k32" and not _hooks_on(self, _SWIN_MERGE_SKIPPED):
+            n = core.patch_merge_ln(x.contiguous(), (H, W), self.norm.weight, self.norm.bias, self.norm.eps)       # K32
+            return core.linear_residual(None, n, self.reduction.weight, None)
+        x = F.pad(x.view(B, H, W, C), (0, 0, 0, W % 2, 0, H % 2))
+        x = torch.cat([x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]], dim=-1)
+        return self.reduction(self.norm(x.view(B, -1, 4 * C)))
+
+
+class _SwinStage(nn.Module):
+    """SwinStage: blocks[j] (shift 0 on even j, window // 2 on odd j) and downsample (None on the last stage).
+    forward -> the stage's output AFTER downsampling, [B, ceil(H/2)*ceil(W/2), 2C], a plain tensor."""
+
+    def __init__(self, dim, depth, heads, window, mlp, eps, downsample):
+        super().__init__()
+        self.blocks = nn.ModuleList([_SwinLayer(dim, heads, window, 0 if j % 2 == 0 else window // 2, mlp, eps)
+                                     for j in range(depth)])
+        self.downsample = _SwinPatchMerging(dim, eps) if downsample else None
+
+    def forward(self, x, grid, hip=False):
+        for blk in self.blocks:                      # through __call__: the hooks on blocks[j] fire
+            x = blk(x, grid, hip)
+        return x if self.downsample is None else self.downsample(x, grid, hip)
+
+
+class _SwinEncoder(nn.Module):
+    def __init__(self, width, depths, heads, windows, mlp_ratio, eps):
+        super().__init__()
+        self.layers = nn.ModuleList([_SwinStage(width << i, depths[i], heads[i], windows[i], int(mlp_ratio * (width << i)), eps,
+                                                i < len(depths) - 1) for i in range(len(depths))])
+
+    def forward(self, x, grid, hip=False):
+        for stage in self.layers:
+            x = stage(x, grid, hip)
+            if stage.downsample is not None:
+                grid = ((grid[0] + 1) // 2, (grid[1] + 1) // 2)
+        return x
+
+
+class _SwinEmbeddings(nn.Module):
+    """SwinEmbeddings without absolute position embeddings and mask token: patch_embeddings.projection (a P x P
+    convolution of stride P on the image zero-padded to whole patches) and norm."""
+
+    def __init__(self, dim, patch, eps):
+        super().__init__()
+        self.patch = patch
+        self.patch_embeddings = _PatchEmbeddings(dim, patch)
+        self.norm = _LayerNorm(dim, eps=eps)
+
+    def forward(self, x):
+        P = self.patch
+        x = self.patch_embeddings.projection(F.pad(x, (0, -x.shape[3] % P, 0, -x.shape[2] % P)))
+        return self.norm(x.flatten(2).transpose(1, 2).contiguous()), (x.shape[2], x.shape[3])
+
+
+class SwinTower(nn.Module):
+    """transformers.SwinModel without its pooler: embeddings.{patch_embeddings.projection, norm},
+    encoder.layers[i].blocks[j].{layernorm_before, attention.self.{query, key, value, relative_position_bias_table},
+    attention.output.dense, layernorm_after, intermediate.dense, output.dense}, encoder.layers[i].downsample.{norm,
+    reduction}, layernorm -- the state-dict keys of transformers 4.41.1, the reference's pin.  forward(image [B, 3, H, W]) ->
+    last_hidden_state [B, T, out_dim] at any image size (the grid is padded per block, as transformers pads it).  The
+    defaults are microsoft/swin-tiny-patch4-window7-224.  window: one int, or one per stage.  Hook points:
+    encoder.layers[i] and encoder.layers[i].blocks[j]; every output is a plain [B, T, C] tensor and a dissection hook reads
+    token 0 of it, as the reference does for a 3-D output."""
+
+    def __init__(self, patch=4, width=96, depths=(2, 2, 6, 2), heads=(3, 6, 12, 24), window=7, mlp_ratio=4.0, eps=1e-5):
+        super().__init__()
+        depths, heads = tuple(depths), tuple(heads)
+        windows = (window,) * len(depths) if isinstance(window, int) else tuple(window)
+        if not (len(depths) == len(heads) == len(windows) >= 1):
+            raise ValueError("SwinTower: depths %s, heads %s and window %s must name the same stages" % (depths, heads, windows))
+        self.config = dict(patch=patch, width=width, depths=depths, heads=heads, window=windows, mlp_ratio=mlp_ratio)
+        self.out_dim = width << (len(depths) - 1)
+        self.embeddings = _SwinEmbeddings(width, patch, eps)
+        self.encoder = _SwinEncoder(width, depths, heads, windows, mlp_ratio, eps)
+        self.layernorm = _LayerNorm(self.out_dim, eps=eps)
+
+    def route(self, x):
+        return swin_route(HIP_SWIN, x.is_cuda, x.dtype, torch.is_grad_enabled(), self.training, _fused_residual_ok(x),
+                          x.shape[0])
+
+    def forward(self, x):
+        hip = x.dim() == 4 and self.route(x) == "hip"
+        t, grid = self.embeddings(x)
+        return self.layernorm(self.encoder(t, grid, hip))
+
+    @staticmethod
+    def config_from_state_dict(sd, prefix=""):
+        """SwinTower's constructor arguments read from the shapes of a SwinModel state dict under `prefix`: patch and width
+        from the projection, the depths by counting keys, per stage the heads from the bias table's columns and the window
+        from its rows ((2w-1)^2), the MLP ratio from intermediate.dense."""
+        def shape(name):
+            if prefix + name not in sd:
+                raise RuntimeError("not a SwinModel state dict: it lacks %r" % (prefix + name,))
+            return tuple(sd[prefix + name].shape)
+        for name in ("embeddings.position_embeddings", "embeddings.mask_token"):
+            if prefix + name in sd:
+                raise ValueError("SwinTower: the checkpoint has %r (absolute position embeddings / masked image modelling), "
+                                 "which this tower does not build" % (prefix + name,))
+        width, _, patch, _ = shape(SWIN_KEY)
+        stem = prefix + "encoder.layers."
+        blocks = {}
+        for k in sd:
+            if k.startswith(stem) and k.endswith(".layernorm_before.weight"):
+                i, _, j = k[len(stem):].split(".")[:3]
+                blocks[int(i)] = max(blocks.get(int(i), 0), int(j) + 1)
+        if not blocks or sorted(blocks) != list(range(len(blocks))):
+            raise RuntimeError("not a SwinModel state dict: stages %s under %r" % (sorted(blocks), stem))
+        depths = tuple(blocks[i] for i in range(len(blocks)))
+        heads, windows = [], []
+        for i in range(len(depths)):
+            rows, h = shape("encoder.layers.%d.blocks.0.attention.self.relative_position_bias_table" % i)
+            w = (math.isqrt(rows) + 1) // 2
+            if (2 * w - 1) ** 2 != rows:
+                raise RuntimeError("stage %d: a relative-position table of %d rows is no (2w-1)^2" % (i, rows))
+            heads.append(h)
+            windows.append(w)
+        return dict(patch=patch, width=width, depths=depths, heads=tuple(heads), window=tuple(windows),
+                    mlp_ratio=shape("encoder.layers.0.blocks.0.intermediate.dense.weight")[0] / width)
+
+    @classmethod
+    def from_state_dict(cls, sd, prefix=""):
+        """The tower of a SwinModel state dict (the keys under `prefix`): sized by config_from_state_dict, fp16 tensors
+        upcast, loaded STRICTLY -- relative_position_index buffers and a pooler are ignored by name, any other missing or
+        unexpected key is an error, never a tower of random weights."""
+        cfg = cls.config_from_state_dict(sd, prefix)
+        model = cls(**cfg)
+        own = {k[len(prefix):]: (v.float() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in sd.items()
+               if k.startswith(prefix) and not k.endswith(_SWIN_IGNORED) and not k[len(prefix):].startswith("pooler.")}
+        model.load_state_dict(own, strict=True)
+        return model
+
+
+class HFImageEncoder(nn.Module):
+    """The reference's HuggingfaceImageEncoder (model/modules/image_encoder.py:14-52) around a Swin tower: holds it as
+    .image_encoder, so a Mammo-CLIP checkpoint's image_encoder.image_encoder.* keys load as they are; out_dim and
+    model_type are the reference's names.  forward(image) -> last_hidden_state [B, T, out_dim]."""
+
+    def __init__(self, tower):
+        super().__init__()
+        self.model_type = "swin"
+        self.image_encoder = tower
+        self.out_dim = tower.out_dim
+
+    def forward(self, image):
+        return self.image_encoder(image)
+
+
+SWIN_PREFIX = "image_encoder.image_encoder."
+# EfficientNet's compound scaling (Tan & Le 2019, table of the b0 .. b7 family): name -> (width, depth) coefficients
+EFFICIENTNET_SCALING = {"b0": (1.0, 1.0), "b1": (1.0, 1.1), "b2": (1.1, 1.2), "b3": (1.2, 1.4), "b4": (1.4, 1.8),
+                        "b5": (1.6, 2.2), "b6": (1.8, 2.6), "b7": (2.0, 3.1)}
+
+
+def efficientnet_scaling(stem, head, blocks):
+    """(name, width, depth) of the EfficientNet whose stem channels, head channels and block count these are; None when
+    no member of the family matches."""
+    for name, (width, depth) in EFFICIENTNET_SCALING.items():
+        n = sum(int(math.ceil(depth * r)) for r, _, _, _, _ in EfficientNetB5Tower.STAGES)
+        if (_round_filters(32, width), _round_filters(1280, width), n) == (stem, head, blocks):
+            return name, width, depth
+    return None
+
+
+def image_tower_of(sd):
+    """What image tower a BreastClip / BreastClipClassifier state dict carries: ('swin', SwinTower's configuration),
+    ('cnn', dict(width=, depth=)) or None when it has no image_encoder.* key at all (a text-only or a head-only file).
+    Keys under image_encoder. that are neither are an error naming what was found."""
+    if SWIN_PREFIX + SWIN_KEY in sd:
+        return "swin", SwinTower.config_from_state_dict(sd, SWIN_PREFIX)
+    if "image_encoder._conv_stem.weight" in sd:
+        stem = sd["image_encoder._conv_stem.weight"].shape[0]
+        head = sd["image_encoder._conv_head.weight"].shape[0] if "image_encoder._conv_head.weight" in sd else -1
+        stemk = "image_encoder._blocks."
+        blocks = 1 + max([int(k[len(stemk):].split(".")[0]) for k in sd if k.startswith(stemk)], default=-1)
+        found = efficientnet_scaling(stem, head, blocks)
+        if found is None:
+            raise ValueError("the checkpoint's image encoder is no EfficientNet b0 .. b7: stem %d, head %d channels, %d blocks"
+                             % (stem, head, blocks))
+        return "cnn", dict(width=found[1], depth=found[2])
+    keys = sorted(k for k in sd if k.startswith("image_encoder."))
+    if keys:
+        raise ValueError("the checkpoint's image encoder is neither a Swin tower (%s*) nor an EfficientNet "
+                         "(image_encoder._conv_stem.weight); its first keys: %s" % (SWIN_PREFIX + "embeddings.patch_embeddings.", keys[:4]))
+    return None
+
+
+# ------------------------------------------------------------------------------------------------------
 # The sentence encoder of get_cos_similarity (reference concept_vit/utils.py:618-646: SentenceTransformer
 # 'all-mpnet-base-v2'.encode): transformers.MPNetModel under its own names + sentence-transformers' Pooling(mean) + Normalize
 # ------------------------------------------------------------------------------------------------------
@@ -3364,16 +3795,31 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
         if hw is not None:
             image_size = hw
             target_name = "breastclip_vit"
+    # the image tower follows the checkpoint (reference model/modules/__init__.py:load_image_encoder builds it from the
+    # checkpoint's config): Swin keys -> the Swin tower sized from them, an EfficientNet's -> its compound scaling (B2, B5,
+    # ...); `ckpt` first, `finetuned_ckpt` when only that carries an image encoder.  No checkpoint: B5 / swin-tiny, seeded.
+    tower, tower_kw = ("swin" if target_name == "breastclip_swin" else "cnn"), {}
+    if target_name in ("breastclip", "breastclip_classifier", "breastclip_swin"):
+        if ckpt is not None:
+            ckpt = _state_dict_of(ckpt)
+        if finetuned_ckpt is not None:
+            finetuned_ckpt = _state_dict_of(finetuned_ckpt)
+        found = next((f for f in (image_tower_of(sd) for sd in (ckpt, finetuned_ckpt) if sd is not None) if f), None)
+        if found is not None:
+            if target_name == "breastclip_swin" and found[0] != "swin":
+                raise ValueError("breastclip_swin: the checkpoint's image encoder is an EfficientNet, not a Swin tower")
+            tower = found[0]
+            tower_kw = dict(swin_config=found[1]) if tower == "swin" else found[1]
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
-        if target_name == "breastclip":
-            model = BreastClip("cnn", **text_kw)
+        if target_name in ("breastclip", "breastclip_swin"):
+            model = BreastClip(tower, **tower_kw, **text_kw)
         elif target_name == "breastclip_vit":
             model = BreastClip("vit", image_size=image_size, **text_kw)
         elif target_name == "breastclip_classifier":
             if n_class is None:
                 raise ValueError("Arguments `args`, `ckpt`, and `n_class` must be provided for BreastClipClassifier.")
-            model = BreastClipClassifier(n_class=n_class)
+            model = BreastClipClassifier(n_class=n_class, image_tower=tower, **tower_kw)
         elif target_name == "clip":
             model = ClipViT(image_size=image_size)
         elif target_name == "resnet50":
@@ -3392,7 +3838,7 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
             model = cls(num_labels=width if width is not None else (2 if n_class is None else n_class),
                         image_size=image_size)
         else:
-            raise ValueError("unknown target model %r (offline build: breastclip, breastclip_vit, "
+            raise ValueError("unknown target model %r (offline build: breastclip, breastclip_vit, breastclip_swin, "
                              "breastclip_classifier, clip, openai_clip, clip_rn50, clip_rn101, resnet18, resnet18_places, resnet34, "
                              "resnet50, resnet101, resnet152, vit, vit-cub, vit-bloodmnist, dino, dino-cub, "
                              "dino-bloodmnist).  mae is built from a ViTMAEForPreTraining checkpoint only: pass ckpt= or "

@@ -527,10 +527,10 @@ def build_mammo_models(target_name, device, breast_clip_ckh=None, fine_tuned_ckh
     dissects repeatedly (bench.py) builds the models once.  text_tower: the dissector's text tower, passed to
     data_utils.get_target_model (None: the BERT tower exactly when the checkpoint carries one)."""
     finetuned = fine_tuned_ckh
-    tower = "vit" if target_name.startswith("breastclip_vit") else "cnn"
-    clip_model, _ = data_utils.get_target_model(target_name if tower == "vit" else "breastclip", device,
+    tower = "vit" if target_name.startswith("breastclip_vit") else "swin" if target_name == "breastclip_swin" else "cnn"
+    clip_model, _ = data_utils.get_target_model(target_name if tower != "cnn" else "breastclip", device,
                                                 ckpt=breast_clip_ckh, text_tower=text_tower)
-    if (target_name == "breastclip" or tower == "vit") and finetuned is None:
+    if (target_name == "breastclip" or tower != "cnn") and finetuned is None:
         target_model = clip_model          # same weights: encode the probe set once
     elif target_name == "breastclip_classifier":
         target_model, _ = data_utils.get_target_model(target_name, device, args=args, ckpt=breast_clip_ckh,

@@ -636,6 +636,74 @@ def cls_token_mix(u, n, out=None):
     return out
 
 
+# ---- K31 -----------------------------------------------------------------------------------------
+WINDOW_ATTENTION_MAX_W = 8      # a window of at most 64 tokens: one per lane of a wave
+WINDOW_ATTENTION_HEAD = 32      # Swin's head width at every released size
+
+
+@_on_device
+def window_attention(qkv, grid, window, shift, table, pad_qkv=None, out=None):
+    """Swin's attention inside shifted windows in one launch (K31, include/mcd_swin.h): qkv a contiguous float32
+    [B, H*W, 3*heads*32] tensor (the fused projection's output: q | k | v along the last axis, heads of 32 inside each, the
+    tokens of the H x W grid in row-major order), grid = (H, W), window 1 .. WINDOW_ATTENTION_MAX_W, 0 <= shift < window,
+    table the contiguous float32 [(2*window-1)^2, heads] relative_position_bias_table as the checkpoint stores it ->
+    [B, H*W, heads*32] in token order.  pad_qkv: the contiguous float32 [3*heads*32] q | k | v of a padded token (the fused
+    bias), needed when H or W is no multiple of window.  Padding, roll, partition, bias gather, the -100 shift mask,
+    softmax, P.V, reverse and un-roll all happen inside the kernel."""
+    _need_gpu(qkv, table, pad_qkv, out)
+    if qkv.dtype != torch.float32 or qkv.dim() != 3 or not qkv.is_contiguous():
+        raise TypeError("qkv must be a contiguous float32 [B, H*W, 3*heads*32] tensor")
+    if table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous():
+        raise TypeError("table must be a contiguous float32 [(2*window-1)^2, heads] tensor")
+    B, T, W3 = qkv.shape
+    H, W = (int(n) for n in grid)
+    window, shift, heads = int(window), int(shift), table.shape[1]
+    if T != H * W or W3 != 3 * heads * WINDOW_ATTENTION_HEAD:
+        raise ValueError("window_attention: qkv %s is not [B, %d*%d, 3 * %d heads * 32]" % (tuple(qkv.shape), H, W, heads))
+    if table.shape[0] != (2 * window - 1) ** 2:
+        raise ValueError("window_attention: the table has %d rows, window %d needs %d"
+                         % (table.shape[0], window, (2 * window - 1) ** 2))
+    if pad_qkv is not None and (pad_qkv.dtype != torch.float32 or pad_qkv.numel() != W3 or not pad_qkv.is_contiguous()):
+        raise TypeError("pad_qkv must be a contiguous float32 tensor of 3*heads*32 elements (or None)")
+    D = heads * WINDOW_ATTENTION_HEAD
+    if out is None:
+        out = torch.empty((B, T, D), dtype=torch.float32, device=qkv.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, T, D) or not out.is_contiguous():
+        raise TypeError("out must be a contiguous float32 [B, H*W, heads*32] tensor")
+    check(_lib.load().mcd_window_attention(qkv.data_ptr(), None if pad_qkv is None else pad_qkv.data_ptr(), B, H, W, heads,
+                                           window, shift, table.data_ptr(), out.data_ptr(), _stream()))
+    return out
+
+
+# ---- K32 -----------------------------------------------------------------------------------------
+PATCH_MERGE_MAX_C = 512         # 4C <= 2048, K10's limit
+
+
+@_on_device
+def patch_merge_ln(x, grid, weight, bias, eps, out=None):
+    """Swin's patch merging up to its LayerNorm in one launch (K32, include/mcd_swin.h): x a contiguous float32
+    [B, H*W, C] tensor, grid = (H, W), weight / bias [4C] -> [B, ceil(H/2)*ceil(W/2), 4C]: every output row is
+    x[2i, 2j] | x[2i+1, 2j] | x[2i, 2j+1] | x[2i+1, 2j+1] (zeros past an odd edge) under LayerNorm -- the bits of layer_norm
+    on the gathered rows.  C a multiple of 4, at most PATCH_MERGE_MAX_C."""
+    _need_gpu(x, weight, bias, out)
+    if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous():
+        raise TypeError("x must be a contiguous float32 [B, H*W, C] tensor")
+    B, T, C = x.shape
+    H, W = (int(n) for n in grid)
+    if T != H * W:
+        raise ValueError("patch_merge_ln: x has %d tokens, the grid is %dx%d" % (T, H, W))
+    if any(t.dtype != torch.float32 or tuple(t.shape) != (4 * C,) or not t.is_contiguous() for t in (weight, bias)):
+        raise TypeError("patch_merge_ln: contiguous float32 [4C] weight / bias")
+    shape = (B, ((H + 1) // 2) * ((W + 1) // 2), 4 * C)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise TypeError("out must be a contiguous float32 [B, ceil(H/2)*ceil(W/2), 4C] tensor")
+    check(_lib.load().mcd_patch_merge_ln(x.data_ptr(), B, H, W, C, weight.data_ptr(), bias.data_ptr(), float(eps),
+                                         out.data_ptr(), _stream()))
+    return out
+
+
 # ---- K10 -----------------------------------------------------------------------------------------
 @_on_device
 def layer_norm(x, weight, bias, eps):

@@ -11,8 +11,14 @@
 //             and embeddings.LayerNorm -- six ATen kernels and three [rows, D] temporaries.
 // out[r] = LayerNorm((word[ids[r]] + type[type_ids[r]]) + pos[r % T]): one wave gathers the three table rows into K10's
 // registers and runs K10's row routine (ln_row) on them, so the result is K10's on ATen's sum, bit for bit.
+//
+// K32 (mcd_patch_merge_ln, include/mcd_swin.h): Swin's patch merging up to its LayerNorm in one launch,
+//   replaces  SwinPatchMerging.forward up to .norm (transformers modeling_swin.py): F.pad to even sizes, four strided
+//             slices, cat and nn.LayerNorm -- a [B, H/2 * W/2, 4C] temporary written and read again.
+// One wave gathers the four neighbours' C values (zeros past an odd edge) into K10's registers and runs ln_row on them.
 #include "mcd_common.h"
 #include "../../include/mcd_text.h"
+#include "../../include/mcd_swin.h"
 
 namespace {
 
@@ -98,7 +104,62 @@ __global__ __launch_bounds__(256) void text_embed_ln_kernel(const int64_t* __res
     ln_row<NV>(v, lane, nq, D, gamma, beta, eps, out, row);
 }
 
+// K32: output row (b, oy, ox) is x[b, 2oy, 2ox] | x[b, 2oy+1, 2ox] | x[b, 2oy, 2ox+1] | x[b, 2oy+1, 2ox+1]; float4 q of
+// the row lies in piece q / (C/4) -- pieces 1 and 3 one grid row down, pieces 2 and 3 one column right.
+template <int NV>
+__global__ __launch_bounds__(256) void patch_merge_ln_kernel(const float* __restrict__ x, int64_t rows, int H, int W, int C,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              float eps, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int Ho = (H + 1) >> 1, Wo = (W + 1) >> 1, cq = C >> 2, nq = C;        // nq = 4C / 4
+    const int ox = (int)(row % Wo), oy = (int)((row / Wo) % Ho);
+    const float* img = x + (row / ((int64_t)Ho * Wo)) * H * W * C;               // in-image offsets fit an int (host)
+    float4 v[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int q = lane + 64 * i;
+        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (q < nq) {
+            const int piece = q / cq, y = 2 * oy + (piece & 1), xx = 2 * ox + (piece >> 1);
+            if (y < H && xx < W) v[i] = reinterpret_cast<const float4*>(img + (y * W + xx) * C)[q % cq];
+        }
+    }
+    ln_row<NV>(v, lane, nq, 4 * C, gamma, beta, eps, out, row);
+}
+
 }  // namespace
+
+extern "C" int mcd_patch_merge_ln(const float* x, int64_t B, int64_t H, int64_t W, int64_t C, const float* gamma,
+                                  const float* beta, float eps, float* out, mcd_stream_t stream) {
+    MCD_REQUIRE(x && out && gamma && beta, MCD_E_ARG, "mcd_patch_merge_ln: NULL pointer");
+    MCD_REQUIRE(B >= 0 && H >= 1 && W >= 1 && C >= 4 && C % 4 == 0, MCD_E_ARG,
+                "mcd_patch_merge_ln: bad shape B=%lld H=%lld W=%lld C=%lld (C a positive multiple of 4)", (long long)B,
+                (long long)H, (long long)W, (long long)C);
+    MCD_REQUIRE(4 * C <= 2048, MCD_E_UNSUPPORTED, "mcd_patch_merge_ln: 4C=%lld is over 2048", (long long)(4 * C));
+    MCD_REQUIRE(H < (1 << 24) && W < (1 << 24) && H * W * C < (1LL << 29) && B < (1LL << 31), MCD_E_UNSUPPORTED,
+                "mcd_patch_merge_ln: one image spans 2^31 bytes or more");
+    MCD_REQUIRE(((uintptr_t)x) % 16 == 0 && ((uintptr_t)out) % 16 == 0 && ((uintptr_t)gamma) % 16 == 0 && ((uintptr_t)beta) % 16 == 0,
+                MCD_E_ARG, "mcd_patch_merge_ln: pointers must be 16-byte aligned");
+    if (B == 0) return MCD_OK;
+    const int64_t rows = B * ((H + 1) / 2) * ((W + 1) / 2);
+    MCD_REQUIRE(mcd_cdiv(rows, 4) < (1LL << 31), MCD_E_UNSUPPORTED, "mcd_patch_merge_ln: %lld output rows", (long long)rows);
+    const unsigned grid = (unsigned)mcd_cdiv(rows, 4);
+    const int nv = (int)mcd_cdiv(C, 64);
+#define MCD_PM(NV)                                                                                                       \
+    hipLaunchKernelGGL(patch_merge_ln_kernel<NV>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, rows, (int)H, (int)W, \
+                       (int)C, gamma, beta, eps, out)
+    if (nv <= 1) MCD_PM(1);
+    else if (nv == 2) MCD_PM(2);
+    else if (nv == 3) MCD_PM(3);
+    else if (nv == 4) MCD_PM(4);
+    else if (nv <= 6) MCD_PM(6);
+    else MCD_PM(8);
+#undef MCD_PM
+    MCD_LAUNCH_CHECK("patch_merge_ln_kernel");
+    return MCD_OK;
+}
 
 extern "C" int mcd_layer_norm(const float* x, int64_t rows, int64_t D, const float* gamma, const float* beta, float eps,
                               float* y, mcd_stream_t stream) {
