@@ -1,7 +1,9 @@
-"""Randomised differential test of the encoder-side entries -- the attention family (K9, K9L, K9M, K9A, K9B), the one-row entries
-(K9C, K30) and the token / row operations (K10, K24, K25, K26, K27, K28, K29) -- with tests/encoder_fuzz.py: stratified case lists
-of consecutive seeds, float64 references from the headers, the headers' bit relations and read sets, every operand in a frame.
-argv: [cases per entry] [seed] [--entries K9 K9M ...]"""
+"""Randomised differential test of the encoder-side entries with the two fuzzers under tests/: encoder_fuzz.py -- the attention
+family (K9, K9L, K9M, K9A, K9B), the one-row entries (K9C, K30) and the token / row operations (K10, K24, K25, K26, K27, K28,
+K29) -- and conv_fuzz.py -- the channels-last towers (K12 - K15, K0N, K16 - K18, K18R, K19 - K21) and the Swin pair (K31, K32):
+stratified case lists of consecutive seeds, float64 references from the headers, the headers' bit relations and read sets, every
+operand in a frame.
+argv: [cases per entry] [seed] [--entries K9 K9M K18 K31 ...]"""
 import argparse
 import os
 import sys
@@ -9,20 +11,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import torch
 import mammo_clip_dissect_amd as mcd
+import conv_fuzz as C
 import encoder_fuzz as E
 
 ap = argparse.ArgumentParser()
 ap.add_argument("cases", nargs="?", type=int, default=600)
 ap.add_argument("seed", nargs="?", type=int, default=0)
-ap.add_argument("--entries", nargs="+", default=list(E.ENTRIES), choices=E.ENTRIES)
+ap.add_argument("--entries", nargs="+", default=list(E.ENTRIES + C.ENTRIES), choices=E.ENTRIES + C.ENTRIES)
 args = ap.parse_args()
 dev = torch.device("cuda:0")
-call = E.gpu_call(mcd._lib.load())
+calls = {E: E.gpu_call(mcd._lib.load()), C: C.gpu_call(mcd._lib.load())}
 bad, top, done = 0, {}, 0
 for entry in args.entries:
     top[entry] = 0.0
-    for case in E.random_cases(entry, args.cases, args.seed):
-        findings, ratio = E.check(entry, case, call, dev)
+    F = E if entry in E.ENTRIES else C
+    for case in F.random_cases(entry, args.cases, args.seed):
+        findings, ratio = F.check(entry, case, calls[F], dev)
         for f in findings:
             print("MISMATCH " + f, flush=True)
         bad += len(findings)

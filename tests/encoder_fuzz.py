@@ -785,6 +785,24 @@ def run(entry, case_list, call, device="cpu", progress=None):
 # =========================================================================================================================
 # 4. the library behind call(): every operand in a frame (GPU only; nothing above needs it)
 # =========================================================================================================================
+def _ptr(a):
+    return None if a is None else a.ptr
+
+
+def _finish(name, o, ins):
+    """The output frame o after the call: its guards intact, every logical element written, the input frames `ins` unchanged;
+    returns a copy of the logical region."""
+    import util
+    out = o.view.clone()
+    o.check(out, what=name)
+    fill_bits = int(util.int_bits(torch.full((1,), util.OUT_FILL))[0])
+    assert not bool((util.int_bits(out) == fill_bits).any()), "%s: an output element was not written" % name
+    for a in ins:
+        if a is not None:
+            a.same()
+    return out
+
+
 def gpu_call(L):
     """call(name, ...) on libmcd_hip.so: inputs through In / Strided of test_gpu_encoder_frames with NaN in their guards and
     gaps (LENS_GAP around index lists), outputs in OUT_FILL frames.  The guards must come back intact, every logical element
@@ -792,22 +810,10 @@ def gpu_call(L):
     import test_gpu_encoder_frames as EF
     import util
 
-    fill_bits = int(util.int_bits(torch.full((1,), util.OUT_FILL))[0])
-
     def ints(values, dev, dtype=torch.int32):
         return None if values is None else EF.In(torch.as_tensor(values, dtype=dtype, device=dev), LENS_GAP)
 
-    def ptr(a):
-        return None if a is None else a.ptr
-
-    def finish(name, o, ins):
-        out = o.view.clone()
-        o.check(out, what=name)
-        assert not bool((util.int_bits(out) == fill_bits).any()), "%s: an output element was not written" % name
-        for a in ins:
-            if a is not None:
-                a.same()
-        return out
+    ptr, finish = _ptr, _finish
 
     def rows3(t, row, img):
         return EF.Strided(t, row, img, NAN)

@@ -106,3 +106,35 @@ def test_cls_row_fuzz(encoder_call, dev, entry):
 def test_token_ops_fuzz(encoder_call, dev, entry):
     """K10 / K25 against float64 at their own tests' tolerances; K24, K26, K27, K28, K29 on the bits their headers spell out."""
     _encoder_fuzz(entry, encoder_call, dev)
+
+
+# ---- the convolution side: tests/conv_fuzz.py on the library, every operand in a frame ------------------------------------
+import conv_fuzz as CF  # noqa: E402  (touches no GPU on import)
+
+
+@pytest.fixture(scope="module")
+def conv_call(mcd, dev):
+    return CF.gpu_call(mcd._lib.load())
+
+
+def _conv_fuzz(entry, call, dev):
+    """The committed case list of one entry (CF.SEEDS): float64, the headers' bit relations, read sets and frames."""
+    case_list = CF.cases(entry, CF.SEEDS[entry])
+    findings, ratio = CF.run(entry, case_list, call, dev)
+    print("%s: %d cases, %d findings, max err / bound %.3f" % (entry, len(case_list), len(findings), ratio))
+    assert not findings, "\n".join(findings[:20])
+
+
+@pytest.mark.parametrize("entry", CF.TOWERS)
+def test_conv_towers_fuzz(conv_call, dev, entry):
+    """K12 - K15 and K0n, K16 - K18 and K18 with a residual, K19 - K21 over their tile edges, channel slices and k-step counts, one
+    case past every grid cap, under exact, random, offset and dead data; every image alone, the batch reversed, permuted output
+    channels, the ReLU flags against each other, one NaN pixel's read set."""
+    _conv_fuzz(entry, conv_call, dev)
+
+
+@pytest.mark.parametrize("entry", CF.SWIN)
+def test_swin_fuzz(conv_call, dev, entry):
+    """K31 at every (window, shift) pair, padded and unpadded grids of one to three windows a side, scores of +-100, a table that
+    dominates q.k, a dominant key, every window of an unshifted grid alone; K32 against K10 on the gathered rows at every parity."""
+    _conv_fuzz(entry, conv_call, dev)

@@ -2,14 +2,13 @@
 pre-filled operands, then data_utils.SwinTower on both routes against transformers' fixture (tests/golden/swin.npz), and
 the EfficientNet-B2 tower a B2 checkpoint builds.
 
-K31's reference is a float64 restatement of the rules written here (reference64): zero padding of the token grid after the
+K31's reference is a float64 restatement of the rules written here (conv_fuzz.reference64): zero padding of the token grid after the
 projection's input (a padded token's q, k, v are pad_qkv), roll by (-s, -s), windows in row-major order, the bias
 table[(i-i'+w-1)(2w-1) + (j-j'+w-1), head], -100 between tokens of different (row region, column region) pairs -- region 0, 1,
 2 for a rolled index below n-w, below n-s, or past it --, softmax over the window's keys, times v, back to the original
 positions.  The bound is the project's for a HIP kernel on its ATen route: error against float64 at most twice ATen's on
 the same input, plus 1e-6 (test_gpu_text_tower._bound); both errors are printed."""
 import json
-import math
 import os
 
 import numpy as np
@@ -21,6 +20,7 @@ import test_gpu_encoder_frames as EF
 import test_gpu_stream_contracts as S
 import test_gpu_text_tower as TT
 import util
+from conv_fuzz import reference64, region  # noqa: F401  (K31's float64 reference: the fuzzer's)
 from test_gpu_text_tower import spin_cycles  # noqa: F401  (the fixture)
 from util import int_bits, nerr
 
@@ -69,37 +69,6 @@ def k31(L, qkv, pad, H, W, heads, w, s, table, gap=NAN):
         if a is not None:
             a.same()
     return out
-
-
-def region(r, n, w, s):
-    return 0 if r < n - w else (1 if r < n - s else 2)
-
-
-def reference64(qkv, pad, H, W, heads, w, s, table):
-    """The rules of the module docstring in float64 on the CPU: qkv [B, H*W, 3*heads*32] -> [B, H*W, heads*32]."""
-    qkv, table = qkv.double().cpu(), table.double().cpu()
-    B, T = qkv.shape[0], w * w
-    Hp, Wp = -(-H // w) * w, -(-W // w) * w
-    if (Hp, Wp) != (H, W):
-        full = pad.double().cpu().view(1, 1, 1, 3, heads, 32).expand(B, Hp, Wp, 3, heads, 32).clone()
-    else:
-        full = torch.empty(B, Hp, Wp, 3, heads, 32, dtype=torch.float64)
-    full[:, :H, :W] = qkv.view(B, H, W, 3, heads, 32)
-    rolled = torch.roll(full, (-s, -s), (1, 2))
-    ii, jj = torch.arange(T) // w, torch.arange(T) % w
-    bias = table[(ii[:, None] - ii[None, :] + w - 1) * (2 * w - 1) + (jj[:, None] - jj[None, :] + w - 1)]       # [T, T, heads]
-    out = torch.zeros(B, Hp, Wp, heads, 32, dtype=torch.float64)
-    for wr in range(Hp // w):
-        for wc in range(Wp // w):
-            blk = rolled[:, wr * w:(wr + 1) * w, wc * w:(wc + 1) * w].reshape(B, T, 3, heads, 32)
-            q, k, v = blk.permute(2, 0, 3, 1, 4)                                          # each [B, heads, T, 32]
-            sc = q @ k.transpose(-1, -2) / math.sqrt(32.0) + bias.permute(2, 0, 1)[None]
-            if s > 0:
-                reg = torch.tensor([3 * region(wr * w + int(i), Hp, w, s) + region(wc * w + int(j), Wp, w, s) for i, j in zip(ii, jj)])
-                sc = sc + (reg[:, None] != reg[None, :]).double() * -100.0
-            o = torch.softmax(sc, dim=-1) @ v                                             # [B, heads, T, 32]
-            out[:, wr * w:(wr + 1) * w, wc * w:(wc + 1) * w] = o.permute(0, 2, 1, 3).reshape(B, w, w, heads, 32)
-    return torch.roll(out, (s, s), (1, 2))[:, :H, :W].reshape(B, H * W, heads * 32)
 
 
 # H, W, w, s
