@@ -103,6 +103,10 @@ SWIN_SIGNATURES = {
     "mcd_window_attention": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p]),
     "mcd_patch_merge_ln": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _f, _p, _p]),
 }
+# the 7x7 / 2 stem with its epilogue, of the same library, declared in include/mcd_stem.h (additive to ABI version 9)
+STEM_SIGNATURES = {
+    "mcd_conv7x7s2_bias_relu_nhwc": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _i64, _int, _p, _p]),
+}
 
 MCD_E_ARG = -1
 MCD_E_RANGE = -2
@@ -132,7 +136,8 @@ def load():
         for name, (res, args) in (list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(CLIP_SIGNATURES.items())
                                   + list(TOKEN_SIGNATURES.items()) + list(SENTENCE_SIGNATURES.items())
                                   + list(MASK_SIGNATURES.items()) + list(CACHE_SIGNATURES.items())
-                                  + list(CLSFOLD_SIGNATURES.items()) + list(SWIN_SIGNATURES.items())):
+                                  + list(CLSFOLD_SIGNATURES.items()) + list(SWIN_SIGNATURES.items())
+                                  + list(STEM_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

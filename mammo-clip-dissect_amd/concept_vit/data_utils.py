@@ -1184,16 +1184,21 @@ class BreastClip(nn.Module):
     text_pooling: 'eos' (the default), 'bos' or 'mean' (model/clip.py:66-77).
     'swin' = HFImageEncoder around a SwinTower (swin_config: its constructor arguments, swin-tiny's by default), token 0 of
     its last_hidden_state as the image feature (model/clip.py:49-52).  width / depth: the EfficientNet's compound-scaling
-    coefficients ('cnn' only; B5's by default, 1.1 / 1.2 give B2, out_dim 1408)."""
+    coefficients ('cnn' only; B5's by default, 1.1 / 1.2 give B2, out_dim 1408).
+    'resnet' = ResNetImageEncoder, the wrapped torchvision ResNet without its fc (layers: the block counts, resnet50's by
+    default), out_dim 2048; its flattened average pool is the image feature as it is (the reference's model_type 'cnn'
+    branch, model/clip.py:47-48)."""
 
     def __init__(self, image_tower="cnn", image_size=224, text_depth=12, text_tower="stand-in", bert_config=None,
-                 text_pooling="eos", swin_config=None, width=1.6, depth=2.2):
+                 text_pooling="eos", swin_config=None, width=1.6, depth=2.2, layers=None):
         super().__init__()
         self.model_type = image_tower
         if image_tower == "cnn":
             self.image_encoder = EfficientNetTower(width, depth)
         elif image_tower == "swin":
             self.image_encoder = HFImageEncoder(SwinTower(**(swin_config or SWIN_TINY)))
+        elif image_tower == "resnet":
+            self.image_encoder = ResNetImageEncoder(layers or (3, 4, 6, 3))
         else:
             self.image_encoder = ViTTower(image_size=image_size)
         if text_tower not in ("stand-in", "bert"):
@@ -1207,7 +1212,7 @@ class BreastClip(nn.Module):
         self.tokenizer = HashTokenizer() if text_tower == "stand-in" else None    # 'bert': resolved at tokenize()
 
     def encode_image(self, image):
-        if self.model_type == "cnn":
+        if self.model_type in ("cnn", "resnet"):
             return self.image_encoder(image)
         if self.model_type == "swin":
             return self.image_encoder(image)[:, 0]
@@ -1246,13 +1251,16 @@ class BreastClipClassifier(nn.Module):
     EfficientNet-B5 image encoder + linear head; forward(images) -> logits [B, n_class].
     width / depth: the EfficientNet's compound-scaling coefficients (1.1 / 1.2: B2, out_dim 1408).  image_tower='swin': the
     reference's other branch, HFImageEncoder around a SwinTower (swin_config) and token 0 of its output; the images are
-    [B, 3, H, W] like everywhere in this package (the reference's forward permutes its dataset's channels-last batch)."""
+    [B, 3, H, W] like everywhere in this package (the reference's forward permutes its dataset's channels-last batch).
+    image_tower='resnet': ResNetImageEncoder (layers: the block counts of layer1..4), out_dim 2048."""
 
-    def __init__(self, n_class=1, image_tower="cnn", swin_config=None, width=1.6, depth=2.2):
+    def __init__(self, n_class=1, image_tower="cnn", swin_config=None, width=1.6, depth=2.2, layers=None):
         super().__init__()
         self.model_type = image_tower
         if image_tower == "swin":
             self.image_encoder = HFImageEncoder(SwinTower(**(swin_config or SWIN_TINY)))
+        elif image_tower == "resnet":
+            self.image_encoder = ResNetImageEncoder(layers or (3, 4, 6, 3))
         else:
             self.image_encoder = EfficientNetTower(width, depth)
         self.classifier = nn.Linear(self.image_encoder.out_dim, n_class)
@@ -1514,6 +1522,37 @@ class _StemConv(nn.Conv2d):
         return super().forward(x)
 
 
+def _bottleneck_hip(x, f, stride):
+    """A bottleneck block on channels-last activations, from its folded operands f (w1, b1: "gemm"; w2, b2: "igemm"; w3,
+    b3: "gemm"; wd, bd: "igemm", absent without a projection on the skip): conv1 as a GEMM (raw, folded bn1 as its bias;
+    its ReLU is K18's relu_in), conv2 by K18 (3x3 / stride, folded bn2, ReLU on the way in and out), the projection as a
+    GEMM (stride 1) or K18 1x1 / 2 (stride 2) with folded BN, conv3 as one GEMM with folded bn3 as its bias, the skip as its
+    residual operand and the ReLU as its epilogue.  Returns [B, C, H, W] in channels_last memory.  The one launch
+    sequence of torchvision's Bottleneck (_Bottleneck) and transformers' ResNetBottleNeckLayer (_HFResNetBottleNeckLayer)."""
+    xn = x.permute(0, 2, 3, 1)                                   # [B, H, W, cin], contiguous
+    h = core.linear_residual(None, xn, f["w1"], f["b1"])
+    h = core.conv_igemm_nhwc(h, f["w2"], f["b2"], 3, stride, relu_in=True, relu_out=True)
+    if "wd" not in f:
+        res = xn
+    elif stride == 1:
+        res = core.linear_residual(None, xn, f["wd"], f["bd"])
+    else:
+        res = core.conv_igemm_nhwc(xn, f["wd"], f["bd"], 1, 2)
+    return core.linear_residual(res, h, f["w3"], f["b3"], relu=True).permute(0, 3, 1, 2)
+
+
+def _basic_block_hip(x, f, stride):
+    """A basic block on channels-last activations, from its folded operands f (w1, b1, w2, b2, and wd, bd with a
+    projection on the skip; all "igemm"): two K18 launches (three with a projection) and nothing else: conv1 (3x3 /
+    stride, folded bn1, ReLU on the way out), the skip (x itself, or K18 1x1 / 2 with the folded batch norm), conv2
+    (3x3 / 1, folded bn2) with the skip as K18's residual operand and the ReLU behind the add.  x is left alone.  Returns
+    [B, C, H, W] in channels_last memory.  Shared by _BasicBlock and _HFResNetBasicLayer."""
+    xn = x.permute(0, 2, 3, 1)                                   # [B, H, W, cin], contiguous
+    h = core.conv_igemm_nhwc(xn, f["w1"], f["b1"], 3, stride, relu_out=True)
+    res = xn if "wd" not in f else core.conv_igemm_nhwc(xn, f["wd"], f["bd"], 1, 2)
+    return core.conv_igemm_nhwc(h, f["w2"], f["b2"], 3, 1, relu_out=True, res=res).permute(0, 3, 1, 2)
+
+
 class _Bottleneck(nn.Module):
     expansion = 4                                    # output channels / width
 
@@ -1540,21 +1579,7 @@ class _Bottleneck(nn.Module):
         return F.relu(y + (x if self.downsample is None else self.downsample(x)))
 
     def _forward_hip(self, x):
-        """The block on channels-last activations: conv1 as a GEMM (raw, folded bn1 as its bias; its ReLU is K18's
-        relu_in), conv2 by K18 (3x3, folded bn2, ReLU on the way in and out), the downsample as a GEMM (stride 1) or
-        K18 1x1 / 2 (stride 2) with folded BN, conv3 as one GEMM with folded bn3 as its bias, the skip as its residual
-        operand and the ReLU as its epilogue.  Returns [B, C, H, W] in channels_last memory."""
-        f = _folded(self, _BOTTLENECK_SKIPPED, _Bottleneck._fold)
-        xn = x.permute(0, 2, 3, 1)                                   # [B, H, W, cin], contiguous
-        h = core.linear_residual(None, xn, f["w1"], f["b1"])
-        h = core.conv_igemm_nhwc(h, f["w2"], f["b2"], 3, self.stride, relu_in=True, relu_out=True)
-        if self.downsample is None:
-            res = xn
-        elif self.stride == 1:
-            res = core.linear_residual(None, xn, f["wd"], f["bd"])
-        else:
-            res = core.conv_igemm_nhwc(xn, f["wd"], f["bd"], 1, 2)
-        return core.linear_residual(res, h, f["w3"], f["b3"], relu=True).permute(0, 3, 1, 2)
+        return _bottleneck_hip(x, _folded(self, _BOTTLENECK_SKIPPED, _Bottleneck._fold), self.stride)
 
     def _fold(self):
         f = {}
@@ -1590,15 +1615,7 @@ class _BasicBlock(nn.Module):
         return F.relu(y + (x if self.downsample is None else self.downsample(x)))
 
     def _forward_hip(self, x):
-        """The block on channels-last activations, two K18 launches (three with a downsample) and nothing else: conv1
-        (3x3 / stride, folded bn1, ReLU on the way out), the skip (x itself, or K18 1x1 / 2 with the folded downsample
-        batch norm), conv2 (3x3 / 1, folded bn2) with the skip as K18's residual operand and the ReLU behind the add.  x
-        is left alone.  Returns [B, C, H, W] in channels_last memory."""
-        f = _folded(self, _BASICBLOCK_SKIPPED, _BasicBlock._fold)
-        xn = x.permute(0, 2, 3, 1)                                   # [B, H, W, cin], contiguous
-        h = core.conv_igemm_nhwc(xn, f["w1"], f["b1"], 3, self.stride, relu_out=True)
-        res = xn if self.downsample is None else core.conv_igemm_nhwc(xn, f["wd"], f["bd"], 1, 2)
-        return core.conv_igemm_nhwc(h, f["w2"], f["b2"], 3, 1, relu_out=True, res=res).permute(0, 3, 1, 2)
+        return _basic_block_hip(x, _folded(self, _BASICBLOCK_SKIPPED, _BasicBlock._fold), self.stride)
 
     def _fold(self):
         f = {}
@@ -1625,7 +1642,9 @@ class _Stage(nn.Sequential):
 
 class ResNet(nn.Module):
     """The torchvision ResNet of `block` (_BasicBlock or _Bottleneck) with layers[i] blocks of width 64 << i in
-    layer<i+1>; the stem, the stages, the pooling and fc are the same for every depth."""
+    layer<i+1>; the stem, the stages, the pooling and fc are the same for every depth.  num_classes=None builds it
+    without fc (no fc.* key): forward then returns the flattened average pool [B, 512 * expansion], which is what
+    Mammo-CLIP's ResNet image encoder keeps of torchvision's model (ResNetImageEncoder)."""
 
     def __init__(self, block, layers, num_classes=1000):
         super().__init__()
@@ -1638,14 +1657,17 @@ class ResNet(nn.Module):
                 blocks.append(block(cin, w, s if j == 0 else 1))
                 cin = w * block.expansion
             setattr(self, "layer%d" % i, _Stage(*blocks))
-        self.fc = nn.Linear(cin, num_classes)
+        self.out_dim = cin
+        if num_classes is not None:
+            self.fc = nn.Linear(cin, num_classes)
 
     def forward(self, x):
         if resnet_route(self, x) == "hip":
             return self._forward_hip(x)
         x = F.max_pool2d(F.relu(self.bn1(self.conv1(x))), 3, 2, 1)
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
-        return self.fc(x.mean(dim=[2, 3]))
+        x = x.mean(dim=[2, 3])
+        return self.fc(x) if hasattr(self, "fc") else x
 
     def _forward_hip(self, x):
         """conv1 called as a module (K16 inside; a hook on it fires on the raw output), bn1 + ReLU + max pooling by K17,
@@ -1657,7 +1679,7 @@ class ResNet(nn.Module):
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))         # _Stage keeps the memory channels-last
         pooled = torch.empty((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
         core.hook_pool(x, "avg", pooled, 0, 0, False)                      # K0n: the mean over the pixels, batch-invariant
-        return self.fc(pooled)
+        return self.fc(pooled) if hasattr(self, "fc") else pooled
 
     encode_image = forward  # describe_og_neurons.py calls encode_image on every target
 
@@ -1672,6 +1694,354 @@ RESNETS = {"resnet18": (_BasicBlock, [2, 2, 2, 2], 1000), "resnet34": (_BasicBlo
            "resnet101": (_Bottleneck, [3, 4, 23, 3], 1000), "resnet152": (_Bottleneck, [3, 8, 36, 3], 1000),
            "resnet18_places": (_BasicBlock, [2, 2, 2, 2], 365)}
 PLACES_CKPT = "data/resnet18_places365.pth.tar"      # where the reference keeps it, relative to the working directory
+
+
+class ResNetImageEncoder(nn.Module):
+    """Mammo-CLIP's ResNet image encoder (reference model/modules/image_encoder.py:123-156): torchvision's resnet50 /
+    resnet101 / resnet152 held as `.resnet`, its fc deleted, forward = the flattened average pool [B, 2048].  The wrapped
+    module is a ResNet of _Bottlenecks, so the HIP route is resnet_route's as it stands; hook points are
+    image_encoder.resnet.conv1 and .layer1..4."""
+
+    def __init__(self, layers=(3, 4, 6, 3)):
+        super().__init__()
+        self.resnet = ResNet(_Bottleneck, list(layers), num_classes=None)
+        self.out_dim = self.resnet.out_dim
+
+    def forward(self, image):
+        return self.resnet(image)
+
+
+RESNET_TOWER_KEY = "image_encoder.resnet.conv1.weight"      # what tells a Mammo-CLIP checkpoint with a ResNet image tower
+RESNET_TOWER_LAYERS = ([3, 4, 6, 3], [3, 4, 23, 3], [3, 8, 36, 3])     # resnet50 / 101 / 152, what the reference builds
+
+
+def resnet_tower_layers(sd, prefix="image_encoder.resnet."):
+    """The block counts of layer1..4 under `prefix`, read from the keys of a state dict."""
+    counts = []
+    for i in range(1, 5):
+        stem = "%slayer%d." % (prefix, i)
+        counts.append(1 + max([int(k[len(stem):].split(".")[0]) for k in sd if k.startswith(stem)], default=-1))
+    return counts
+
+
+# ------------------------------------------------------------------------------------------------------
+# transformers' ResNetForImageClassification under its own module names (the reference's `resnet`, `resnet-cub` and
+# `resnet-bloodmnist` targets, data_utils.py:21-36 and :63-69: microsoft/resnet-50 and its fine-tunes)
+# ------------------------------------------------------------------------------------------------------
+HF_RESNET_KEY = "resnet.embedder.embedder.convolution.weight"     # what tells a ResNetForImageClassification state dict
+_HF_LAYER_SKIPPED = ("shortcut", "layer", "activation")
+_HF_CONVLAYER_SKIPPED = ("convolution", "normalization", "activation")
+_HF_EMBEDDINGS_SKIPPED = ("pooler",)
+_HF_MODEL_SKIPPED = ("pooler",)
+
+
+def hf_resnet_route(module, x):
+    """'hip' when a module of an HFResNet can take the HIP route for the tensor it is called with: resnet_route's gate and
+    rules, under the same flag -- HIP_RESNET on (MCD_NO_HIP_RESNET=1 turns it off), a CUDA fp32 tensor, inference (no
+    autograd, eval mode), libmcd_blaslt.so loaded, at most 65535 images, one image's tensors under 2^31 bytes -- and no
+    hook on a submodule that the route would skip (the module then takes ATen, for itself alone).  'aten' otherwise.
+      the stem _HFResNetConvLayer (resnet.embedder.embedder) with the NCHW-contiguous image: a 7x7 / 2 / pad 3 convolution without
+        bias, Cin <= 4, Cout a multiple of 4, a ReLU behind it; skipped: convolution, normalization, activation.  A hook on
+        the unit itself fires on either route and sees the tensor behind the ReLU.  Any other _HFResNetConvLayer called on its
+        own takes ATen (inside a layer, the layer's route decides).
+      _HFResNetEmbeddings (resnet.embedder): the stem's shapes as above (a stem that takes ATen for a hook inside it still hands
+        its output to K17), an output of at least one pixel; skipped: pooler.
+      _HFResNetBottleNeckLayer with a channels_last-contiguous input: _bottleneck_ok's rules (every width a multiple of 32,
+        stride 1 or 2, 16-byte address) with the stride on the 3x3.  downsample_in_bottleneck=True moves the stride to the
+        first 1x1, which is no GEMM any more: such a layer with stride 2 takes ATen, its stride-1 layers are the same
+        module either way and take HIP.  Skipped: shortcut, layer, activation (a hook on layer[1].convolution must fire,
+        so that layer takes ATen and its neighbours do not).
+      _HFResNetBasicLayer with a channels_last-contiguous input: the rules of a _BasicBlock (widths multiples of 32, stride 2 or
+        cin == width: K18 has no 1x1 / 1).  Skipped: shortcut, layer, activation.
+      _HFResNetModel (resnet) with the last stage's output: any 4-D tensor K0n pools; skipped: pooler (a hooked pooler is
+        called as a module)."""
+    if not _tower_gate(HIP_RESNET, module, x):
+        return "aten"
+    B, C, H, W = x.shape
+    if H < 1 or W < 1:
+        return "aten"
+    if isinstance(module, _HFResNetBottleNeckLayer):
+        ok = (not (module.downsample_in_bottleneck and module.stride != 1)
+              and _bottleneck_ok(module, x, lambda s: core.conv_out(H, 3, s, 1) * core.conv_out(W, 3, s, 1)))
+        names = _HF_LAYER_SKIPPED
+    elif isinstance(module, _HFResNetBasicLayer):
+        cin, width, s = module.conv1.in_channels, module.conv2.out_channels, module.stride
+        ok = (C == cin and not (cin % 32 or width % 32) and s in (1, 2) and (s == 2 or cin == width)
+              and core.channels_last(x) and not x.data_ptr() % 16
+              and _under_2g(cin * H * W, width * core.conv_out(H, 3, s, 1) * core.conv_out(W, 3, s, 1),
+                            9 * max(cin, width) * width))
+        names = _HF_LAYER_SKIPPED
+    elif isinstance(module, (_HFResNetConvLayer, _HFResNetEmbeddings)):
+        unit = module.embedder if isinstance(module, _HFResNetEmbeddings) else module
+        stem = unit.convolution
+        ho, wo = core.conv_out(H, 7, 2, 3), core.conv_out(W, 7, 2, 3)
+        ok = (C == stem.in_channels and C <= 4 and not stem.out_channels % 4 and stem.kernel_size == (7, 7)
+              and stem.stride == (2, 2) and stem.padding == (3, 3) and stem.dilation == (1, 1) and stem.groups == 1
+              and stem.bias is None and isinstance(unit.activation, nn.ReLU) and x.is_contiguous()
+              and not x.data_ptr() % 16 and ho >= 1 and wo >= 1 and _under_2g(C * H * W, stem.out_channels * ho * wo))
+        names = _HF_EMBEDDINGS_SKIPPED if isinstance(module, _HFResNetEmbeddings) else _HF_CONVLAYER_SKIPPED
+    elif isinstance(module, _HFResNetModel):
+        ok, names = _under_2g(C * H * W), _HF_MODEL_SKIPPED
+    else:
+        return "aten"
+    return "hip" if ok and not _hooks_on(module, names) else "aten"
+
+
+class _HFResNetConvLayer(nn.Module):
+    """transformers' ResNetConvLayer: convolution (no bias, pad k // 2), normalization, activation (ReLU, or Identity)."""
+
+    def __init__(self, cin, cout, k=3, stride=1, act=True):
+        super().__init__()
+        self.convolution = nn.Conv2d(cin, cout, k, stride, k // 2, bias=False)
+        self.normalization = nn.BatchNorm2d(cout)
+        self.activation = nn.ReLU() if act else nn.Identity()
+
+    def forward(self, x):
+        if hf_resnet_route(self, x) == "hip":
+            # the stem: one launch, the folded batch norm as bias and the ReLU in the epilogue; a [B, Cout, Ho, Wo] view
+            # of channels-last memory comes back
+            w, b = _folded(self, _HF_CONVLAYER_SKIPPED, lambda m: _fold_conv(m.convolution, m.normalization, "tap"))
+            return core.conv7x7s2_bias_relu_nhwc(x, w, b, relu=True).permute(0, 3, 1, 2)
+        return self.activation(self.normalization(self.convolution(x)))
+
+
+class _HFResNetEmbeddings(nn.Module):
+    """transformers' ResNetEmbeddings: embedder (the 7x7 / 2 unit) and pooler (max pooling 3 / 2 / 1)."""
+
+    def __init__(self, num_channels, embedding_size):
+        super().__init__()
+        self.embedder = _HFResNetConvLayer(num_channels, embedding_size, 7, 2)
+        self.pooler = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
+        self.num_channels = num_channels
+
+    def forward(self, x):
+        if x.shape[1] != self.num_channels:
+            raise ValueError("Make sure that the channel dimension of the pixel values match with the one set in the "
+                             "configuration.")
+        if hf_resnet_route(self, x) != "hip":
+            return self.pooler(self.embedder(x))
+        # K17 with unit scale and zero shift: relu(fma(x, 1, 0)) is x on a ReLU's output, so this is the max pooling
+        y = self.embedder(x).contiguous(memory_format=torch.channels_last)     # a no-op copy on the HIP route
+        one, zero = _folded(self, ("embedder",), lambda m: (torch.ones_like(m.embedder.normalization.weight),
+                                                            torch.zeros_like(m.embedder.normalization.weight)))
+        return core.bn_relu_maxpool_nhwc(y.permute(0, 2, 3, 1), one, zero).permute(0, 3, 1, 2)
+
+
+class _HFResNetShortCut(nn.Module):
+    """transformers' ResNetShortCut: convolution 1x1 / stride (no bias), normalization."""
+
+    def __init__(self, cin, cout, stride=2):
+        super().__init__()
+        self.convolution = nn.Conv2d(cin, cout, kernel_size=1, stride=stride, bias=False)
+        self.normalization = nn.BatchNorm2d(cout)
+
+    def forward(self, x):
+        return self.normalization(self.convolution(x))
+
+
+class _HFResNetLayer(nn.Module):
+    """What both of transformers' residual layers share: shortcut (a _HFResNetShortCut, or Identity when neither the channel
+    count nor the stride changes), layer (a Sequential of _HFResNetConvLayers, the last without activation), activation."""
+
+    def _build(self, cin, cout, stride, units):
+        self.stride = stride
+        self.shortcut = _HFResNetShortCut(cin, cout, stride) if cin != cout or stride != 1 else nn.Identity()
+        self.layer = nn.Sequential(*units)
+        self.activation = nn.ReLU()
+
+    def forward(self, x):
+        if hf_resnet_route(self, x) == "hip":
+            return self._hip(x, _folded(self, _HF_LAYER_SKIPPED, type(self)._fold), self.stride)
+        return self.activation(self.layer(x) + self.shortcut(x))
+
+    def _fold_units(self, layouts):
+        f = {}
+        for i, (unit, layout) in enumerate(zip(self.layer, layouts), 1):
+            f["w%d" % i], f["b%d" % i] = _fold_conv(unit.convolution, unit.normalization, layout)
+        if isinstance(self.shortcut, _HFResNetShortCut):
+            f["wd"], f["bd"] = _fold_conv(self.shortcut.convolution, self.shortcut.normalization, "igemm")
+        return f
+
+
+class _HFResNetBottleNeckLayer(_HFResNetLayer):
+    """transformers' ResNetBottleNeckLayer: 1x1, 3x3 / stride, 1x1 (reduction 4); downsample_in_bottleneck moves the
+    stride to the first 1x1.  On the HIP route it is _bottleneck_hip, the launches of a torchvision Bottleneck."""
+
+    def __init__(self, cin, cout, stride=1, reduction=4, downsample_in_bottleneck=False):
+        super().__init__()
+        mid = cout // reduction
+        self.downsample_in_bottleneck = downsample_in_bottleneck
+        self._build(cin, cout, stride, [_HFResNetConvLayer(cin, mid, 1, stride if downsample_in_bottleneck else 1),
+                                       _HFResNetConvLayer(mid, mid, 3, 1 if downsample_in_bottleneck else stride),
+                                       _HFResNetConvLayer(mid, cout, 1, act=False)])
+
+    conv1 = property(lambda self: self.layer[0].convolution)       # what _bottleneck_ok reads
+    conv2 = property(lambda self: self.layer[1].convolution)
+    conv3 = property(lambda self: self.layer[2].convolution)
+    _hip = staticmethod(_bottleneck_hip)
+
+    def _fold(self):
+        return self._fold_units(("gemm", "igemm", "gemm"))
+
+
+class _HFResNetBasicLayer(_HFResNetLayer):
+    """transformers' ResNetBasicLayer: 3x3 / stride, 3x3.  On the HIP route it is _basic_block_hip."""
+
+    def __init__(self, cin, cout, stride=1):
+        super().__init__()
+        self._build(cin, cout, stride, [_HFResNetConvLayer(cin, cout, 3, stride), _HFResNetConvLayer(cout, cout, 3, act=False)])
+
+    conv1 = property(lambda self: self.layer[0].convolution)
+    conv2 = property(lambda self: self.layer[1].convolution)
+    _hip = staticmethod(_basic_block_hip)
+
+    def _fold(self):
+        return self._fold_units(("igemm", "igemm"))
+
+
+class _HFResNetStage(nn.Module):
+    """transformers' ResNetStage: layers, a Sequential (a _Stage: it keeps channels-last memory between the layers)."""
+
+    def __init__(self, layer_type, cin, cout, stride, depth, downsample_in_bottleneck):
+        super().__init__()
+        if layer_type == "bottleneck":
+            first = _HFResNetBottleNeckLayer(cin, cout, stride, downsample_in_bottleneck=downsample_in_bottleneck)
+            rest = [_HFResNetBottleNeckLayer(cout, cout) for _ in range(depth - 1)]
+        else:
+            first = _HFResNetBasicLayer(cin, cout, stride)
+            rest = [_HFResNetBasicLayer(cout, cout) for _ in range(depth - 1)]
+        self.layers = _Stage(first, *rest)
+
+    def forward(self, x):
+        return self.layers(x)
+
+
+class _HFResNetEncoder(nn.Module):
+    def __init__(self, layer_type, embedding_size, hidden_sizes, depths, downsample_in_first_stage,
+                 downsample_in_bottleneck):
+        super().__init__()
+        self.stages = nn.ModuleList()
+        cin = embedding_size
+        for i, (cout, depth) in enumerate(zip(hidden_sizes, depths)):
+            stride = 2 if i or downsample_in_first_stage else 1
+            self.stages.append(_HFResNetStage(layer_type, cin, cout, stride, depth, downsample_in_bottleneck))
+            cin = cout
+
+    def forward(self, x):
+        for stage in self.stages:
+            x = stage(x)
+        return x
+
+
+class _HFResNetModel(nn.Module):
+    """transformers' ResNetModel: embedder, encoder, pooler; forward returns the pooler's output [B, C, 1, 1]."""
+
+    def __init__(self, num_channels, embedding_size, hidden_sizes, depths, layer_type, downsample_in_first_stage,
+                 downsample_in_bottleneck):
+        super().__init__()
+        self.embedder = _HFResNetEmbeddings(num_channels, embedding_size)
+        self.encoder = _HFResNetEncoder(layer_type, embedding_size, hidden_sizes, depths, downsample_in_first_stage,
+                                  downsample_in_bottleneck)
+        self.pooler = nn.AdaptiveAvgPool2d((1, 1))
+
+    def forward(self, x):
+        x = self.encoder(self.embedder(x))
+        if hf_resnet_route(self, x) != "hip":
+            return self.pooler(x)
+        pooled = torch.empty((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
+        core.hook_pool(x, "avg", pooled, 0, 0, False)                      # K0n: the mean over the pixels, batch-invariant
+        return pooled[:, :, None, None]
+
+
+def hf_resnet_config(sd, downsample_in_first_stage=False, downsample_in_bottleneck=False):
+    """HFResNet's constructor arguments read from the shapes of a ResNetForImageClassification state dict: num_channels
+    and embedding_size from the stem's weight, depths by counting the layers of every stage, hidden_sizes from each
+    stage's last convolution, layer_type 'bottleneck' exactly when a layer.2 exists, num_labels from classifier.1.weight
+    when the file has one (else the key is absent: the caller decides).  The state dict does not carry the two
+    downsample_* flags: False, microsoft/resnet-*'s value, unless the caller says otherwise."""
+    def shape(key):
+        if key not in sd:
+            raise RuntimeError("not a ResNetForImageClassification state dict: it lacks %r" % (key,))
+        return tuple(sd[key].shape)
+    embedding_size, num_channels = shape(HF_RESNET_KEY)[:2]
+    stem = "resnet.encoder.stages."
+    found = {}
+    for k in sd:
+        if k.startswith(stem) and k.endswith(".convolution.weight"):
+            parts = k[len(stem):].split(".")
+            if len(parts) >= 3 and parts[1] == "layers" and parts[0].isdigit() and parts[2].isdigit():
+                found.setdefault(int(parts[0]), set()).add(int(parts[2]))
+    shape(stem + "0.layers.0.layer.0.convolution.weight")
+    depths = [1 + max(found[s]) for s in sorted(found)]
+    bottleneck = stem + "0.layers.0.layer.2.convolution.weight" in sd
+    last = 2 if bottleneck else 1
+    hidden_sizes = [shape("%s%d.layers.0.layer.%d.convolution.weight" % (stem, s, last))[0] for s in range(len(depths))]
+    cfg = dict(num_channels=num_channels, embedding_size=embedding_size, hidden_sizes=hidden_sizes, depths=depths,
+               layer_type="bottleneck" if bottleneck else "basic", downsample_in_first_stage=downsample_in_first_stage,
+               downsample_in_bottleneck=downsample_in_bottleneck)
+    if "classifier.1.weight" in sd:
+        cfg["num_labels"] = shape("classifier.1.weight")[0]
+    return cfg
+
+
+class HFResNet(nn.Module):
+    """transformers' ResNetForImageClassification under transformers' own module and parameter names, so that a real state
+    dict loads strictly and the reference's --target_layers resolve: resnet.embedder.embedder.{convolution, normalization,
+    activation}, resnet.embedder.pooler, resnet.encoder.stages[s].layers[l].{shortcut.{convolution, normalization},
+    layer[k].{convolution, normalization, activation}}, resnet.pooler, classifier = Sequential(Flatten, Linear).  The
+    defaults are microsoft/resnet-50's.
+
+    forward(pixel_values) -> the logits tensor [B, num_labels] (encode_image is the same call).
+    Hook points: every module of the tree; a dissection uses resnet.embedder (behind the pooling),
+    resnet.embedder.embedder (behind the ReLU), resnet.encoder.stages[i] and .layers[j], resnet.pooler, classifier.
+
+    The HIP route (HIP_RESNET, hf_resnet_route; every module picks its own): the stem unit in one launch (K16's kernel with
+    the folded batch norm as bias and the ReLU in its epilogue, include/mcd_stem.h), K17 as the max pooling, per layer
+    the launches of the torchvision blocks (_bottleneck_hip, _basic_block_hip) on channels-last memory, K0n for the
+    mean, the classifier's Linear."""
+
+    def __init__(self, num_labels=1000, num_channels=3, embedding_size=64, hidden_sizes=(256, 512, 1024, 2048),
+                 depths=(3, 4, 6, 3), layer_type="bottleneck", downsample_in_first_stage=False,
+                 downsample_in_bottleneck=False):
+        super().__init__()
+        if layer_type not in ("basic", "bottleneck"):
+            raise ValueError("layer_type must be 'basic' or 'bottleneck', got %r" % (layer_type,))
+        if len(hidden_sizes) != len(depths) or not depths or min(depths) < 1:
+            raise ValueError("hidden_sizes %r and depths %r must be equally long, every depth at least 1"
+                             % (tuple(hidden_sizes), tuple(depths)))
+        self.resnet = _HFResNetModel(num_channels, embedding_size, list(hidden_sizes), list(depths), layer_type,
+                                     downsample_in_first_stage, downsample_in_bottleneck)
+        self.classifier = nn.Sequential(nn.Flatten(), nn.Linear(hidden_sizes[-1], num_labels))
+
+    @classmethod
+    def from_state_dict(cls, sd, n_class=None, **flags):
+        """The model of a ResNetForImageClassification state dict: sized by hf_resnet_config (flags: its two downsample_*
+        keywords), fp16 tensors upcast, loaded STRICTLY -- a missing or an unexpected key is an error, never a model of
+        random weights.  A file without classifier.* keeps the freshly initialised head with n_class outputs (2 when
+        None, transformers' default), as HFClip.from_state_dict does."""
+        sd = {k: (v.float() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in sd.items()}
+        cfg = hf_resnet_config(sd, **flags)
+        cfg.setdefault("num_labels", 2 if n_class is None else n_class)
+        model = cls(**cfg)
+        want = set(model.state_dict())
+        if not any(k.startswith("classifier.") for k in sd):
+            want -= {"classifier.1.weight", "classifier.1.bias"}
+        missing, unexpected = sorted(want - set(sd)), sorted(set(sd) - want)
+        if missing or unexpected:
+            raise RuntimeError("the checkpoint does not match ResNetForImageClassification: %d missing key(s) %s, %d "
+                               "unexpected key(s) %s" % (len(missing), missing[:4], len(unexpected), unexpected[:4]))
+        model.load_state_dict(sd, strict=False)          # (the key sets were compared above; shapes are checked here)
+        return model
+
+    def forward(self, pixel_values):
+        return self.classifier(self.resnet(pixel_values.to(self.classifier[1].weight.dtype)))
+
+    def encode_image(self, image):
+        return self(image)
+
+
+HF_RESNET_TARGETS = ("resnet", "resnet-cub", "resnet-bloodmnist")
+HF_CLIP_TARGETS = ("clip", "clip-cub", "clip-bloodmnist")
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -3265,8 +3635,9 @@ def efficientnet_scaling(stem, head, blocks):
 
 def image_tower_of(sd):
     """What image tower a BreastClip / BreastClipClassifier state dict carries: ('swin', SwinTower's configuration),
-    ('cnn', dict(width=, depth=)) or None when it has no image_encoder.* key at all (a text-only or a head-only file).
-    Keys under image_encoder. that are neither are an error naming what was found."""
+    ('cnn', dict(width=, depth=)), ('resnet', dict(layers=)) for the wrapped torchvision resnet50 / 101 / 152 (block counts
+    read from the keys; any other counts are an error naming them), or None when it has no image_encoder.* key at all (a
+    text-only or a head-only file).  Keys under image_encoder. that are none of these are an error naming what was found."""
     if SWIN_PREFIX + SWIN_KEY in sd:
         return "swin", SwinTower.config_from_state_dict(sd, SWIN_PREFIX)
     if "image_encoder._conv_stem.weight" in sd:
@@ -3279,6 +3650,12 @@ def image_tower_of(sd):
             raise ValueError("the checkpoint's image encoder is no EfficientNet b0 .. b7: stem %d, head %d channels, %d blocks"
                              % (stem, head, blocks))
         return "cnn", dict(width=found[1], depth=found[2])
+    if RESNET_TOWER_KEY in sd:
+        layers = resnet_tower_layers(sd)
+        if layers not in RESNET_TOWER_LAYERS:
+            raise ValueError("the checkpoint's image encoder is a ResNet with %s blocks in layer1..4: neither resnet50 "
+                             "[3, 4, 6, 3], resnet101 [3, 4, 23, 3] nor resnet152 [3, 8, 36, 3]" % (layers,))
+        return "resnet", dict(layers=layers)
     keys = sorted(k for k in sd if k.startswith("image_encoder."))
     if keys:
         raise ValueError("the checkpoint's image encoder is neither a Swin tower (%s*) nor an EfficientNet "
@@ -3679,7 +4056,8 @@ def _load_local(model, ckpt, text_strict=False):
     text_strict (a BreastClip with the BERT tower): the text side loads strictly -- pooler.* and
     embeddings.position_ids are ignored by name (BertTextTower has no pooler; 4.41.1 no longer stores the buffer, older
     checkpoints do), any other missing or unexpected key under text_encoder. is an error instead of a tower of random
-    weights."""
+    weights.  A BreastClip / BreastClipClassifier with the ResNet image tower loads the image side strictly in the same
+    way whenever the state dict has a key under image_encoder. at all."""
     if ckpt is None:
         return model
     sd = _state_dict_of(ckpt)
@@ -3691,6 +4069,12 @@ def _load_local(model, ckpt, text_strict=False):
     if isinstance(ckpt, RegisteredCheckpoint) and len(result.unexpected_keys) == len(sd):
         raise RuntimeError("the checkpoint registered for this target, %r, has no key that %s takes (its first keys: %s): a "
                            "wrong file, or a wrong target name" % (str(ckpt), type(model).__name__, sorted(sd)[:4]))
+    if getattr(model, "model_type", None) == "resnet" and any(k.startswith("image_encoder.") for k in sd):
+        missing = [k for k in result.missing_keys if k.startswith("image_encoder.")]
+        unexpected = [k for k in result.unexpected_keys if k.startswith("image_encoder.")]
+        if missing or unexpected:
+            raise RuntimeError("the checkpoint's image encoder does not match the ResNet tower: %d missing key(s) %s, %d "
+                               "unexpected key(s) %s" % (len(missing), missing[:4], len(unexpected), unexpected[:4]))
     if text_strict:
         missing = [k for k in result.missing_keys if k.startswith("text_encoder.")]
         unexpected = [k for k in result.unexpected_keys if k.startswith("text_encoder.")]
@@ -3734,7 +4118,11 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
     size, depth, intermediate size, vocabulary and position rows are read from the checkpoint's shapes.
     use_registered (clip): False keeps the checkpoint registered for the `clip` TARGET out of this call -- the drivers build
     their stand-in DISSECTOR under the same name (og_utils._clip_dissector).
-    `mae` exists only with a checkpoint (ckpt= holding MAE_KEYS, or one registered for `mae`): HFMae sized from it."""
+    `mae` exists only with a checkpoint (ckpt= holding MAE_KEYS, or one registered for `mae`): HFMae sized from it.
+    `resnet`, `resnet-cub`, `resnet-bloodmnist` likewise (ckpt= holding HF_RESNET_KEY, or one registered for the name): an
+    HFResNet sized from it, the classifier's width included; `clip-cub`, `clip-bloodmnist`: an HFClip, as `clip` with a
+    checkpoint.  breastclip / breastclip_classifier follow the checkpoint's image keys: Swin, EfficientNet or the wrapped
+    torchvision ResNet (image_tower_of)."""
     if text_tower not in (None, "stand-in", "bert"):
         raise ValueError("text_tower must be None, 'stand-in' or 'bert', got %r" % (text_tower,))
     if target_name == "openai_clip":
@@ -3744,9 +4132,10 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
             torch.manual_seed(seed)
             model = OpenAIClip(**VIT_B16) if ckpt is None else OpenAIClip.from_state_dict(openai_clip_state_dict(ckpt))
         return model.to(device).eval(), None
-    if target_name == "clip":
+    if target_name in HF_CLIP_TARGETS:
         # transformers' CLIPForImageClassification when a checkpoint of it is at hand: `ckpt` itself when it carries the
-        # vision tower's keys, else the one registered for `clip`.  Sized from the shapes (a fine-tuned clip-cub /
+        # vision tower's keys, else the one registered for the name (`clip`, or the fine-tunes `clip-cub` /
+        # `clip-bloodmnist`, which exist only with such a checkpoint: without one they fall to the ValueError below).  Sized from the shapes (a fine-tuned clip-cub /
         # clip-bloodmnist file is this target with that file) and loaded strictly.  Without either, the stand-in below.
         sd = None
         if ckpt is not None:
@@ -3756,12 +4145,31 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
             else:
                 ckpt = loaded                    # read once: the stand-in below loads from the state dict
         if sd is None and use_registered:
-            registered = target_checkpoint("clip")
+            registered = target_checkpoint(target_name)
             sd = None if registered is None else _state_dict_of(registered)
         if sd is not None:
             with torch.random.fork_rng(devices=[]):
                 torch.manual_seed(seed)
                 model = HFClip.from_state_dict(sd, n_class=n_class)
+            _load_local(model, finetuned_ckpt)
+            return model.to(device).eval(), None
+    if target_name in HF_RESNET_TARGETS:
+        # transformers' ResNetForImageClassification (microsoft/resnet-50 and its fine-tunes), and only from a checkpoint of
+        # it: `ckpt` itself when it carries HF_RESNET_KEY (or is the registered file), else the one registered for the name.
+        # Sized from the shapes, the classifier's width included, and loaded strictly.  Without either the name stays
+        # unknown (the ValueError below).
+        sd = None
+        if ckpt is not None:
+            loaded = _state_dict_of(ckpt)
+            if isinstance(ckpt, RegisteredCheckpoint) or (isinstance(loaded, dict) and HF_RESNET_KEY in loaded):
+                sd = loaded
+        if sd is None and use_registered:
+            registered = target_checkpoint(target_name)
+            sd = None if registered is None else _state_dict_of(registered)
+        if sd is not None:
+            with torch.random.fork_rng(devices=[]):
+                torch.manual_seed(seed)
+                model = HFResNet.from_state_dict(sd, n_class=n_class)
             _load_local(model, finetuned_ckpt)
             return model.to(device).eval(), None
     if target_name == "mae":
@@ -3807,7 +4215,8 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
         found = next((f for f in (image_tower_of(sd) for sd in (ckpt, finetuned_ckpt) if sd is not None) if f), None)
         if found is not None:
             if target_name == "breastclip_swin" and found[0] != "swin":
-                raise ValueError("breastclip_swin: the checkpoint's image encoder is an EfficientNet, not a Swin tower")
+                raise ValueError("breastclip_swin: the checkpoint's image encoder is %s, not a Swin tower"
+                                 % ("a ResNet" if found[0] == "resnet" else "an EfficientNet"))
             tower = found[0]
             tower_kw = dict(swin_config=found[1]) if tower == "swin" else found[1]
     with torch.random.fork_rng(devices=[]):
@@ -3842,7 +4251,9 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
                              "breastclip_classifier, clip, openai_clip, clip_rn50, clip_rn101, resnet18, resnet18_places, resnet34, "
                              "resnet50, resnet101, resnet152, vit, vit-cub, vit-bloodmnist, dino, dino-cub, "
                              "dino-bloodmnist).  mae is built from a ViTMAEForPreTraining checkpoint only: pass ckpt= or "
-                             "register one (register_target_checkpoint('mae', path))" % (target_name,))
+                             "register one (register_target_checkpoint('mae', path)).  resnet, resnet-cub and resnet-bloodmnist are built "
+                             "from a ResNetForImageClassification checkpoint only, clip-cub and clip-bloodmnist from a "
+                             "CLIPForImageClassification checkpoint only, in the same two ways" % (target_name,))
     if target_name == "resnet18_places":
         _load_places(model, ckpt)
     else:

@@ -966,6 +966,19 @@ def conv7x7s2_nhwc(x, w_tap):
 
 
 @_on_device
+def conv7x7s2_bias_relu_nhwc(x, w_tap, bias, relu=False):
+    """K16's kernel with K19's epilogue (include/mcd_stem.h): the stem of transformers' ResNet, conv7x7/2, pad 3, + bias
+    (+ ReLU): x NCHW [B, Cin, H, W] (Cin <= 4), w_tap [Cin, 7, 7, Cout] (the folded weight, tap-major, Cout % 4 == 0),
+    bias [Cout] -> NHWC [B, Ho, Wo, Cout]."""
+    B, Cin, H, W, Cout = _stem_args("conv7x7s2_bias_relu_nhwc", x, w_tap, 7, bias)
+    y = torch.empty((B, conv_out(H, 7, 2, 3), conv_out(W, 7, 2, 3), Cout), dtype=torch.float32, device=x.device)
+    L = _lib.load()
+    check(L.mcd_conv7x7s2_bias_relu_nhwc(x.data_ptr(), B, Cin, H, W, w_tap.data_ptr(), bias.data_ptr(), Cout,
+                                         1 if relu else 0, y.data_ptr(), _stream()))
+    return y
+
+
+@_on_device
 def bn_relu_maxpool_nhwc(x, scale, shift):
     """K17: max over the 3x3 / stride 2 / pad 1 window of relu(x * scale[c] + shift[c]): NHWC [B, H, W, C] (C % 4 == 0)
     -> [B, Ho, Wo, C]."""

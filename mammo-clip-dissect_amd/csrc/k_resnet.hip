@@ -11,12 +11,14 @@
 // reduction: each output element is one fmaf chain in a fixed order (K16, K19: channel, row, column; K18: tap, then
 // channel), so an image's bits depend neither on the batch it is in nor on its place in it.
 #include "k_nhwc.h"
+#include "../../include/mcd_stem.h"
 
 namespace {
 
 // ---- K16 / K19: the KS x KS / 2 image stems, pad KS / 2 -------------------------------------------------------------
 // K16 = <7, CO, false>: the ResNet stem, raw sums (conv1 is a hook point).  K19 = <3, CO, true>: CLIP's anti-aliased
-// stem, + bias (the folded batch norm), then the optional ReLU.
+// stem, + bias (the folded batch norm), then the optional ReLU.  <7, CO, true>: the stem of transformers' ResNet
+// (mcd_conv7x7s2_bias_relu_nhwc, include/mcd_stem.h), K16's chain with K19's epilogue.
 // A workgroup owns a 16 x 16 tile of output pixels of one image and stages its ST_WIN x ST_WIN x Cin input window (37 or
 // 33 wide) in LDS (zeros outside the image = the padding).  A thread owns one pixel and CO output channels at a time (32,
 // or 4 for a width that is no multiple of 32): the weight and bias indices depend on loop counters only, so they come
@@ -352,11 +354,11 @@ int launch_igemm(const float* x, int64_t B, int64_t H, int64_t W, int64_t Cin, c
     return MCD_OK;
 }
 
-// The checks and the dispatch of both stem entries (`name` is the entry's, for the messages).  k = 7: K16, raw, no bias;
-// k = 3: K19, with its epilogue.
-int stem_conv_entry(const char* name, int k, const float* x, int64_t B, int64_t Cin, int64_t H, int64_t W, const float* w,
-                    const float* bias, int64_t Cout, int relu, float* y, mcd_stream_t stream) {
-    const bool epi = k == 3;
+// The checks and the dispatch of the stem entries (`name` is the entry's, for the messages).  k = 7 without epi: K16, raw,
+// no bias; k = 3 with epi: K19, with its epilogue; k = 7 with epi: the stem of transformers' ResNet, whose convolution,
+// batch norm and ReLU are one module.
+int stem_conv_entry(const char* name, int k, bool epi, const float* x, int64_t B, int64_t Cin, int64_t H, int64_t W,
+                    const float* w, const float* bias, int64_t Cout, int relu, float* y, mcd_stream_t stream) {
     MCD_REQUIRE(x && w && y && (bias || !epi), MCD_E_ARG, "%s: NULL pointer", name);
     MCD_REQUIRE(B >= 0 && Cin >= 1 && Cin <= 4 && H >= 1 && W >= 1 && Cout >= 4 && Cout % 4 == 0, MCD_E_ARG,
                 "%s: bad shape B=%lld Cin=%lld H=%lld W=%lld Cout=%lld (Cin <= 4, Cout %% 4 == 0)", name, (long long)B,
@@ -377,9 +379,12 @@ int stem_conv_entry(const char* name, int k, const float* x, int64_t B, int64_t 
 #define MCD_STEM(KS, CO, EPI)                                                                                            \
     hipLaunchKernelGGL((stem_conv_kernel<KS, CO, EPI>), grid, dim3(256), 0, (hipStream_t)stream, x, (int)Cin, (int)H,   \
                        (int)W, w, bias, (int)Cout, (int)Ho, (int)Wo, (int)ntx, relu ? 1 : 0, y)
-    if (epi) {
+    if (k == 3) {
         if (Cout % 32 == 0) MCD_STEM(3, 32, true);
         else MCD_STEM(3, 4, true);
+    } else if (epi) {
+        if (Cout % 32 == 0) MCD_STEM(7, 32, true);
+        else MCD_STEM(7, 4, true);
     } else {
         if (Cout % 32 == 0) MCD_STEM(7, 32, false);
         else MCD_STEM(7, 4, false);
@@ -393,12 +398,17 @@ int stem_conv_entry(const char* name, int k, const float* x, int64_t B, int64_t 
 
 extern "C" int mcd_conv7x7s2_nhwc(const float* x, int64_t B, int64_t Cin, int64_t H, int64_t W, const float* w,
                                   int64_t Cout, float* y, mcd_stream_t stream) {
-    return stem_conv_entry("mcd_conv7x7s2_nhwc", 7, x, B, Cin, H, W, w, nullptr, Cout, 0, y, stream);
+    return stem_conv_entry("mcd_conv7x7s2_nhwc", 7, false, x, B, Cin, H, W, w, nullptr, Cout, 0, y, stream);
 }
 
 extern "C" int mcd_conv3x3s2_nhwc(const float* x, int64_t B, int64_t Cin, int64_t H, int64_t W, const float* w,
                                   const float* bias, int64_t Cout, int relu, float* y, mcd_stream_t stream) {
-    return stem_conv_entry("mcd_conv3x3s2_nhwc", 3, x, B, Cin, H, W, w, bias, Cout, relu, y, stream);
+    return stem_conv_entry("mcd_conv3x3s2_nhwc", 3, true, x, B, Cin, H, W, w, bias, Cout, relu, y, stream);
+}
+
+extern "C" int mcd_conv7x7s2_bias_relu_nhwc(const float* x, int64_t B, int64_t Cin, int64_t H, int64_t W, const float* w,
+                                            const float* bias, int64_t Cout, int relu, float* y, mcd_stream_t stream) {
+    return stem_conv_entry("mcd_conv7x7s2_bias_relu_nhwc", 7, true, x, B, Cin, H, W, w, bias, Cout, relu, y, stream);
 }
 
 extern "C" int mcd_bn_relu_maxpool_nhwc(const float* x, int64_t B, int64_t H, int64_t W, int64_t C, const float* scale,

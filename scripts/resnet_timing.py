@@ -13,6 +13,15 @@
                   CSV there (for --compare).
   --forwards [N]  N (default 4) forwards of the tower at batch 250, for a rocprofv3 --kernel-trace --stats pass.
   --compare A B   two descriptions.csv: how many neurons agree on the top-1 concept and on the top-5 images.
+  --hf [R]        data_utils.HFResNet in microsoft/resnet-50's configuration (seeded weights, mild batch-norm statistics) at
+                  batch --batch (default 250), 224 x 224, with the five hook points of a dissection (resnet.embedder,
+                  resnet.encoder.stages[0..3]) pooled by K0 / K0n into an activation matrix as the drivers' hooks do; beside
+                  it the torchvision-layout resnet50 with conv1 + layer1..4.  One child process: a warm-up of both routes,
+                  then R rounds (default 3, at least 3) that alternate the HIP route and the ATen route (HIP_RESNET off,
+                  what MCD_NO_HIP_RESNET=1 sets) of the same module on the same tree, --forwards-per-round (default 5)
+                  forwards each, timed with device events.  Prints every round, then per model and route the median and
+                  the spread (max - min) of the rounds in ms per forward, and one JSON line.  Every step (the warm-up, each
+                  round of each route) runs under its own time limit: an alarm whose default action ends the process.
 
 Every measurement of --kernels / --driver runs in a fresh child process of this script (the route flag MCD_NO_HIP_RESNET
 is read at import, and MIOpen / hipBLASLt keep per-process state); the child is started with subprocess, nothing replaces
@@ -177,6 +186,75 @@ def forwards_child(n, target):
     print("%d forwards done, route %s" % (n, "hip" if getattr(data_utils, "HIP_RESNET", False) else "aten"))
 
 
+def hf_child(rounds, batch, per_round, limit):
+    import signal
+    import statistics
+    sys.path.insert(0, ROOT)
+    import torch
+    import mammo_clip_dissect_amd  # noqa: F401
+    from mammo_clip_dissect_amd import core
+    from mammo_clip_dissect_amd.concept_vit import data_utils as du
+    dev = torch.device("cuda:0")
+
+    def seeded(net):
+        g = torch.Generator().manual_seed(2)
+        with torch.no_grad():
+            for m in net.modules():
+                if isinstance(m, torch.nn.BatchNorm2d):
+                    n = m.num_features
+                    m.running_mean.copy_(torch.randn(n, generator=g) * 0.1)
+                    m.running_var.copy_(torch.rand(n, generator=g) + 0.5)
+                    m.weight.copy_(1 + 0.2 * torch.randn(n, generator=g))
+                    m.bias.copy_(0.1 * torch.randn(n, generator=g))
+        return net.eval().to(dev)
+    torch.manual_seed(0)
+    models = {"HFResNet (microsoft/resnet-50)": (seeded(du.HFResNet()), ["resnet.embedder"]
+                                                 + ["resnet.encoder.stages.%d" % i for i in range(4)]),
+              "resnet50 (torchvision layout)": (seeded(du.ResNet50()), ["conv1", "layer1", "layer2", "layer3", "layer4"])}
+    x = torch.randn(batch, 3, 224, 224, device=dev, generator=torch.Generator(device=dev).manual_seed(1))
+    for name, (net, layers) in models.items():
+        for layer in layers:
+            dst = {}
+
+            def hook(m, a, o, dst=dst):                  # the drivers' hook body: pool into the activation matrix
+                if "t" not in dst:
+                    dst["t"] = torch.empty((o.shape[0], o.shape[1]), dtype=torch.float32, device=o.device)
+                core.hook_pool(o, "avg", dst["t"], 0, 0, False)
+            net.get_submodule(layer).register_forward_hook(hook)
+
+    def step(net, hip, n):
+        """n forwards on one route under the step's own time limit; ms per forward by device events."""
+        signal.alarm(limit)
+        du.HIP_RESNET = hip
+        with torch.no_grad():
+            net(x)
+            torch.cuda.synchronize()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(n):
+                net(x)
+            e.record()
+            torch.cuda.synchronize()
+        signal.alarm(0)
+        return s.elapsed_time(e) / n
+    result = {"tool": "scripts/resnet_timing.py --hf", "batch": batch, "rounds": rounds, "forwards_per_round": per_round}
+    for name, (net, layers) in models.items():
+        for hip in (True, False):                        # the warm-up: plans, picks, MIOpen's find, the folded weights
+            step(net, hip, 2)
+        ms = {True: [], False: []}
+        for r in range(rounds):
+            for hip in (True, False):
+                ms[hip].append(step(net, hip, per_round))
+                print("%-32s round %d  %-4s %9.3f ms / forward" % (name, r, "hip" if hip else "aten", ms[hip][-1]), flush=True)
+        for hip in (True, False):
+            med, spread = statistics.median(ms[hip]), max(ms[hip]) - min(ms[hip])
+            print("%-32s %-4s median %9.3f ms  spread %7.3f ms  (%d rounds of %d forwards, batch %d, %d hook points)"
+                  % (name, "hip" if hip else "aten", med, spread, rounds, per_round, batch, len(layers)), flush=True)
+            result["%s %s" % (name, "hip" if hip else "aten")] = {"median_ms": round(med, 3), "spread_ms": round(spread, 3),
+                                                                   "rounds_ms": [round(v, 3) for v in ms[hip]]}
+    print(json.dumps(result), flush=True)
+
+
 def compare(a, b):
     import pandas as pd
     da, db = pd.read_csv(a), pd.read_csv(b)
@@ -193,7 +271,12 @@ if __name__ == "__main__":
     target = opt("--target", "resnet50")
     if target not in DEPTHS:
         sys.exit("--target: one of %s" % ", ".join(sorted(DEPTHS)))
-    if "--child-kernels" in sys.argv:
+    if "--child-hf" in sys.argv:
+        hf_child(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5]))
+    elif "--hf" in sys.argv:
+        child(["--child-hf", str(max(arg_n("--hf", 3), 3)), opt("--batch", "250"), opt("--forwards-per-round", "5"),
+               opt("--step-limit", "120")], 900)
+    elif "--child-kernels" in sys.argv:
         kernels_child(int(sys.argv[2]), sys.argv[3], target)
     elif "--child-driver" in sys.argv:
         driver_child(int(sys.argv[2]), int(sys.argv[3]), opt("--keep", None), target)
