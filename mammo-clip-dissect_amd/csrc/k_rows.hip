@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void row_softmax_kernel(const float* __restric
         float acc = __shfl(e, 0, 16);
         for (int i = 1; i < (int)C; ++i) acc = acc + __shfl(e, i, 16);
         const float r = 1.0f / acc;
-        if (l < lds) sr[l] = e * r;
+        if (l < lds) sr[l] = (l < C) ? e * r : 0.f;   // (0 * r is NaN in the padding of a row whose sum is NaN)
         for (int64_t c = 16 + l; c < lds; c += 16) sr[c] = 0.f;
         return;
     }
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256) void row_softmax_kernel(const float* __restric
 #pragma unroll
         for (int j = 0; j < JMAX; ++j) {
             const int64_t c = l + 16 * j;
-            if (c < lds) sr[c] = v[j] * r;  // padding columns C..lds-1 get exactly 0
+            if (c < lds) sr[c] = (c < C) ? v[j] * r : 0.f;  // padding columns C..lds-1 get exactly 0, in a NaN row too
         }
     } else {
         float m = -INFINITY;

@@ -78,3 +78,59 @@ def hook_pool(x, mode, dst, row0, col0, neuron_major):
     else:
         dst[row0:row0 + B, col0:col0 + W] = r
     return W
+
+
+# ---- what tests/scoring_fuzz.py needs beyond the Dissector's backend: K7, the gathered row preparation, K8 on given lists ---
+def center_cube_normalize_rows(x, min_norm=1e-3, out=None):
+    """K7 in oracle.cos_similarity_cubed's fp32 steps (centre, cube, norm clipped at min_norm), one row at a time, so that a
+    row's bits depend on nothing but the row."""
+    f32 = np.float32
+    a = np.ascontiguousarray(_np(x), dtype=f32)
+    y = np.empty_like(a)
+    with np.errstate(invalid="ignore"):
+        for r in range(a.shape[0]):
+            c = a[r] - a[r].mean(dtype=f32)
+            c = c * c * c
+            y[r] = c / np.clip(np.sqrt((c * c).sum(dtype=f32)), f32(min_norm), None)
+    y = torch.from_numpy(y)
+    if out is not None:
+        out.copy_(y)
+        return out
+    return y
+
+
+def prepare_rows_gathered(pieces, rows, mode, min_norm=1e-3):
+    """mcd_prepare_rows_gathered on the pieces [R, counts[g]] of the logical rows: the one-piece preparation of the
+    concatenated rows row0 .. row1 - 1 (mode "normalize": the oracle's bits)."""
+    whole = torch.cat([p for p in pieces], dim=1)[int(rows[0]):int(rows[1])].contiguous()
+    return normalize_rows(whole) if mode == "normalize" else center_cube_normalize_rows(whole, min_norm)
+
+
+def rank_reorder(P, tvals, tidx, perms, p=3, scale_p=0.5, out=None, order=None, colsum=None):
+    """core.rank_reorder's signature on the oracle's primitives: oracle.rank_reorder's loop body (similarity.py:107-132) on
+    GIVEN top lists -- tvals / tidx [U, top_n] descending activations and their images, perms [U, n_perm, top_n].  `order`
+    (the ascending argsort of the gathered columns) and `colsum` (torch.sum(dim=0)'s order) are what a test may swap out."""
+    f32 = np.float32
+    order = order or (lambda G: np.argsort(G, axis=0, kind="stable"))
+    colsum = colsum or O.sum0
+    Pn, tv, ti, pm = _np(P).astype(f32), _np(tvals).astype(f32), _np(tidx).astype(np.int64), _np(perms).astype(np.int64)
+    U, top_n = tv.shape
+    res = np.empty((U, Pn.shape[1]), f32)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for u in range(U):
+            G = np.ascontiguousarray(Pn[ti[u]])
+            avg = (colsum(G) / f32(top_n)).astype(f32)
+            rank = np.argsort(order(G), axis=0, kind="stable")
+            t = tv[u][:, None]
+            st = t[::-1]
+            base = st - np.concatenate([st[pm[u, k]] for k in range(pm.shape[1])], axis=1)
+            ab = np.abs(base).astype(f32)
+            base = (O._pow(ab, p).sum(dtype=f32) / f32(ab.size)).astype(f32)
+            d = np.abs(t - st[:, 0][rank]).astype(f32)
+            err = (O.sum0(O._pow(d, p)) / f32(top_n)).astype(f32) / base
+            res[u] = -(err / O._pow(avg, scale_p)).astype(f32)
+    res = torch.from_numpy(res)
+    if out is not None:
+        out.copy_(res)
+        return out
+    return res

@@ -138,3 +138,26 @@ def test_swin_fuzz(conv_call, dev, entry):
     """K31 at every (window, shift) pair, padded and unpadded grids of one to three windows a side, scores of +-100, a table that
     dominates q.k, a dominant key, every window of an unshifted grid alone; K32 against K10 on the gathered rows at every parity."""
     _conv_fuzz(entry, conv_call, dev)
+
+
+# ---- the scoring side: tests/scoring_fuzz.py on the library, every operand in a frame -------------------------------------
+import scoring_fuzz as SF  # noqa: E402  (touches no GPU on import)
+
+
+@pytest.fixture(scope="module")
+def scoring_call(mcd, dev):
+    return SF.gpu_call(mcd._lib.load())
+
+
+@pytest.mark.parametrize("entry", SF.ENTRIES)
+def test_scoring_fuzz(scoring_call, dev, entry):
+    """K1A, K1 (f32), K2, K4, K5, K7, the gathered row preparation and K8 over every class of their host dispatch
+    (SF.dispatch: kernel form, template flags, persistent passes, panel width, npad), one case with 64-bit gather offsets: the
+    oracle's bits or the entry's numeric rule, a row / neuron / segment alone, the batch reversed, the entry's twin forms
+    (pitch, trusted, route) on the same bits, one NaN's read set, both guard fills."""
+    import time
+    t0 = time.perf_counter()
+    case_list = SF.cases(entry, SF.SEEDS[entry])
+    findings, ratio = SF.run(entry, case_list, scoring_call, dev)
+    print("%s: %d cases, %d findings, max err / bound %.3f, %.1f s" % (entry, len(case_list), len(findings), ratio, time.perf_counter() - t0))
+    assert not findings, "\n".join(findings[:20])
