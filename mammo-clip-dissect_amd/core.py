@@ -83,6 +83,39 @@ def _ld(t):
     return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
 
 
+def _dense(t, message, dim=None, shape=None, device=None):
+    """t must be a contiguous float32 tensor -- of `dim` dimensions, of exactly `shape`, on `device`, where given;
+    TypeError(message) otherwise.  Returns t's shape.  That t is a GPU tensor at all is _need_gpu's to say."""
+    got = t.shape
+    if (t.dtype != torch.float32 or (dim is not None and len(got) != dim) or (shape is not None and got != shape)
+            or not t.is_contiguous() or (device is not None and t.device != device)):
+        raise TypeError(message)
+    return got
+
+
+def _key_counts(lens, B, device, name):
+    """The optional key counts of K9M, K9B and K27: None, or a contiguous int32 [B] tensor on `device`, the device of the
+    operand the message calls `name`."""
+    if lens is not None and (lens.dtype != torch.int32 or lens.shape != (B,) or not lens.is_contiguous()
+                             or lens.device != device):
+        raise TypeError("lens must be a contiguous int32 [B] tensor on %s's device (or None)" % name)
+
+
+def _out(out, shape, device, message, dense=True):
+    """The caller's `out` -- float32, of `shape`, contiguous (dense=False: a unit inner stride is enough), or
+    TypeError(message) -- or, for None, a new contiguous tensor on `device`."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if out.dtype != torch.float32 or out.shape != shape or not (out.is_contiguous() if dense else out.stride(-1) == 1):
+        raise TypeError(message)
+    return out
+
+
+def _ptr(t):
+    """The address of an optional operand: NULL for None."""
+    return None if t is None else t.data_ptr()
+
+
 def _nchw_image(x, message):
     """x must be a contiguous fp32 NCHW image batch on the GPU; TypeError(message) otherwise."""
     _need_gpu(x)
@@ -410,19 +443,21 @@ def rank_reorder(P, tvals, tidx, perms, p=3, scale_p=0.5, out=None):
 VIT_ATTENTION_MAX_T = 256
 
 
-def _attention(entry, qkv, heads, out):
-    """The argument checks and the output of K9 and K9L, then the library entry `entry`."""
-    _need_gpu(qkv)
-    if qkv.dtype != torch.float32 or qkv.dim() != 3 or not qkv.is_contiguous():
-        raise TypeError("qkv must be a contiguous float32 [B, T, 3*heads*64] tensor")
-    B, T, W = qkv.shape
+def _attention(entry, qkv, heads, out, *masks):
+    """The argument checks and the output of the K9 family, then the library entry `entry`.  masks: the optional operands
+    an entry takes between H and out -- (lens,) for K9M, (lens, rel) for K9B -- each a tensor or None."""
+    _need_gpu(qkv, *masks)
+    B, T, W = _dense(qkv, "qkv must be a contiguous float32 [B, T, 3*heads*64] tensor", 3)
     if W != 3 * heads * 64:
         raise ValueError("qkv last dimension %d is not 3 * %d heads * 64" % (W, heads))
-    if out is None:
-        out = torch.empty((B, T, heads * 64), dtype=torch.float32, device=qkv.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, T, heads * 64) or not out.is_contiguous():
-        raise TypeError("out must be a contiguous float32 [B, T, heads*64] tensor")
-    check(getattr(_lib.load(), entry)(qkv.data_ptr(), B, T, heads, out.data_ptr(), _stream()))
+    device = qkv.device
+    if masks:
+        _key_counts(masks[0], B, device, "qkv")
+        if len(masks) == 2 and masks[1] is not None:
+            _dense(masks[1], "rel must be a contiguous float32 [heads, 2T-1] tensor on qkv's device (or None)",
+                   shape=(heads, 2 * T - 1), device=device)
+    out = _out(out, (B, T, heads * 64), device, "out must be a contiguous float32 [B, T, heads*64] tensor")
+    check(getattr(_lib.load(), entry)(qkv.data_ptr(), B, T, heads, *map(_ptr, masks), out.data_ptr(), _stream()))
     return out
 
 
@@ -451,22 +486,7 @@ def vit_attention_keylen(qkv, heads, lens, out=None):
     contiguous int32 [B] tensor on qkv's device, or None (every length is T: vit_attention's bits).  Sequence b attends to
     keys 0 .. L-1, L = clamp(lens[b], 1, T) -- the kernel clamps, the values are not read back.  Every query row is
     computed, padded ones included; no K or V row >= L is read."""
-    _need_gpu(qkv, lens)
-    if qkv.dtype != torch.float32 or qkv.dim() != 3 or not qkv.is_contiguous():
-        raise TypeError("qkv must be a contiguous float32 [B, T, 3*heads*64] tensor")
-    B, T, W = qkv.shape
-    if W != 3 * heads * 64:
-        raise ValueError("qkv last dimension %d is not 3 * %d heads * 64" % (W, heads))
-    if lens is not None and (lens.dtype != torch.int32 or tuple(lens.shape) != (B,) or not lens.is_contiguous()
-                             or lens.device != qkv.device):
-        raise TypeError("lens must be a contiguous int32 [B] tensor on qkv's device (or None)")
-    if out is None:
-        out = torch.empty((B, T, heads * 64), dtype=torch.float32, device=qkv.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, T, heads * 64) or not out.is_contiguous():
-        raise TypeError("out must be a contiguous float32 [B, T, heads*64] tensor")
-    check(_lib.load().mcd_vit_attention_keylen(qkv.data_ptr(), B, T, heads, None if lens is None else lens.data_ptr(),
-                                               out.data_ptr(), _stream()))
-    return out
+    return _attention("mcd_vit_attention_keylen", qkv, heads, out, lens)
 
 
 # ---- K9B -----------------------------------------------------------------------------------------
@@ -476,25 +496,7 @@ def vit_attention_relbias(qkv, heads, lens, rel, out=None):
     include/mcd_sentence.h): rel a contiguous float32 [heads, 2T-1] tensor, rel[h, (j - t) + T - 1] the bias of key j for
     query t, or None (vit_attention_keylen's bits).  Valid rows t < L attend to the L valid keys; the padded query rows are
     written but carry a clamped bias -- nothing may read them.  Of rel only the distances |d| < L of a sequence are read."""
-    _need_gpu(qkv, lens, rel)
-    if qkv.dtype != torch.float32 or qkv.dim() != 3 or not qkv.is_contiguous():
-        raise TypeError("qkv must be a contiguous float32 [B, T, 3*heads*64] tensor")
-    B, T, W = qkv.shape
-    if W != 3 * heads * 64:
-        raise ValueError("qkv last dimension %d is not 3 * %d heads * 64" % (W, heads))
-    if lens is not None and (lens.dtype != torch.int32 or tuple(lens.shape) != (B,) or not lens.is_contiguous()
-                             or lens.device != qkv.device):
-        raise TypeError("lens must be a contiguous int32 [B] tensor on qkv's device (or None)")
-    if rel is not None and (rel.dtype != torch.float32 or tuple(rel.shape) != (heads, 2 * T - 1) or not rel.is_contiguous()
-                            or rel.device != qkv.device):
-        raise TypeError("rel must be a contiguous float32 [heads, 2T-1] tensor on qkv's device (or None)")
-    if out is None:
-        out = torch.empty((B, T, heads * 64), dtype=torch.float32, device=qkv.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, T, heads * 64) or not out.is_contiguous():
-        raise TypeError("out must be a contiguous float32 [B, T, heads*64] tensor")
-    check(_lib.load().mcd_vit_attention_relbias(qkv.data_ptr(), B, T, heads, None if lens is None else lens.data_ptr(),
-                                                None if rel is None else rel.data_ptr(), out.data_ptr(), _stream()))
-    return out
+    return _attention("mcd_vit_attention_relbias", qkv, heads, out, lens, rel)
 
 
 # ---- K27 -----------------------------------------------------------------------------------------
@@ -504,18 +506,11 @@ def masked_mean_l2(x, lens, normalize=True, out=None):
     False, in one launch (K27, include/mcd_sentence.h): x a contiguous float32 [B, T, D] tensor, lens a contiguous int32
     [B] tensor on x's device or None (L = T) -> [B, D].  sentence-transformers' Pooling(mean) + Normalize."""
     _need_gpu(x, lens, out)
-    if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous():
-        raise TypeError("x must be a contiguous float32 [B, T, D] tensor")
-    B, T, D = x.shape
-    if lens is not None and (lens.dtype != torch.int32 or tuple(lens.shape) != (B,) or not lens.is_contiguous()
-                             or lens.device != x.device):
-        raise TypeError("lens must be a contiguous int32 [B] tensor on x's device (or None)")
-    if out is None:
-        out = torch.empty((B, D), dtype=torch.float32, device=x.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, D) or not out.is_contiguous():
-        raise TypeError("out must be a contiguous float32 [B, D] tensor")
-    check(_lib.load().mcd_masked_mean_l2(x.data_ptr(), B, T, D, None if lens is None else lens.data_ptr(),
-                                         1 if normalize else 0, out.data_ptr(), _stream()))
+    B, T, D = _dense(x, "x must be a contiguous float32 [B, T, D] tensor", 3)
+    device = x.device
+    _key_counts(lens, B, device, "x")
+    out = _out(out, (B, D), device, "out must be a contiguous float32 [B, D] tensor")
+    check(_lib.load().mcd_masked_mean_l2(x.data_ptr(), B, T, D, _ptr(lens), 1 if normalize else 0, out.data_ptr(), _stream()))
     return out
 
 
@@ -533,12 +528,8 @@ def quick_gelu(x, out=None):
     """x * sigmoid(1.702 x) in one launch (K25, include/mcd_clip.h): x a contiguous float32 tensor of any shape; out None
     (a new tensor), x itself (in place) or another contiguous float32 tensor of x's shape."""
     _need_gpu(x, out)
-    if x.dtype != torch.float32 or not x.is_contiguous():
-        raise TypeError("x must be a contiguous float32 tensor")
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.dtype != torch.float32 or out.shape != x.shape or not out.is_contiguous():
-        raise TypeError("out must be a contiguous float32 tensor of x's shape")
+    shape = _dense(x, "x must be a contiguous float32 tensor")
+    out = _out(out, shape, x.device, "out must be a contiguous float32 tensor of x's shape")
     check(_lib.load().mcd_quick_gelu(x.data_ptr(), x.numel(), out.data_ptr(), _stream()))
     return out
 
@@ -551,14 +542,12 @@ def token_mean(x, t0=1, out=None):
     out None (a new tensor) or a float32 [B, D] tensor with a unit inner stride (a row-strided view too).  t0 = 1 is
     x[:, 1:].mean(dim=1), the mean of a ViT's patch tokens.  The entry checks widths, strides, alignment and overlap."""
     _need_gpu(x, out)
-    if x.dtype != torch.float32 or x.dim() != 3 or x.stride(2) != 1:
+    strides = x.stride()
+    if x.dtype != torch.float32 or len(strides) != 3 or strides[2] != 1:
         raise TypeError("x must be a float32 [B, T, D] tensor with a unit inner stride")
     B, T, D = x.shape
-    if out is None:
-        out = torch.empty((B, D), dtype=torch.float32, device=x.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, D) or out.stride(1) != 1:
-        raise TypeError("out must be a float32 [B, D] tensor with a unit inner stride")
-    check(_lib.load().mcd_token_mean(x.data_ptr(), B, T, D, x.stride(0), x.stride(1), t0, out.data_ptr(), out.stride(0),
+    out = _out(out, (B, D), x.device, "out must be a float32 [B, D] tensor with a unit inner stride", False)
+    check(_lib.load().mcd_token_mean(x.data_ptr(), B, T, D, strides[0], strides[1], t0, out.data_ptr(), out.stride(0),
                                      _stream()))
     return out
 
@@ -577,21 +566,19 @@ def vit_attention_cls(q, k, v, out=None):
     if any(t.dtype != torch.float32 for t in (q, k, v)) or k.dim() != 4 or k.shape[3] != 64 or v.shape != k.shape:
         raise TypeError("vit_attention_cls: float32 k and v of one shape [B, T, heads, 64]")
     B, T, H, _ = k.shape
+    qs, kvs = q.stride(), (k.stride(), v.stride())
     if q.dim() == 3:
-        if tuple(q.shape) != (B, H, 64) or (H > 1 and q.stride(1) != 64):
+        if tuple(q.shape) != (B, H, 64) or (H > 1 and qs[1] != 64):
             raise ValueError("vit_attention_cls: q must be [B, heads, 64] with a row's heads adjacent")
     elif tuple(q.shape) != (B, H * 64):
         raise ValueError("vit_attention_cls: q has shape %s, k %s" % (tuple(q.shape), tuple(k.shape)))
-    if q.stride(-1) != 1 or any(t.stride(3) != 1 or (H > 1 and t.stride(2) != 64) for t in (k, v)):
+    if qs[-1] != 1 or any(s[3] != 1 or (H > 1 and s[2] != 64) for s in kvs):
         raise ValueError("vit_attention_cls: the heads*64 floats of a token must be adjacent in q, k and v")
-    if out is None:
-        out = torch.empty((B, H * 64), dtype=torch.float32, device=k.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, H * 64) or not out.is_contiguous():
-        raise TypeError("out must be a contiguous float32 [B, heads*64] tensor")
     W = H * 64
-    q_img = q.stride(0) if B > 1 else W
-    row = [t.stride(1) if T > 1 else W for t in (k, v)]
-    img = [t.stride(0) if B > 1 else max(T * r, W) for t, r in zip((k, v), row)]
+    out = _out(out, (B, W), k.device, "out must be a contiguous float32 [B, heads*64] tensor")
+    q_img = qs[0] if B > 1 else W
+    row = [s[1] if T > 1 else W for s in kvs]
+    img = [s[0] if B > 1 else max(T * r, W) for s, r in zip(kvs, row)]
     check(_lib.load().mcd_vit_attention_cls(q.data_ptr(), q_img, k.data_ptr(), row[0], img[0], v.data_ptr(), row[1], img[1],
                                             B, T, H, out.data_ptr(), _stream()))
     return out
@@ -623,11 +610,10 @@ def cls_token_mix(u, n, out=None):
         raise ValueError("cls_token_mix: u has shape %s, n %s" % (tuple(u.shape), tuple(n.shape)))
     if u.stride(2) != 1 or n.stride(2) != 1 or (H > 1 and u.stride(1) != D):
         raise ValueError("cls_token_mix: the D floats of a row, and the heads of an image in u, must be adjacent")
-    if out is None:
-        out = torch.empty((B, H, D), dtype=torch.float32, device=n.device)
-    elif (out.dtype != torch.float32 or tuple(out.shape) != (B, H, D) or out.stride(2) != 1
-          or (H > 1 and out.stride(1) != D)):
-        raise TypeError("out must be a float32 [B, heads, D] tensor with an image's heads*D floats adjacent")
+    message = "out must be a float32 [B, heads, D] tensor with an image's heads*D floats adjacent"
+    out = _out(out, (B, H, D), n.device, message, False)
+    if H > 1 and out.stride(1) != D:
+        raise TypeError(message)
     u_img, m_img = (t.stride(0) if B > 1 else H * D for t in (u, out))
     n_row = n.stride(1) if T > 1 else D
     n_img = n.stride(0) if B > 1 else max(T * n_row, D)
@@ -651,11 +637,8 @@ def window_attention(qkv, grid, window, shift, table, pad_qkv=None, out=None):
     bias), needed when H or W is no multiple of window.  Padding, roll, partition, bias gather, the -100 shift mask,
     softmax, P.V, reverse and un-roll all happen inside the kernel."""
     _need_gpu(qkv, table, pad_qkv, out)
-    if qkv.dtype != torch.float32 or qkv.dim() != 3 or not qkv.is_contiguous():
-        raise TypeError("qkv must be a contiguous float32 [B, H*W, 3*heads*32] tensor")
-    if table.dtype != torch.float32 or table.dim() != 2 or not table.is_contiguous():
-        raise TypeError("table must be a contiguous float32 [(2*window-1)^2, heads] tensor")
-    B, T, W3 = qkv.shape
+    B, T, W3 = _dense(qkv, "qkv must be a contiguous float32 [B, H*W, 3*heads*32] tensor", 3)
+    _dense(table, "table must be a contiguous float32 [(2*window-1)^2, heads] tensor", 2)
     H, W = (int(n) for n in grid)
     window, shift, heads = int(window), int(shift), table.shape[1]
     if T != H * W or W3 != 3 * heads * WINDOW_ATTENTION_HEAD:
@@ -665,13 +648,9 @@ def window_attention(qkv, grid, window, shift, table, pad_qkv=None, out=None):
                          % (table.shape[0], window, (2 * window - 1) ** 2))
     if pad_qkv is not None and (pad_qkv.dtype != torch.float32 or pad_qkv.numel() != W3 or not pad_qkv.is_contiguous()):
         raise TypeError("pad_qkv must be a contiguous float32 tensor of 3*heads*32 elements (or None)")
-    D = heads * WINDOW_ATTENTION_HEAD
-    if out is None:
-        out = torch.empty((B, T, D), dtype=torch.float32, device=qkv.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, T, D) or not out.is_contiguous():
-        raise TypeError("out must be a contiguous float32 [B, H*W, heads*32] tensor")
-    check(_lib.load().mcd_window_attention(qkv.data_ptr(), None if pad_qkv is None else pad_qkv.data_ptr(), B, H, W, heads,
-                                           window, shift, table.data_ptr(), out.data_ptr(), _stream()))
+    out = _out(out, (B, T, heads * WINDOW_ATTENTION_HEAD), qkv.device, "out must be a contiguous float32 [B, H*W, heads*32] tensor")
+    check(_lib.load().mcd_window_attention(qkv.data_ptr(), _ptr(pad_qkv), B, H, W, heads, window, shift, table.data_ptr(),
+                                           out.data_ptr(), _stream()))
     return out
 
 
@@ -686,19 +665,14 @@ def patch_merge_ln(x, grid, weight, bias, eps, out=None):
     x[2i, 2j] | x[2i+1, 2j] | x[2i, 2j+1] | x[2i+1, 2j+1] (zeros past an odd edge) under LayerNorm -- the bits of layer_norm
     on the gathered rows.  C a multiple of 4, at most PATCH_MERGE_MAX_C."""
     _need_gpu(x, weight, bias, out)
-    if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous():
-        raise TypeError("x must be a contiguous float32 [B, H*W, C] tensor")
-    B, T, C = x.shape
+    B, T, C = _dense(x, "x must be a contiguous float32 [B, H*W, C] tensor", 3)
     H, W = (int(n) for n in grid)
     if T != H * W:
         raise ValueError("patch_merge_ln: x has %d tokens, the grid is %dx%d" % (T, H, W))
-    if any(t.dtype != torch.float32 or tuple(t.shape) != (4 * C,) or not t.is_contiguous() for t in (weight, bias)):
-        raise TypeError("patch_merge_ln: contiguous float32 [4C] weight / bias")
-    shape = (B, ((H + 1) // 2) * ((W + 1) // 2), 4 * C)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
-        raise TypeError("out must be a contiguous float32 [B, ceil(H/2)*ceil(W/2), 4C] tensor")
+    for t in (weight, bias):
+        _dense(t, "patch_merge_ln: contiguous float32 [4C] weight / bias", shape=(4 * C,))
+    out = _out(out, (B, ((H + 1) // 2) * ((W + 1) // 2), 4 * C), x.device,
+               "out must be a contiguous float32 [B, ceil(H/2)*ceil(W/2), 4C] tensor")
     check(_lib.load().mcd_patch_merge_ln(x.data_ptr(), B, H, W, C, weight.data_ptr(), bias.data_ptr(), float(eps),
                                          out.data_ptr(), _stream()))
     return out
@@ -732,9 +706,8 @@ def text_embed_ln(ids, type_ids, word, pos, type_table, weight, bias, eps, out=N
                                                                                or type_ids.shape != ids.shape)):
         raise TypeError("text_embed_ln: ids (and type_ids) must be int64 [B, T]")
     B, T = ids.shape
-    tables = (word, pos, type_table)
-    if any(t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() for t in tables):
-        raise TypeError("text_embed_ln: contiguous float32 [rows, D] tables")
+    for t in (word, pos, type_table):
+        _dense(t, "text_embed_ln: contiguous float32 [rows, D] tables", 2)
     D = word.shape[1]
     if pos.shape[1] != D or type_table.shape[1] != D or weight.shape != (D,) or bias.shape != (D,):
         raise ValueError("text_embed_ln: the tables, weight and bias must share the width D=%d" % D)
@@ -745,13 +718,10 @@ def text_embed_ln(ids, type_ids, word, pos, type_table, weight, bias, eps, out=N
             raise ValueError("text_embed_ln: %s outside [0, %d)" % (name, n))
     ids = ids.to(word.device).contiguous()
     type_ids = None if type_ids is None else type_ids.to(word.device).contiguous()
-    if out is None:
-        out = torch.empty((B, T, D), dtype=torch.float32, device=word.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, T, D) or not out.is_contiguous():
-        raise TypeError("out must be a contiguous float32 [B, T, D] tensor")
-    check(_lib.load().mcd_text_embed_ln(ids.data_ptr(), None if type_ids is None else type_ids.data_ptr(), word.data_ptr(),
-                                        pos.data_ptr(), type_table.data_ptr(), weight.data_ptr(), bias.data_ptr(), float(eps),
-                                        B * T, T, D, word.shape[0], type_table.shape[0], out.data_ptr(), _stream()))
+    out = _out(out, (B, T, D), word.device, "out must be a contiguous float32 [B, T, D] tensor")
+    check(_lib.load().mcd_text_embed_ln(ids.data_ptr(), _ptr(type_ids), word.data_ptr(), pos.data_ptr(), type_table.data_ptr(),
+                                        weight.data_ptr(), bias.data_ptr(), float(eps), B * T, T, D, word.shape[0],
+                                        type_table.shape[0], out.data_ptr(), _stream()))
     return out
 
 
@@ -814,13 +784,9 @@ def token_restore(src, restore, fill=None, add=None, out=None):
     for name, t, shape in (("fill", fill, (D,)), ("add", add, (1 + L, D))):
         if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous()):
             raise TypeError("%s must be a contiguous float32 tensor of shape %s" % (name, shape))
-    if out is None:
-        out = torch.empty((B, 1 + L, D), dtype=torch.float32, device=src.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, 1 + L, D) or not out.is_contiguous():
-        raise TypeError("out must be a contiguous float32 [B, 1 + L, D] tensor")
-    check(_lib.load().mcd_token_restore(src.data_ptr(), rows * D if src.dim() == 3 else 0, restore.data_ptr(),
-                                        None if fill is None else fill.data_ptr(), None if add is None else add.data_ptr(),
-                                        B, L, rows - 1, D, out.data_ptr(), _stream()))
+    out = _out(out, (B, 1 + L, D), src.device, "out must be a contiguous float32 [B, 1 + L, D] tensor")
+    check(_lib.load().mcd_token_restore(src.data_ptr(), rows * D if src.dim() == 3 else 0, restore.data_ptr(), _ptr(fill),
+                                        _ptr(add), B, L, rows - 1, D, out.data_ptr(), _stream()))
     return out
 
 
@@ -909,9 +875,7 @@ def se_gate(psum, hw, w_r, b_r, w_et, b_e):
     """K14: s [B, C] = sigmoid(b_e + w_et^T . SiLU(b_r + w_r . mean)), mean = psum summed over its tiles / hw;
     w_r [sq, C] (the reduce convolution's weight), w_et [sq, C] (the expand convolution's weight, transposed)."""
     _need_gpu(psum)
-    if psum.dtype != torch.float32 or psum.dim() != 3 or not psum.is_contiguous():
-        raise TypeError("psum must be a contiguous float32 [B, T, C] tensor")
-    B, T, C = psum.shape
+    B, T, C = _dense(psum, "psum must be a contiguous float32 [B, T, C] tensor", 3)
     sq = b_r.numel()
     _vec(w_r, sq * C, "w_r")
     _vec(b_r, sq, "b_r")
@@ -930,8 +894,7 @@ def channel_scale_(y, s):
     y = _nhwc(y, "y")
     B, H, W, C = y.shape
     _need_gpu(s)
-    if s.dtype != torch.float32 or tuple(s.shape) != (B, C) or not s.is_contiguous():
-        raise TypeError("s must be a contiguous float32 [B, C] tensor")
+    _dense(s, "s must be a contiguous float32 [B, C] tensor", shape=(B, C))
     L = _lib.load()
     check(L.mcd_channel_scale(y.data_ptr(), B, H * W, C, s.data_ptr(), _stream()))
     return y

@@ -461,83 +461,69 @@ __global__ __launch_bounds__(64 * AC_WAVES) void vit_attention_cls_kernel(
     }
 }
 
+// The checks and the launch of K9, K9M, K9B and K9A (`name` is the entry's, for the messages).  lens and rel are the extra
+// operands of K9M and K9B (NULL elsewhere, and NULL is aligned), `aligned` the entry's sentence about all of them.
+// launch(grid, block) starts the entry's kernel and returns that kernel's name.
+template <typename Launch>
+int attention_entry(const char* name, const float* qkv, int64_t B, int64_t T, int64_t H, const int32_t* lens, const float* rel,
+                    const char* aligned, float* out, Launch launch) {
+    MCD_REQUIRE(qkv && out, MCD_E_ARG, "%s: NULL pointer", name);
+    MCD_REQUIRE(B >= 0 && T >= 1 && H >= 1, MCD_E_ARG, "%s: bad shape B=%lld T=%lld H=%lld", name, (long long)B, (long long)T,
+                (long long)H);
+    MCD_REQUIRE(T <= AT_MAX_T, MCD_E_UNSUPPORTED, "%s: T=%lld tokens, at most %d (one wave per 32 queries, 8 waves)", name,
+                (long long)T, AT_MAX_T);
+    MCD_REQUIRE(B <= 65535 && H <= 65535, MCD_E_UNSUPPORTED, "%s: B and H must be <= 65535", name);
+    MCD_REQUIRE(((uintptr_t)qkv) % 16 == 0 && ((uintptr_t)out) % 16 == 0 && ((uintptr_t)lens) % 4 == 0 &&
+                    ((uintptr_t)rel) % 16 == 0,
+                MCD_E_ARG, "%s: %s", name, aligned);
+    if (B == 0) return MCD_OK;
+    const int nwaves = (int)((T + 31) / 32) + 1;   // one per 32 queries + the loader
+    const char* kernel = launch(dim3((unsigned)H, (unsigned)B), dim3(64 * nwaves));
+    MCD_LAUNCH_CHECK(kernel);
+    return MCD_OK;
+}
+
 }  // namespace
 
 extern "C" int mcd_vit_attention(const float* qkv, int64_t B, int64_t T, int64_t H, float* out, mcd_stream_t stream) {
-    MCD_REQUIRE(qkv && out, MCD_E_ARG, "mcd_vit_attention: NULL pointer");
-    MCD_REQUIRE(B >= 0 && T >= 1 && H >= 1, MCD_E_ARG, "mcd_vit_attention: bad shape B=%lld T=%lld H=%lld", (long long)B,
-                (long long)T, (long long)H);
-    MCD_REQUIRE(T <= AT_MAX_T, MCD_E_UNSUPPORTED, "mcd_vit_attention: T=%lld tokens, at most %d (one wave per 32 queries, 8 waves)",
-                (long long)T, AT_MAX_T);
-    MCD_REQUIRE(B <= 65535 && H <= 65535, MCD_E_UNSUPPORTED, "mcd_vit_attention: B and H must be <= 65535");
-    MCD_REQUIRE(((uintptr_t)qkv) % 16 == 0 && ((uintptr_t)out) % 16 == 0, MCD_E_ARG,
-                "mcd_vit_attention: qkv and out must be 16-byte aligned");
-    if (B == 0) return MCD_OK;
-    const int nwaves = (int)((T + 31) / 32) + 1;   // one per 32 queries + the loader
-    hipLaunchKernelGGL(vit_attention_kernel, dim3((unsigned)H, (unsigned)B), dim3(64 * nwaves), 0, (hipStream_t)stream, qkv,
-                       (int)T, (int)H, out);
-    MCD_LAUNCH_CHECK("vit_attention_kernel");
-    return MCD_OK;
+    const auto launch = [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(vit_attention_kernel, grid, block, 0, (hipStream_t)stream, qkv, (int)T, (int)H, out);
+        return "vit_attention_kernel";
+    };
+    return attention_entry("mcd_vit_attention", qkv, B, T, H, nullptr, nullptr, "qkv and out must be 16-byte aligned", out, launch);
 }
 
 extern "C" int mcd_vit_attention_keylen(const float* qkv, int64_t B, int64_t T, int64_t H, const int32_t* lens, float* out,
                                         mcd_stream_t stream) {
-    MCD_REQUIRE(qkv && out, MCD_E_ARG, "mcd_vit_attention_keylen: NULL pointer");
-    MCD_REQUIRE(B >= 0 && T >= 1 && H >= 1, MCD_E_ARG, "mcd_vit_attention_keylen: bad shape B=%lld T=%lld H=%lld",
-                (long long)B, (long long)T, (long long)H);
-    MCD_REQUIRE(T <= AT_MAX_T, MCD_E_UNSUPPORTED,
-                "mcd_vit_attention_keylen: T=%lld tokens, at most %d (one wave per 32 queries, 8 waves)", (long long)T, AT_MAX_T);
-    MCD_REQUIRE(B <= 65535 && H <= 65535, MCD_E_UNSUPPORTED, "mcd_vit_attention_keylen: B and H must be <= 65535");
-    MCD_REQUIRE(((uintptr_t)qkv) % 16 == 0 && ((uintptr_t)out) % 16 == 0 && ((uintptr_t)lens) % 4 == 0, MCD_E_ARG,
-                "mcd_vit_attention_keylen: qkv and out must be 16-byte aligned, lens 4-byte aligned");
-    if (B == 0) return MCD_OK;
-    const int nwaves = (int)((T + 31) / 32) + 1;   // one per 32 queries + the loader
-    hipLaunchKernelGGL(vit_attention_keylen_kernel, dim3((unsigned)H, (unsigned)B), dim3(64 * nwaves), 0, (hipStream_t)stream,
-                       qkv, (int)T, (int)H, lens, out);
-    MCD_LAUNCH_CHECK("vit_attention_keylen_kernel");
-    return MCD_OK;
+    const auto launch = [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(vit_attention_keylen_kernel, grid, block, 0, (hipStream_t)stream, qkv, (int)T, (int)H, lens, out);
+        return "vit_attention_keylen_kernel";
+    };
+    return attention_entry("mcd_vit_attention_keylen", qkv, B, T, H, lens, nullptr,
+                           "qkv and out must be 16-byte aligned, lens 4-byte aligned", out, launch);
 }
 
 extern "C" int mcd_vit_attention_relbias(const float* qkv, int64_t B, int64_t T, int64_t H, const int32_t* lens,
                                          const float* rel, float* out, mcd_stream_t stream) {
-    MCD_REQUIRE(qkv && out, MCD_E_ARG, "mcd_vit_attention_relbias: NULL pointer");
-    MCD_REQUIRE(B >= 0 && T >= 1 && H >= 1, MCD_E_ARG, "mcd_vit_attention_relbias: bad shape B=%lld T=%lld H=%lld",
-                (long long)B, (long long)T, (long long)H);
-    MCD_REQUIRE(T <= AT_MAX_T, MCD_E_UNSUPPORTED,
-                "mcd_vit_attention_relbias: T=%lld tokens, at most %d (one wave per 32 queries, 8 waves)", (long long)T, AT_MAX_T);
-    MCD_REQUIRE(B <= 65535 && H <= 65535, MCD_E_UNSUPPORTED, "mcd_vit_attention_relbias: B and H must be <= 65535");
-    MCD_REQUIRE(((uintptr_t)qkv) % 16 == 0 && ((uintptr_t)out) % 16 == 0 && ((uintptr_t)lens) % 4 == 0 &&
-                    ((uintptr_t)rel) % 16 == 0,
-                MCD_E_ARG, "mcd_vit_attention_relbias: qkv, out and rel must be 16-byte aligned, lens 4-byte aligned");
-    if (B == 0) return MCD_OK;
-    const int nwaves = (int)((T + 31) / 32) + 1;   // one per 32 queries + the loader
-    if (!rel) {                                    // no bias: K9M's own kernel, K9M's bits
-        hipLaunchKernelGGL(vit_attention_keylen_kernel, dim3((unsigned)H, (unsigned)B), dim3(64 * nwaves), 0,
-                           (hipStream_t)stream, qkv, (int)T, (int)H, lens, out);
-        MCD_LAUNCH_CHECK("vit_attention_keylen_kernel");
-        return MCD_OK;
-    }
-    hipLaunchKernelGGL(vit_attention_relbias_kernel, dim3((unsigned)H, (unsigned)B), dim3(64 * nwaves), 0, (hipStream_t)stream,
-                       qkv, (int)T, (int)H, lens, rel, out);
-    MCD_LAUNCH_CHECK("vit_attention_relbias_kernel");
-    return MCD_OK;
+    const auto launch = [&](dim3 grid, dim3 block) {
+        if (!rel) {   // no bias: K9M's own kernel, K9M's bits
+            hipLaunchKernelGGL(vit_attention_keylen_kernel, grid, block, 0, (hipStream_t)stream, qkv, (int)T, (int)H, lens, out);
+            return "vit_attention_keylen_kernel";
+        }
+        hipLaunchKernelGGL(vit_attention_relbias_kernel, grid, block, 0, (hipStream_t)stream, qkv, (int)T, (int)H, lens, rel, out);
+        return "vit_attention_relbias_kernel";
+    };
+    return attention_entry("mcd_vit_attention_relbias", qkv, B, T, H, lens, rel,
+                           "qkv, out and rel must be 16-byte aligned, lens 4-byte aligned", out, launch);
 }
 
 extern "C" int mcd_vit_attention_causal(const float* qkv, int64_t B, int64_t T, int64_t H, float* out, mcd_stream_t stream) {
-    MCD_REQUIRE(qkv && out, MCD_E_ARG, "mcd_vit_attention_causal: NULL pointer");
-    MCD_REQUIRE(B >= 0 && T >= 1 && H >= 1, MCD_E_ARG, "mcd_vit_attention_causal: bad shape B=%lld T=%lld H=%lld", (long long)B,
-                (long long)T, (long long)H);
-    MCD_REQUIRE(T <= AT_MAX_T, MCD_E_UNSUPPORTED,
-                "mcd_vit_attention_causal: T=%lld tokens, at most %d (one wave per 32 queries, 8 waves)", (long long)T, AT_MAX_T);
-    MCD_REQUIRE(B <= 65535 && H <= 65535, MCD_E_UNSUPPORTED, "mcd_vit_attention_causal: B and H must be <= 65535");
-    MCD_REQUIRE(((uintptr_t)qkv) % 16 == 0 && ((uintptr_t)out) % 16 == 0, MCD_E_ARG,
-                "mcd_vit_attention_causal: qkv and out must be 16-byte aligned");
-    if (B == 0) return MCD_OK;
-    const int nwaves = (int)((T + 31) / 32) + 1;   // one per 32 queries + the loader
-    hipLaunchKernelGGL(vit_attention_causal_kernel, dim3((unsigned)H, (unsigned)B), dim3(64 * nwaves), 0, (hipStream_t)stream,
-                       qkv, (int)T, (int)H, out);
-    MCD_LAUNCH_CHECK("vit_attention_causal_kernel");
-    return MCD_OK;
+    const auto launch = [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(vit_attention_causal_kernel, grid, block, 0, (hipStream_t)stream, qkv, (int)T, (int)H, out);
+        return "vit_attention_causal_kernel";
+    };
+    return attention_entry("mcd_vit_attention_causal", qkv, B, T, H, nullptr, nullptr, "qkv and out must be 16-byte aligned", out,
+                           launch);
 }
 
 extern "C" int mcd_vit_attention_long(const float* qkv, int64_t B, int64_t T, int64_t H, float* out, mcd_stream_t stream) {

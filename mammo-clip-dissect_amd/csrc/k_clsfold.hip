@@ -177,14 +177,7 @@ int cf_heads_per_pass(int64_t T, int64_t H, int64_t D) {
 template <int HC>
 int cf_launch(const float* u, int64_t u_img, const float* n, int64_t n_row, int64_t n_img, int64_t B, int64_t T, int64_t H,
               int64_t D, float* m, int64_t m_img, hipStream_t st) {
-    static bool attr_done[MCD_MAX_DEVICES] = {};
-    const int dev = mcd_cur_device();
-    if (!attr_done[dev]) {
-        if (hipFuncSetAttribute((const void*)cls_token_mix_kernel<HC>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                CF_LDS_BYTES) != hipSuccess)
-            return mcd_fail(MCD_E_LAUNCH, "mcd_cls_token_mix: cannot reserve %d bytes of LDS", CF_LDS_BYTES);
-        attr_done[dev] = true;
-    }
+    MCD_RESERVE_LDS_ONCE(cls_token_mix_kernel<HC>, CF_LDS_BYTES, "mcd_cls_token_mix: cannot reserve %d bytes of LDS", CF_LDS_BYTES);
     hipLaunchKernelGGL(cls_token_mix_kernel<HC>, dim3((unsigned)B), dim3(CF_THREADS), cf_lds_bytes(HC, T, H, D), st, u, u_img, n,
                        n_row, n_img, (int)T, (int)H, (int)D, m, m_img);
     MCD_LAUNCH_CHECK("cls_token_mix_kernel");

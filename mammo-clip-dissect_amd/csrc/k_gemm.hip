@@ -1031,13 +1031,14 @@ static bool gemm_use_big(int64_t N, int64_t C) { return mcd_cdiv(N, GB_M) * mcd_
 
 // CUs of the current device (the persistent kernels launch one workgroup per CU)
 static int gemm_cu_count() {
-    static int n_cu_dev[MCD_MAX_DEVICES];
+    static std::atomic<int> n_cu_dev[MCD_MAX_DEVICES];      // 0: not asked yet; threads that race store the same count
     const int dev = mcd_cur_device();
-    int& n_cu = n_cu_dev[dev];
+    int n_cu = n_cu_dev[dev].load(std::memory_order_acquire);
     if (n_cu == 0) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
         if (n_cu < 8) n_cu = 256;
+        n_cu_dev[dev].store(n_cu, std::memory_order_release);
     }
     return n_cu;
 }
@@ -1078,25 +1079,11 @@ extern "C" int mcd_embed_gemm(const float* I, int64_t ldi, const float* T, int64
             const int64_t grid64 = mcd_cdiv(nbands, 8) * 8 * GB_RS * tiles_n;
             MCD_REQUIRE(grid64 < (1LL << 31), MCD_E_UNSUPPORTED, "mcd_embed_gemm: too many tiles for one launch");
             const size_t shmem = 8u * (size_t)GB_T_BYTES;   // 2 stages x 4 arrays: 128 KB
-            static bool attr_done_dev[MCD_MAX_DEVICES];
-            bool& attr_done = attr_done_dev[mcd_cur_device()];
-            if (!attr_done) {
-                MCD_REQUIRE(hipFuncSetAttribute((const void*)gemm_nt_bf16_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                8 * GB_T_BYTES) == hipSuccess,
-                            MCD_E_LAUNCH, "mcd_embed_gemm: cannot reserve 128 KB of LDS");
-                attr_done = true;
-            }
+            MCD_RESERVE_LDS_ONCE(gemm_nt_bf16_big_kernel, shmem, "mcd_embed_gemm: cannot reserve 128 KB of LDS");
             hipLaunchKernelGGL(gemm_nt_bf16_big_kernel, dim3((unsigned)grid64), dim3(GB_THREADS), shmem, st, a_hi, a_lo, b_hi,
                                b_lo, Kp, N, C, P, ldp, tiles_m, tiles_n);
         } else {
-            static bool attr2_dev[MCD_MAX_DEVICES];
-            bool& attr2 = attr2_dev[mcd_cur_device()];
-            if (!attr2) {
-                MCD_REQUIRE(hipFuncSetAttribute((const void*)gemm_nt_bf16_persist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                GP_NSTAGE * GP_STAGE) == hipSuccess,
-                            MCD_E_LAUNCH, "mcd_embed_gemm: cannot reserve 128 KB of LDS");
-                attr2 = true;
-            }
+            MCD_RESERVE_LDS_ONCE(gemm_nt_bf16_persist_kernel, GP_NSTAGE * GP_STAGE, "mcd_embed_gemm: cannot reserve 128 KB of LDS");
             const int ptiles_m = (int)mcd_cdiv(N, GP_M), ptiles_n = (int)mcd_cdiv(C, GP_N);
             MCD_REQUIRE((int64_t)GP_M * ldp < (1LL << 31), MCD_E_UNSUPPORTED, "mcd_embed_gemm: ldp too large");
             const unsigned pgrid = (unsigned)((gemm_cu_count() / 8) * 8);   // one workgroup per CU, a multiple of the 8 XCDs
@@ -1257,13 +1244,7 @@ extern "C" int mcd_embed_gemm_exp(const float* I, int64_t ldi, const float* T, i
     // late start of the workgroups with the shorter tile walk (k_gexp_v6.inc), in cycles of one tile period: ~1 200 per k-step
     // + ~7 000 of boundary phase
     const int stagger = (int)(Kp / 32) * 1200 + 7000;
-    static bool attr[MCD_MAX_DEVICES];
-    if (!attr[dev]) {
-        MCD_REQUIRE(hipFuncSetAttribute((const void*)gemm_nt_bf16_exp_v6_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, G6_LDS) ==
-                        hipSuccess,
-                    MCD_E_LAUNCH, "mcd_embed_gemm_exp: cannot reserve the LDS ring");
-        attr[dev] = true;
-    }
+    MCD_RESERVE_LDS_ONCE(gemm_nt_bf16_exp_v6_kernel, G6_LDS, "mcd_embed_gemm_exp: cannot reserve the LDS ring");
     int launches = 0;
     gexp_time_mark(dev, 0, st, 0);
     for (int rep_ = 0; rep_ < (g_gexp_time > 1 ? g_gexp_time : 1); ++rep_) {   // (timing: the same launch, back to back)

@@ -16,6 +16,8 @@
 //   replaces  SwinPatchMerging.forward up to .norm (transformers modeling_swin.py): F.pad to even sizes, four strided
 //             slices, cat and nn.LayerNorm -- a [B, H/2 * W/2, 4C] temporary written and read again.
 // One wave gathers the four neighbours' C values (zeros past an odd edge) into K10's registers and runs ln_row on them.
+#include <type_traits>
+
 #include "mcd_common.h"
 #include "../../include/mcd_text.h"
 #include "../../include/mcd_swin.h"
@@ -129,6 +131,25 @@ __global__ __launch_bounds__(256) void patch_merge_ln_kernel(const float* __rest
     ln_row<NV>(v, lane, nq, 4 * C, gamma, beta, eps, out, row);
 }
 
+// The instantiated NV (float4 per lane) of a row of nq float4: the smallest of 1, 2, 3, 4, 6, 8 that holds it (nq <= 512).
+int ln_nv(int64_t nq) {
+    const int nv = (int)mcd_cdiv(nq, 64);
+    return nv <= 1 ? 1 : nv <= 4 ? nv : nv <= 6 ? 6 : 8;
+}
+
+// launch(NV as a compile-time constant) for the rows of K10, K24 and K32: the one place that lists the instantiations.
+template <typename Launch>
+void ln_dispatch(int64_t nq, Launch launch) {
+    switch (ln_nv(nq)) {
+        case 1: return launch(std::integral_constant<int, 1>());
+        case 2: return launch(std::integral_constant<int, 2>());
+        case 3: return launch(std::integral_constant<int, 3>());
+        case 4: return launch(std::integral_constant<int, 4>());
+        case 6: return launch(std::integral_constant<int, 6>());
+        default: return launch(std::integral_constant<int, 8>());
+    }
+}
+
 }  // namespace
 
 extern "C" int mcd_patch_merge_ln(const float* x, int64_t B, int64_t H, int64_t W, int64_t C, const float* gamma,
@@ -146,17 +167,10 @@ extern "C" int mcd_patch_merge_ln(const float* x, int64_t B, int64_t H, int64_t 
     const int64_t rows = B * ((H + 1) / 2) * ((W + 1) / 2);
     MCD_REQUIRE(mcd_cdiv(rows, 4) < (1LL << 31), MCD_E_UNSUPPORTED, "mcd_patch_merge_ln: %lld output rows", (long long)rows);
     const unsigned grid = (unsigned)mcd_cdiv(rows, 4);
-    const int nv = (int)mcd_cdiv(C, 64);
-#define MCD_PM(NV)                                                                                                       \
-    hipLaunchKernelGGL(patch_merge_ln_kernel<NV>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, rows, (int)H, (int)W, \
-                       (int)C, gamma, beta, eps, out)
-    if (nv <= 1) MCD_PM(1);
-    else if (nv == 2) MCD_PM(2);
-    else if (nv == 3) MCD_PM(3);
-    else if (nv == 4) MCD_PM(4);
-    else if (nv <= 6) MCD_PM(6);
-    else MCD_PM(8);
-#undef MCD_PM
+    ln_dispatch(C, [&](auto nv) {      // a row of 4C floats
+        hipLaunchKernelGGL(patch_merge_ln_kernel<decltype(nv)::value>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, rows,
+                           (int)H, (int)W, (int)C, gamma, beta, eps, out);
+    });
     MCD_LAUNCH_CHECK("patch_merge_ln_kernel");
     return MCD_OK;
 }
@@ -170,16 +184,10 @@ extern "C" int mcd_layer_norm(const float* x, int64_t rows, int64_t D, const flo
                 MCD_E_ARG, "mcd_layer_norm: pointers must be 16-byte aligned");
     if (rows == 0) return MCD_OK;
     const unsigned grid = (unsigned)mcd_cdiv(rows, 4);
-    const int nv = (int)mcd_cdiv(D / 4, 64);
-#define MCD_LN(NV) \
-    hipLaunchKernelGGL(layer_norm_kernel<NV>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, rows, (int)D, gamma, beta, eps, y)
-    if (nv <= 1) MCD_LN(1);
-    else if (nv == 2) MCD_LN(2);
-    else if (nv == 3) MCD_LN(3);
-    else if (nv == 4) MCD_LN(4);
-    else if (nv <= 6) MCD_LN(6);
-    else MCD_LN(8);
-#undef MCD_LN
+    ln_dispatch(D / 4, [&](auto nv) {
+        hipLaunchKernelGGL(layer_norm_kernel<decltype(nv)::value>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, rows, (int)D,
+                           gamma, beta, eps, y);
+    });
     MCD_LAUNCH_CHECK("layer_norm_kernel");
     return MCD_OK;
 }
@@ -199,17 +207,10 @@ extern "C" int mcd_text_embed_ln(const int64_t* ids, const int64_t* type_ids, co
                 MCD_E_ARG, "mcd_text_embed_ln: float pointers must be 16-byte aligned, id pointers 8-byte aligned");
     if (rows == 0) return MCD_OK;
     const unsigned grid = (unsigned)mcd_cdiv(rows, 4);
-    const int nv = (int)mcd_cdiv(D / 4, 64);
-#define MCD_TE(NV)                                                                                                             \
-    hipLaunchKernelGGL(text_embed_ln_kernel<NV>, dim3(grid), dim3(256), 0, (hipStream_t)stream, ids, type_ids, word, pos, type, \
-                       gamma, beta, eps, rows, (int)T, (int)D, vocab, n_type, out)
-    if (nv <= 1) MCD_TE(1);
-    else if (nv == 2) MCD_TE(2);
-    else if (nv == 3) MCD_TE(3);
-    else if (nv == 4) MCD_TE(4);
-    else if (nv <= 6) MCD_TE(6);
-    else MCD_TE(8);
-#undef MCD_TE
+    ln_dispatch(D / 4, [&](auto nv) {
+        hipLaunchKernelGGL(text_embed_ln_kernel<decltype(nv)::value>, dim3(grid), dim3(256), 0, (hipStream_t)stream, ids, type_ids,
+                           word, pos, type, gamma, beta, eps, rows, (int)T, (int)D, vocab, n_type, out);
+    });
     MCD_LAUNCH_CHECK("text_embed_ln_kernel");
     return MCD_OK;
 }

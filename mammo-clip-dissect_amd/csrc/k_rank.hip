@@ -237,7 +237,7 @@ extern "C" int mcd_rank_reorder(const float* P, int64_t ldP, int64_t N, int64_t 
     // whole 16-byte quads: aligned base and pitch, and every tile inside the row (the host pads S/P rows to a
     // multiple of 4 floats, or the last tile takes the scalar kernel below)
     const bool vec4 = (ldP % 4 == 0) && (((uintptr_t)P) % 16 == 0) && (mcd_cdiv(C, RK_CT) * RK_CT <= ldP);
-    if (shmem > 48 * 1024) {
+    if (shmem > 48 * 1024) {   // not cached like mcd_reserve_lds(): the size grows with top_n, so it is set on every call
         hipError_t e1 = hipFuncSetAttribute((const void*)rank_reorder_kernel<true>,
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
         hipError_t e2 = hipFuncSetAttribute((const void*)rank_reorder_kernel<false>,

@@ -334,15 +334,8 @@ template <int BC, int KS, bool RES>
 int launch_igemm(const float* x, int64_t B, int64_t H, int64_t W, int64_t Cin, const float* wt, const float* bias,
                  const float* res, int64_t Cout, int stride, int pad, int64_t Ho, int64_t Wo, int relu_in, int relu_out,
                  float* y, hipStream_t st) {
-    static bool attr_done[MCD_MAX_DEVICES] = {};
     constexpr size_t lds = (size_t)2 * IG_BK * (IG_LDP + BC + 4) * sizeof(float);
-    const int dev = mcd_cur_device();
-    if (!attr_done[dev]) {
-        if (hipFuncSetAttribute((const void*)conv_igemm_kernel<BC, KS, RES>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return mcd_fail(MCD_E_LAUNCH, "mcd_conv_igemm_nhwc: cannot reserve %zu bytes of LDS", lds);
-        attr_done[dev] = true;
-    }
+    MCD_RESERVE_LDS_ONCE((conv_igemm_kernel<BC, KS, RES>), lds, "mcd_conv_igemm_nhwc: cannot reserve %zu bytes of LDS", lds);
     const int64_t Mtot = B * Ho * Wo;
     const int64_t nct = mcd_cdiv(Cout, BC), npt = mcd_cdiv(Mtot, IG_BP);
     MCD_REQUIRE(nct * npt < ((int64_t)1 << 31), MCD_E_UNSUPPORTED, "mcd_conv_igemm_nhwc: %lld tiles exceed the grid",

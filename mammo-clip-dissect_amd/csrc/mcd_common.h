@@ -6,6 +6,8 @@
 #include <stdarg.h>
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "../../include/mcd_hip.h"
 
 #define MCD_WAVE 64
@@ -47,6 +49,25 @@ static inline int mcd_cur_device(void) {
     if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= MCD_MAX_DEVICES) d = 0;
     return d;
 }
+
+// Reserve `bytes` of dynamic LDS for `kernel` on the current device, once per (kernel, device): `done` is the call site's own
+// static mcd_once_t.  The flags are atomics -- acquire on the read, release after the attribute is set -- so entries may be
+// called from several host threads; two threads that race both set the attribute, which is idempotent.  false: the runtime
+// refused, and the flag stays clear.
+typedef std::atomic<bool> mcd_once_t[MCD_MAX_DEVICES];
+static inline bool mcd_reserve_lds(mcd_once_t& done, const void* kernel, size_t bytes) {
+    std::atomic<bool>& flag = done[mcd_cur_device()];
+    if (flag.load(std::memory_order_acquire)) return true;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return false;
+    flag.store(true, std::memory_order_release);
+    return true;
+}
+// ... or leave the entry with MCD_E_LAUNCH and the given message
+#define MCD_RESERVE_LDS_ONCE(kernel, bytes, ...)                                                              \
+    do {                                                                                                      \
+        static mcd_once_t done__;                                                                             \
+        MCD_REQUIRE(mcd_reserve_lds(done__, (const void*)(kernel), bytes), MCD_E_LAUNCH, __VA_ARGS__);        \
+    } while (0)
 
 // ---- device helpers ---------------------------------------------------------------------------
 // Order-preserving map fp32 -> u32 (larger float <=> larger key); every NaN maps to the top key,
