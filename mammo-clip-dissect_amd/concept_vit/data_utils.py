@@ -41,6 +41,7 @@ import torch.nn.functional as F
 from torch.nn.modules import module as _nn_module
 
 from .. import core
+from . import checkpoint_io
 
 PROJ_DIM = 512
 # The image tower's mask-free fp32 attention runs on the HIP kernels K9 (T <= 256) and K9L (longer sequences, the
@@ -1435,9 +1436,9 @@ class HFDinov2(_HFClassifier):
     H != W, gets the table interpolated."""
     prefix = "dinov2"
 
-    def __init__(self, num_labels=2, image_size=224, patch=14, layer_scale=1.0, **kw):
+    def __init__(self, num_labels=2, image_size=224, patch=14, layer_scale=1.0, eps=1e-6, **kw):
         super().__init__()
-        self.dinov2 = HFTower(interpolate=True, image_size=image_size, patch=patch, eps=1e-6, layer_scale=layer_scale, **kw)
+        self.dinov2 = HFTower(interpolate=True, image_size=image_size, patch=patch, eps=eps, layer_scale=layer_scale, **kw)
         self.classifier = nn.Linear(2 * self.dinov2.out_dim, num_labels)
 
     def forward(self, image):
@@ -2480,14 +2481,15 @@ class OpenAIClip(nn.Module):
     block to the class-token row (cls_tail_route, K9C)."""
 
     def __init__(self, embed_dim=512, image_resolution=224, vision_layers=12, vision_width=768, vision_patch_size=16,
-                 context_length=77, vocab_size=49408, transformer_width=512, transformer_heads=8, transformer_layers=12):
+                 context_length=77, vocab_size=49408, transformer_width=512, transformer_heads=8, transformer_layers=12,
+                 vision_heads=None):
         super().__init__()
         self.context_length, self.vocab_size, self.embed_dim = context_length, vocab_size, embed_dim
         if isinstance(vision_layers, (tuple, list)):
             self.visual = ModifiedResNet(tuple(vision_layers), embed_dim, vision_width * 32 // 64, image_resolution, vision_width)
         else:
             self.visual = _ClipVisionTransformer(image_resolution, vision_patch_size, vision_width, vision_layers,
-                                                 vision_width // 64, embed_dim)
+                                                 vision_heads or vision_width // 64, embed_dim)
         self.transformer = _ClipTransformer(transformer_width, transformer_layers, transformer_heads, causal=True)
         self.token_embedding = nn.Embedding(vocab_size, transformer_width)
         self.positional_embedding = nn.Parameter(torch.empty(context_length, transformer_width))
@@ -2511,13 +2513,15 @@ class OpenAIClip(nn.Module):
         nn.init.normal_(self.text_projection, std=self.transformer.width ** -0.5)
 
     @classmethod
-    def from_state_dict(cls, sd):
+    def from_state_dict(cls, sd, **heads):
         """The model of an OpenAI CLIP state dict: the configuration from its shapes (openai_clip_config), the three
         scalar keys input_resolution / context_length / vocab_size ignored by name, floating tensors upcast to fp32, and
-        a STRICT load: a missing or an unexpected key is an error, never a tower of random weights."""
+        a STRICT load: a missing or an unexpected key is an error, never a tower of random weights.  heads:
+        vision_heads= / transformer_heads= of a ViT CLIP whose head counts are known (a snapshot's config.json) in place
+        of width // 64."""
         sd = {k: (v.float() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in sd.items()
               if k not in _CLIP_IGNORED}
-        model = cls(**openai_clip_config(sd))
+        model = cls(**dict(openai_clip_config(sd), **heads))
         model.load_state_dict(sd, strict=True)
         return model
 
@@ -2758,12 +2762,14 @@ def _is_torchscript_archive(path):
 
 
 def openai_clip_state_dict(ckpt):
-    """ckpt: a state dict, or a LOCAL path to one (read with weights_only=True) or to a TorchScript archive, whose
-    state_dict() is taken as clip.load does (clip.py:126-138; loading such an archive unpickles its code)."""
+    """ckpt: a state dict, or a LOCAL path to one (read with weights_only=True), to a .safetensors file or a snapshot
+    directory (checkpoint_io.resolve_checkpoint), or to a TorchScript archive, whose state_dict() is taken as clip.load
+    does (clip.py:126-138; loading such an archive unpickles its code).  A transformers CLIPModel state dict comes back
+    as it is: get_target_model('openai_clip') renames it (hf_clip_to_openai)."""
     if isinstance(ckpt, str):
-        if _is_torchscript_archive(ckpt):
+        if os.path.isfile(ckpt) and _is_torchscript_archive(ckpt):
             return dict(torch.jit.load(ckpt, map_location="cpu").state_dict())
-        ckpt = torch.load(ckpt, map_location="cpu", weights_only=True)
+        ckpt = checkpoint_io.resolve_checkpoint(ckpt).state_dict()
     return ckpt["model"] if isinstance(ckpt, dict) and "model" in ckpt and "text_projection" not in ckpt else ckpt
 
 
@@ -2844,12 +2850,12 @@ class _HFClipLayer(nn.Module):
     """CLIPEncoderLayer, pre-norm: x1 = x + self_attn(layer_norm1(x)), out = x1 + mlp(layer_norm2(x1)).  Returns the
     hidden-state tensor."""
 
-    def __init__(self, dim, heads, mlp, hidden_act):
+    def __init__(self, dim, heads, mlp, hidden_act, eps=1e-5):
         super().__init__()
         self.self_attn = _HFClipAttention(dim, heads)
-        self.layer_norm1 = nn.LayerNorm(dim, eps=1e-5)
+        self.layer_norm1 = nn.LayerNorm(dim, eps=eps)
         self.mlp = _HFClipMLP(dim, mlp, hidden_act)
-        self.layer_norm2 = nn.LayerNorm(dim, eps=1e-5)
+        self.layer_norm2 = nn.LayerNorm(dim, eps=eps)
 
     def forward(self, x, hip=False):
         """hip: the model has checked clip_tower_route; the layer takes the HIP route unless a hook sits inside it."""
@@ -2867,9 +2873,9 @@ class _HFClipLayer(nn.Module):
 
 
 class _HFClipEncoder(nn.Module):
-    def __init__(self, depth, dim, heads, mlp, hidden_act):
+    def __init__(self, depth, dim, heads, mlp, hidden_act, eps=1e-5):
         super().__init__()
-        self.layers = nn.ModuleList([_HFClipLayer(dim, heads, mlp, hidden_act) for _ in range(depth)])
+        self.layers = nn.ModuleList([_HFClipLayer(dim, heads, mlp, hidden_act, eps) for _ in range(depth)])
 
     def forward(self, x, hip=False):
         for layer in self.layers:                    # through __call__: the hooks on layers[i] fire
@@ -2883,12 +2889,12 @@ class _HFClipVisionTransformer(nn.Module):
     token for pooler_output, and CLIPForImageClassification discards the result; here it holds its parameters and is not
     computed at all, so a hook on vision_model.post_layernorm fires in transformers and never here."""
 
-    def __init__(self, dim, image_size, patch, depth, heads, mlp, hidden_act):
+    def __init__(self, dim, image_size, patch, depth, heads, mlp, hidden_act, eps=1e-5):
         super().__init__()
         self.embeddings = _HFClipEmbeddings(dim, image_size, patch)
-        self.pre_layrnorm = nn.LayerNorm(dim, eps=1e-5)
-        self.encoder = _HFClipEncoder(depth, dim, heads, mlp, hidden_act)
-        self.post_layernorm = nn.LayerNorm(dim, eps=1e-5)
+        self.pre_layrnorm = nn.LayerNorm(dim, eps=eps)
+        self.encoder = _HFClipEncoder(depth, dim, heads, mlp, hidden_act, eps)
+        self.post_layernorm = nn.LayerNorm(dim, eps=eps)
 
     def forward(self, x, hip=False):
         if not hip:
@@ -2943,8 +2949,8 @@ class HFClip(nn.Module):
 
     forward(images) -> the logits tensor [B, num_labels] (encode_image is the same call): the patch convolution, the class
     embedding in front, + the position table, pre_layrnorm, the pre-norm layers (QuickGELU for hidden_act 'quick_gelu', erf
-    GELU for 'gelu'; LayerNorm eps 1e-5), then the mean of last_hidden_state[:, 1:] -- last_hidden_state does not pass
-    post_layernorm, whose parameters are loaded and whose result nothing reads (transformers computes it for pooler_output
+    GELU for 'gelu'; LayerNorm eps `eps`, CLIPVisionConfig's layer_norm_eps, 1e-5 by default), then the mean of
+    last_hidden_state[:, 1:] -- last_hidden_state does not pass post_layernorm, whose parameters are loaded and whose result nothing reads (transformers computes it for pooler_output
     and this class discards it; here it is not computed) -- and the classifier.
     Hook points: vision_model.encoder.layers[i] and every module under it.  A layer returns its hidden-state tensor
     [B, T, D]: so does transformers 5.x; transformers 4.41.1, the reference's pin, returns a 1-tuple, which the reference's
@@ -2955,18 +2961,18 @@ class HFClip(nn.Module):
     last layer always runs whole.  A layer with a hook on a module inside it runs its ATen modules for that call."""
 
     def __init__(self, num_labels=2, image_size=224, patch=16, hidden=768, layers=12, heads=12, mlp=3072,
-                 hidden_act="quick_gelu"):
+                 hidden_act="quick_gelu", eps=1e-5):
         super().__init__()
         if hidden_act not in ("quick_gelu", "gelu"):
             raise ValueError("hidden_act must be 'quick_gelu' or 'gelu', got %r" % (hidden_act,))
         if not isinstance(image_size, int):
             raise ValueError("HFClip: image_size must be an int (the position table is a square grid), got %r" % (image_size,))
         self.heads = heads
-        self.vision_model = _HFClipVisionTransformer(hidden, image_size, patch, layers, heads, mlp, hidden_act)
+        self.vision_model = _HFClipVisionTransformer(hidden, image_size, patch, layers, heads, mlp, hidden_act, eps)
         self.classifier = nn.Linear(hidden, num_labels)
 
     @classmethod
-    def from_state_dict(cls, sd, n_class=None, heads=None, hidden_act="quick_gelu"):
+    def from_state_dict(cls, sd, n_class=None, heads=None, hidden_act="quick_gelu", eps=1e-5):
         """The model of a CLIPForImageClassification (or hub CLIPModel) state dict: sized by hf_clip_config, fp16 tensors
         upcast, everything under vision_model. and classifier. loaded STRICTLY -- a missing or an unexpected key is an
         error, never a tower of random weights.  The names of _HF_CLIP_IGNORED are dropped, as from_pretrained drops them
@@ -2976,7 +2982,7 @@ class HFClip(nn.Module):
               if not k.startswith(_HF_CLIP_IGNORED)}
         cfg = hf_clip_config(sd, heads)
         cfg.setdefault("num_labels", 2 if n_class is None else n_class)
-        model = cls(hidden_act=hidden_act, **cfg)
+        model = cls(hidden_act=hidden_act, eps=eps, **cfg)
         want = set(model.state_dict())
         if not any(k.startswith("classifier.") for k in sd):
             want -= {"classifier.weight", "classifier.bias"}
@@ -3046,9 +3052,9 @@ class _MaeLayer(_Block):
 
 
 class _MaeEncoder(nn.Module):
-    def __init__(self, depth, dim, heads, mlp):
+    def __init__(self, depth, dim, heads, mlp, eps=1e-12):
         super().__init__()
-        self.layer = nn.ModuleList([_MaeLayer(dim, heads, mlp, eps=1e-12) for _ in range(depth)])
+        self.layer = nn.ModuleList([_MaeLayer(dim, heads, mlp, eps=eps) for _ in range(depth)])
 
     def forward(self, x, hip=False):
         for layer in self.layer:                     # through __call__: the hooks on layer[i] fire
@@ -3061,12 +3067,12 @@ class _MaeViT(nn.Module):
     forward(x, ids_keep) embeds the patches ids_keep [B, Lk] names, puts the class token in front and returns
     layernorm(encoder(.)) as [B, 1 + Lk, D]."""
 
-    def __init__(self, dim, image_size, patch, depth, heads, mlp):
+    def __init__(self, dim, image_size, patch, depth, heads, mlp, eps=1e-12):
         super().__init__()
         self.image_size, self.patch = image_size, patch
         self.embeddings = _HFEmbeddings(dim, patch, (image_size // patch) ** 2)
-        self.encoder = _MaeEncoder(depth, dim, heads, mlp)
-        self.layernorm = _LayerNorm(dim, eps=1e-12)
+        self.encoder = _MaeEncoder(depth, dim, heads, mlp, eps)
+        self.layernorm = _LayerNorm(dim, eps=eps)
 
     def embed(self, x, ids_keep, hip=False):
         emb = self.embeddings
@@ -3099,13 +3105,13 @@ class _MaeDecoder(nn.Module):
     """ViTMAEDecoder: decoder_embed, mask_token, decoder_pos_embed, decoder_layers[i], decoder_norm, decoder_pred.
     forward(latent [B, 1 + Lk, D], ids_restore [B, L]) -> the pixel predictions [B, L, patch^2 * 3] (the class row dropped)."""
 
-    def __init__(self, dim, num_patches, width, depth, heads, mlp, out_dim):
+    def __init__(self, dim, num_patches, width, depth, heads, mlp, out_dim, eps=1e-12):
         super().__init__()
         self.mask_token = nn.Parameter(torch.zeros(1, 1, width))
         self.decoder_pos_embed = nn.Parameter(torch.zeros(1, num_patches + 1, width), requires_grad=False)
         self.decoder_embed = nn.Linear(dim, width)
-        self.decoder_layers = nn.ModuleList([_MaeLayer(width, heads, mlp, eps=1e-12) for _ in range(depth)])
-        self.decoder_norm = _LayerNorm(width, eps=1e-12)
+        self.decoder_layers = nn.ModuleList([_MaeLayer(width, heads, mlp, eps=eps) for _ in range(depth)])
+        self.decoder_norm = _LayerNorm(width, eps=eps)
         self.decoder_pred = nn.Linear(width, out_dim)
 
     def forward(self, latent, ids_restore, hip=False):
@@ -3181,26 +3187,26 @@ class HFMae(nn.Module):
     and the decoder read every row: the last block always runs whole.  encode_image is forward."""
 
     def __init__(self, image_size=224, patch=16, hidden=768, layers=12, heads=12, mlp=3072, decoder_hidden=512,
-                 decoder_layers=8, decoder_heads=16, decoder_mlp=2048, mask_ratio=0.75, norm_pix_loss=False):
+                 decoder_layers=8, decoder_heads=16, decoder_mlp=2048, mask_ratio=0.75, norm_pix_loss=False, eps=1e-12):
         super().__init__()
         if not isinstance(image_size, int):
             raise ValueError("HFMae: image_size must be an int (the position table is a square grid), got %r" % (image_size,))
         self.mask_ratio, self.norm_pix_loss = float(mask_ratio), bool(norm_pix_loss)
         self.num_patches = (image_size // patch) ** 2
-        self.vit = _MaeViT(hidden, image_size, patch, layers, heads, mlp)
+        self.vit = _MaeViT(hidden, image_size, patch, layers, heads, mlp, eps)
         self.decoder = _MaeDecoder(hidden, self.num_patches, decoder_hidden, decoder_layers, decoder_heads, decoder_mlp,
-                                   patch * patch * 3)
+                                   patch * patch * 3, eps)
 
     def convert_state_dict(self, sd):
         sd = hf_state_dict(sd, "vit", len(self.vit.encoder.layer))
         return hf_state_dict(sd, "decoder", len(self.decoder.decoder_layers), stem="decoder_layers")
 
     @classmethod
-    def from_state_dict(cls, sd, heads=None, decoder_heads=None, mask_ratio=0.75, norm_pix_loss=False):
+    def from_state_dict(cls, sd, heads=None, decoder_heads=None, mask_ratio=0.75, norm_pix_loss=False, eps=1e-12):
         """The model of a ViTMAEForPreTraining state dict: sized by mae_config, fp16 tensors upcast, loaded STRICTLY -- a
         missing or an unexpected key is an error, never a tower of random weights."""
         sd = {k: (v.float() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in sd.items()}
-        model = cls(mask_ratio=mask_ratio, norm_pix_loss=norm_pix_loss, **mae_config(sd, heads, decoder_heads))
+        model = cls(mask_ratio=mask_ratio, norm_pix_loss=norm_pix_loss, eps=eps, **mae_config(sd, heads, decoder_heads))
         sd = model.convert_state_dict(sd)
         want = set(model.state_dict())
         missing, unexpected = sorted(want - set(sd)), sorted(set(sd) - want)
@@ -3969,22 +3975,276 @@ SENTENCE_CHECKPOINT = {}
 
 def register_sentence_checkpoint(path):
     """Where the sentence encoder's checkpoint lives: a LOCAL file holding an MPNetModel state dict (all-mpnet-base-v2's
-    pytorch_model.bin), which must exist now.  The environment variable MCD_MPNET_CKPT does the same for a process that
+    pytorch_model.bin or model.safetensors) or the snapshot directory itself, which must exist now; a directory's
+    vocab.txt becomes the `mpnet` vocabulary when none is registered.  The environment variable MCD_MPNET_CKPT does the same for a process that
     registers nothing."""
-    if not isinstance(path, str) or not os.path.isfile(path):
-        raise FileNotFoundError("register_sentence_checkpoint: %r is not an existing local file" % (path,))
+    if not isinstance(path, str) or not (os.path.isfile(path) or os.path.isdir(path)):
+        raise FileNotFoundError("register_sentence_checkpoint: %r is not an existing local file or snapshot directory" % (path,))
     SENTENCE_CHECKPOINT["path"] = path
+    vocab = os.path.join(path, "vocab.txt")
+    if os.path.isdir(path) and os.path.isfile(vocab) and "mpnet" not in TOKENIZER_VOCABS:
+        register_tokenizer("mpnet", vocab)
 
 
 def sentence_encoder(device, ckpt=None):
     """The MPNetSentenceEncoder of get_cos_similarity's mpnet_model argument, in eval mode on `device`: from ckpt (a state
-    dict or a LOCAL path), else from the registered checkpoint (register_sentence_checkpoint / MCD_MPNET_CKPT).  Files are
+    dict, a LOCAL file or a snapshot directory), else from the registered checkpoint (register_sentence_checkpoint / MCD_MPNET_CKPT).  Files are
     read with weights_only=True; the load is strict.  Nothing is downloaded: without a checkpoint this is an error."""
     ckpt = ckpt if ckpt is not None else SENTENCE_CHECKPOINT.get("path") or os.environ.get("MCD_MPNET_CKPT")
     if ckpt is None:
         raise RuntimeError("the sentence encoder needs a local MPNetModel checkpoint: pass ckpt=, call "
                            "data_utils.register_sentence_checkpoint('/path/pytorch_model.bin') or set MCD_MPNET_CKPT")
-    return MPNetSentenceEncoder.from_state_dict(_state_dict_of(ckpt)).to(device).eval()
+    sd = _state_dict_of(ckpt)
+    return MPNetSentenceEncoder.from_state_dict(sd, **snapshot_kwargs("mpnet", _config_of(ckpt), sd)).to(device).eval()
+
+
+# ------------------------------------------------------------------------------------------------------
+# config.json of a Hugging Face snapshot -> the mirrors' constructor arguments
+# ------------------------------------------------------------------------------------------------------
+def hf_vit_config(sd, prefix, heads=None):
+    """HFViT's / HFDinov2's constructor arguments read from the shapes of a ViTForImageClassification /
+    Dinov2ForImageClassification state dict (transformers' key names or the mirror's; prefix 'vit' / 'dinov2'): the width
+    from cls_token, the patch from the projection, the grid (and with it the resolution the position table was built for)
+    from the position rows, the depth by counting layers, the MLP width from the first layer, num_labels from
+    classifier.weight when the file has one (else the key is absent: the caller decides).  The state dict does not carry
+    the head count: width // 64 (every released ViT and DINOv2 has 64-wide heads) unless `heads` says otherwise."""
+    def shape(*keys):
+        for key in keys:
+            if key in sd:
+                return tuple(sd[key].shape)
+        raise RuntimeError("not a %s classifier's state dict: it lacks %r" % (prefix, keys[0]))
+    dim = shape(prefix + ".embeddings.cls_token")[2]
+    patch = shape(prefix + ".embeddings.patch_embeddings.projection.weight")[2]
+    rows = shape(prefix + ".embeddings.position_embeddings")[1]
+    grid = round((rows - 1) ** 0.5)
+    if grid * grid + 1 != rows:
+        raise RuntimeError("%s.embeddings.position_embeddings has %d rows: not a square grid plus one" % (prefix, rows))
+    stem = prefix + ".encoder.layer."
+    depth = len([k for k in sd if k.startswith(stem) and k.endswith((".layernorm_before.weight", ".norm1.weight"))])
+    first = stem + "0."
+    cfg = dict(image_size=grid * patch, patch=patch, dim=dim, depth=depth, heads=heads or max(1, dim // 64),
+               mlp=shape(first + "intermediate.dense.weight", first + "mlp.fc1.weight", first + "fc1.weight")[0] if depth
+               else 4 * dim)
+    if "classifier.weight" in sd:
+        cfg["num_labels"] = shape("classifier.weight")[0]
+    return cfg
+
+
+# family -> (the model_type values its config.json may carry, transformers' class defaults of the fields that are not in
+# a state dict: a config.json written as a difference to the defaults leaves such a field out)
+_SNAPSHOT_FAMILIES = {
+    "vit": (("vit",), dict(num_attention_heads=12, layer_norm_eps=1e-12, hidden_act="gelu", qkv_bias=True)),
+    "dino": (("dinov2",), dict(num_attention_heads=12, layer_norm_eps=1e-6, hidden_act="gelu", qkv_bias=True,
+                               layerscale_value=1.0, use_swiglu_ffn=False)),
+    "clip": (("clip", "clip_vision_model"), dict(num_attention_heads=12, layer_norm_eps=1e-5, hidden_act="quick_gelu")),
+    "openai_clip": (("clip",), dict(layer_norm_eps=1e-5, hidden_act="quick_gelu")),
+    "resnet": (("resnet",), dict(downsample_in_first_stage=False, downsample_in_bottleneck=False, layer_type="bottleneck",
+                                 hidden_act="relu")),
+    "mae": (("vit_mae",), dict(num_attention_heads=12, decoder_num_attention_heads=16, mask_ratio=0.75, norm_pix_loss=False,
+                               layer_norm_eps=1e-12, hidden_act="gelu", qkv_bias=True)),
+    "mpnet": (("mpnet",), dict(layer_norm_eps=1e-12, relative_attention_num_buckets=32, hidden_act="gelu")),
+}
+
+
+def _config_labels(config):
+    """num_labels of a config.json: the field itself, else the length of id2label (what transformers stores)."""
+    if "num_labels" in config:
+        return int(config["num_labels"])
+    return len(config["id2label"]) if isinstance(config.get("id2label"), dict) else None
+
+
+def snapshot_kwargs(family, config, sd=None):
+    """The keyword arguments a snapshot's config.json adds to a mirror's constructor / from_state_dict: what a state dict
+    does not carry (head counts, LayerNorm eps, the activation, MAE's mask_ratio / norm_pix_loss, the HF ResNet's
+    downsample_* flags, ...).  family: 'vit' (HFViT), 'dino' (HFDinov2), 'clip' (HFClip; a CLIPModel config's
+    vision_config, or a clip_vision_model one), 'resnet' (HFResNet), 'mae' (HFMae), 'mpnet' (MPNetSentenceEncoder),
+    'openai_clip' (OpenAIClip from a CLIPModel snapshot: hf_clip_to_openai).  config None: {} -- the shape-based guesses
+    stay as they are.
+    A model_type that is not the family's is a ValueError; a configuration the mirror cannot compute (use_swiglu_ffn,
+    another activation, qkv_bias false, ...) a NotImplementedError naming the field; with `sd`, a field that the state
+    dict's shapes give as well (widths, depths, patch, grid, classifier width) and give differently a RuntimeError naming
+    the field and both values."""
+    if config is None:
+        return {}
+    types, defaults = _SNAPSHOT_FAMILIES[family]
+    kind = config.get("model_type")
+    if kind not in types:
+        raise ValueError("config.json describes a %r model, which is not the %r target's family (model_type %s)"
+                         % (kind, family, " or ".join(repr(t) for t in types)))
+    top = config
+
+    def tower(name):
+        sub = top.get(name) if kind == "clip" else top
+        if not isinstance(sub, dict):
+            raise ValueError("config.json of model_type 'clip' has no %s object" % name)
+        return sub
+
+    def get(cfg, field):
+        return cfg[field] if field in cfg and cfg[field] is not None else defaults[field]
+
+    def refuse(field, value, takes):
+        raise NotImplementedError("config.json: %s = %r is not something %s computes (it takes %s)"
+                                  % (field, value, family, takes))
+
+    def act(cfg, allowed, field="hidden_act"):
+        value = get(cfg, field)
+        if value not in allowed:
+            refuse(field, value, " or ".join(repr(a) for a in allowed))
+        return value
+
+    def agree(cfg, pairs, shapes, where=""):
+        for field, key in pairs:
+            if field in cfg and cfg[field] is not None and key in shapes:
+                a, b = cfg[field], shapes[key]
+                if isinstance(b, (list, tuple)):
+                    a, b = list(a) if isinstance(a, (list, tuple)) else a, list(b)
+                if a != b:
+                    raise RuntimeError("config.json says %s%s = %r, the state dict's shapes say %r" % (where, field, a, b))
+
+    if family in ("vit", "dino", "mae"):
+        if not get(config, "qkv_bias"):
+            refuse("qkv_bias", config["qkv_bias"], "projections with a bias")
+        act(config, ("gelu",))
+    if family in ("vit", "dino"):
+        out = dict(heads=int(get(config, "num_attention_heads")), eps=float(get(config, "layer_norm_eps")))
+        if family == "dino":
+            if get(config, "use_swiglu_ffn"):
+                refuse("use_swiglu_ffn", True, "the fc1 / GELU / fc2 MLP")
+            out["layer_scale"] = float(get(config, "layerscale_value"))
+        if sd is not None:
+            shapes = hf_vit_config(sd, "vit" if family == "vit" else "dinov2")
+            if family == "dino" and config.get("mlp_ratio") is not None and config.get("hidden_size") is not None:
+                shapes["mlp_ratio_width"] = shapes["mlp"]
+                config = dict(config, mlp_ratio_width=int(config["hidden_size"] * config["mlp_ratio"]))
+            labels = _config_labels(config)
+            agree(dict(config, num_labels=labels),
+                  (("hidden_size", "dim"), ("num_hidden_layers", "depth"), ("intermediate_size", "mlp"), ("patch_size", "patch"),
+                   ("image_size", "image_size"), ("num_labels", "num_labels"), ("mlp_ratio_width", "mlp_ratio_width")), shapes)
+        return out
+    if family == "clip":
+        vision = tower("vision_config")
+        out = dict(heads=int(get(vision, "num_attention_heads")), hidden_act=act(vision, ("quick_gelu", "gelu")),
+                   eps=float(get(vision, "layer_norm_eps")))
+        if sd is not None and HF_CLIP_KEY in sd:
+            agree(dict(vision, num_labels=_config_labels(top) if any(k.startswith("classifier.") for k in sd) else None),
+                  (("hidden_size", "hidden"), ("num_hidden_layers", "layers"), ("intermediate_size", "mlp"),
+                   ("patch_size", "patch"), ("image_size", "image_size"), ("num_labels", "num_labels")),
+                  hf_clip_config(sd), "vision_config." if kind == "clip" else "")
+        return out
+    if family == "openai_clip":
+        vision, text = tower("vision_config"), tower("text_config")
+        for name, cfg in (("vision_config", vision), ("text_config", text)):
+            act(cfg, ("quick_gelu",))
+            if float(get(cfg, "layer_norm_eps")) != 1e-5:
+                refuse(name + ".layer_norm_eps", cfg["layer_norm_eps"], "1e-05")
+        out = {}
+        if vision.get("num_attention_heads") is not None:
+            out["vision_heads"] = int(vision["num_attention_heads"])
+        if text.get("num_attention_heads") is not None:
+            out["transformer_heads"] = int(text["num_attention_heads"])
+        if sd is not None:
+            shapes = openai_clip_config(sd)
+            agree(vision, (("hidden_size", "vision_width"), ("num_hidden_layers", "vision_layers"),
+                           ("patch_size", "vision_patch_size"), ("image_size", "image_resolution")), shapes, "vision_config.")
+            agree(text, (("hidden_size", "transformer_width"), ("num_hidden_layers", "transformer_layers"),
+                         ("vocab_size", "vocab_size"), ("max_position_embeddings", "context_length")), shapes, "text_config.")
+            agree(top, (("projection_dim", "embed_dim"),), shapes)
+        return out
+    if family == "resnet":
+        act(config, ("relu",))
+        out = dict(downsample_in_first_stage=bool(get(config, "downsample_in_first_stage")),
+                   downsample_in_bottleneck=bool(get(config, "downsample_in_bottleneck")))
+        if get(config, "layer_type") not in ("basic", "bottleneck"):
+            refuse("layer_type", config["layer_type"], "'basic' or 'bottleneck'")
+        if sd is not None:
+            agree(dict(config, num_labels=_config_labels(config) if "classifier.1.weight" in sd else None),
+                  (("num_channels", "num_channels"), ("embedding_size", "embedding_size"), ("hidden_sizes", "hidden_sizes"),
+                   ("depths", "depths"), ("layer_type", "layer_type"), ("num_labels", "num_labels")), hf_resnet_config(sd))
+        return out
+    if family == "mae":
+        out = dict(heads=int(get(config, "num_attention_heads")), decoder_heads=int(get(config, "decoder_num_attention_heads")),
+                   mask_ratio=float(get(config, "mask_ratio")), norm_pix_loss=bool(get(config, "norm_pix_loss")),
+                   eps=float(get(config, "layer_norm_eps")))
+        if sd is not None:
+            agree(config, (("hidden_size", "hidden"), ("num_hidden_layers", "layers"), ("intermediate_size", "mlp"),
+                           ("patch_size", "patch"), ("image_size", "image_size"), ("decoder_hidden_size", "decoder_hidden"),
+                           ("decoder_num_hidden_layers", "decoder_layers"), ("decoder_intermediate_size", "decoder_mlp")),
+                  mae_config(sd))
+        return out
+    act(config, ("gelu",))                                                                         # mpnet
+    out = dict(eps=float(get(config, "layer_norm_eps")))
+    if sd is not None:
+        shapes = {}
+        for key, axis, name in (("embeddings.word_embeddings.weight", 0, "vocab_size"),
+                                ("embeddings.word_embeddings.weight", 1, "hidden_size"),
+                                ("embeddings.position_embeddings.weight", 0, "max_position_embeddings"),
+                                ("encoder.relative_attention_bias.weight", 0, "relative_attention_num_buckets"),
+                                ("encoder.relative_attention_bias.weight", 1, "num_attention_heads"),
+                                ("encoder.layer.0.intermediate.dense.weight", 0, "intermediate_size")):
+            if key in sd:
+                shapes[name] = tuple(sd[key].shape)[axis]
+        shapes["num_hidden_layers"] = len([k for k in sd if k.startswith("encoder.layer.") and k.endswith(".attention.attn.q.weight")])
+        agree(dict(config, relative_attention_num_buckets=get(config, "relative_attention_num_buckets")),
+              tuple((name, name) for name in shapes), shapes)
+    return out
+
+
+def hf_clip_to_openai(sd, config=None):
+    """A transformers CLIPModel state dict (openai/clip-vit-*'s model.safetensors) under OpenAI's names, so that
+    OpenAIClip.from_state_dict loads it strictly.  The two layouts dictate the rules: q_proj | k_proj | v_proj concatenated
+    into attn.in_proj_weight / in_proj_bias; visual_projection.weight and text_projection.weight transposed into
+    visual.proj and text_projection; pre_layrnorm -> ln_pre, post_layernorm -> ln_post, final_layer_norm -> ln_final;
+    layer_norm1 / 2 -> ln_1 / 2; mlp.fc1 / fc2 -> mlp.c_fc / c_proj; the patch convolution, the class and position tables
+    under visual.conv1 / class_embedding / positional_embedding; position_ids buffers dropped.  config (the snapshot's
+    config.json) is checked by snapshot_kwargs('openai_clip', ...); only the ViT CLIPs exist in this format."""
+    if config is not None:
+        snapshot_kwargs("openai_clip", config)
+    fixed = {"vision_model.embeddings.class_embedding": "visual.class_embedding",
+             "vision_model.embeddings.patch_embedding.weight": "visual.conv1.weight",
+             "vision_model.embeddings.position_embedding.weight": "visual.positional_embedding",
+             "text_model.embeddings.token_embedding.weight": "token_embedding.weight",
+             "text_model.embeddings.position_embedding.weight": "positional_embedding",
+             "logit_scale": "logit_scale"}
+    norms = {"vision_model.pre_layrnorm.": "visual.ln_pre.", "vision_model.post_layernorm.": "visual.ln_post.",
+             "text_model.final_layer_norm.": "ln_final."}
+    towers = {"vision_model.encoder.layers.": "visual.transformer.resblocks.", "text_model.encoder.layers.": "transformer.resblocks."}
+    inner = {"self_attn.out_proj.": "attn.out_proj.", "layer_norm1.": "ln_1.", "layer_norm2.": "ln_2.", "mlp.fc1.": "mlp.c_fc.",
+             "mlp.fc2.": "mlp.c_proj."}
+    out, qkv = {}, {}
+    for key, value in sd.items():
+        if key.endswith(".position_ids"):
+            continue
+        if key in fixed:
+            out[fixed[key]] = value
+        elif key == "visual_projection.weight":
+            out["visual.proj"] = value.t().contiguous()
+        elif key == "text_projection.weight":
+            out["text_projection"] = value.t().contiguous()
+        elif key.startswith(tuple(norms)):
+            old = next(n for n in norms if key.startswith(n))
+            out[norms[old] + key[len(old):]] = value
+        elif key.startswith(tuple(towers)):
+            old = next(t for t in towers if key.startswith(t))
+            index, _, rest = key[len(old):].partition(".")
+            base = towers[old] + index + "."
+            part = next((p for p in ("q_proj", "k_proj", "v_proj") if rest.startswith("self_attn.%s." % p)), None)
+            if part is not None:
+                qkv.setdefault((base, rest.rsplit(".", 1)[1]), {})[part] = value
+                continue
+            name = next((n for n in inner if rest.startswith(n)), None)
+            if name is None:
+                raise RuntimeError("not a CLIPModel state dict: %r has no OpenAI name" % (key,))
+            out[base + inner[name] + rest[len(name):]] = value
+        else:
+            raise RuntimeError("not a CLIPModel state dict: %r has no OpenAI name" % (key,))
+    for (base, leaf), parts in qkv.items():
+        if sorted(parts) != ["k_proj", "q_proj", "v_proj"]:
+            raise RuntimeError("%sself_attn: q_proj, k_proj and v_proj %s must come together" % (base, leaf))
+        out["%sattn.in_proj_%s" % (base, leaf)] = torch.cat([parts["q_proj"], parts["k_proj"], parts["v_proj"]], dim=0)
+    return out
+
+
+HF_CLIP_MODEL_KEY = "text_model.embeddings.token_embedding.weight"       # what tells a CLIPModel state dict (with HF_CLIP_KEY)
 
 
 # target name -> a LOCAL checkpoint of that target, like register_clip_checkpoint for the dissector
@@ -3998,13 +4258,15 @@ class RegisteredCheckpoint(str):
 
 
 def register_target_checkpoint(name, path):
-    """Where the checkpoint of --target_model `name` lives (a state dict file or {'model': state dict}; local paths
-    only, and the file must exist now).  The drivers then build that target from it: for `clip` an HFClip sized from the
+    """Where the checkpoint of --target_model `name` lives (a state dict file or {'model': state dict}, a .safetensors
+    file, or a Hugging Face snapshot directory, whose config.json then sizes the model: snapshot_kwargs; local paths
+    only, and the path must exist now).  The drivers then build that target from it: for `clip` an HFClip sized from the
     file; for every other target that is not a breastclip* one, the file in place of the Mammo-CLIP checkpoint.  The
     environment variable MCD_TARGET_CKPTS names a JSON file {name: path} that does the same for a process that registers
     nothing."""
-    if not isinstance(path, str) or not os.path.isfile(path):
-        raise FileNotFoundError("register_target_checkpoint(%r): %r is not an existing local file" % (name, path))
+    if not isinstance(path, str) or not (os.path.isfile(path) or os.path.isdir(path)):
+        raise FileNotFoundError("register_target_checkpoint(%r): %r is not an existing local file or snapshot directory"
+                                % (name, path))
     TARGET_CHECKPOINTS[name] = path
 
 
@@ -4022,8 +4284,9 @@ def target_checkpoint(name):
                 raise ValueError("MCD_TARGET_CKPTS=%r: the file must hold one JSON object {target name: path}" % (table,))
             _TARGET_TABLE.update(stamp=stamp, entries=entries)
         path = _TARGET_TABLE["entries"].get(name)
-        if path is not None and not (isinstance(path, str) and os.path.isfile(path)):
-            raise FileNotFoundError("MCD_TARGET_CKPTS=%r: %r -> %r is not an existing local file" % (table, name, path))
+        if path is not None and not (isinstance(path, str) and (os.path.isfile(path) or os.path.isdir(path))):
+            raise FileNotFoundError("MCD_TARGET_CKPTS=%r: %r -> %r is not an existing local file or snapshot directory"
+                                    % (table, name, path))
     return None if path is None else RegisteredCheckpoint(path)
 
 
@@ -4044,15 +4307,24 @@ _BERT_IGNORED = (BERT_PREFIX + "pooler.", BERT_PREFIX + "embeddings.position_ids
 
 def _state_dict_of(ckpt):
     """The state dict in ckpt: a state dict, {'model': state dict} (reference utils.py:451-455), or a LOCAL path to
-    either (loaded with weights_only=True: nothing from the file is executed)."""
+    either (loaded with weights_only=True: nothing from the file is executed), to a .safetensors file or to a Hugging
+    Face snapshot directory (checkpoint_io.resolve_checkpoint)."""
     if isinstance(ckpt, str):
-        ckpt = torch.load(ckpt, map_location="cpu", weights_only=True)
+        ckpt = checkpoint_io.resolve_checkpoint(ckpt).state_dict()
     return ckpt["model"] if isinstance(ckpt, dict) and "model" in ckpt else ckpt
 
 
-def _load_local(model, ckpt, text_strict=False):
+def _config_of(ckpt):
+    """The parsed config.json that comes with ckpt: a snapshot directory's, or the one beside a .safetensors file; None
+    for a state dict and for a torch file (those never carried one: the shapes size the model, as before)."""
+    if isinstance(ckpt, str) and checkpoint_io.is_snapshot_path(ckpt):
+        return checkpoint_io.resolve_checkpoint(ckpt).config
+    return None
+
+
+def _load_local(model, ckpt, text_strict=False, sd=None):
     """ckpt: None, a state dict, {'model': state dict} (reference utils.py:451-455), or a LOCAL path
-    (loaded with weights_only=True: nothing from the file is executed).
+    (_state_dict_of: nothing from the file is executed); sd: ckpt's state dict when the caller has read it already.
     text_strict (a BreastClip with the BERT tower): the text side loads strictly -- pooler.* and
     embeddings.position_ids are ignored by name (BertTextTower has no pooler; 4.41.1 no longer stores the buffer, older
     checkpoints do), any other missing or unexpected key under text_encoder. is an error instead of a tower of random
@@ -4060,7 +4332,7 @@ def _load_local(model, ckpt, text_strict=False):
     way whenever the state dict has a key under image_encoder. at all."""
     if ckpt is None:
         return model
-    sd = _state_dict_of(ckpt)
+    sd = _state_dict_of(ckpt) if sd is None else sd
     if isinstance(model, (_HFClassifier, HFMae)):    # transformers' key names -> the mirror's
         sd = model.convert_state_dict(sd)
     if text_strict:
@@ -4109,6 +4381,11 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
                      text_tower=None, use_registered=True):
     """Returns (target model in eval mode, preprocess) -- reference data_utils.py:38-93.  Weights are
     random-init under `seed` unless a local checkpoint is given; nothing is downloaded.
+    ckpt / finetuned_ckpt: a state dict, {'model': state dict}, or a LOCAL path -- a torch file, a .safetensors file or a
+    Hugging Face snapshot directory (checkpoint_io.resolve_checkpoint).  A directory's (or a .safetensors file's)
+    config.json gives what the shapes do not -- head counts, LayerNorm eps, activation, MAE's mask_ratio, the HF ResNet's
+    downsample_* flags (snapshot_kwargs) -- and must agree with the shapes; `vit` / `dino` are sized from such a
+    checkpoint's shapes (hf_vit_config).  `openai_clip` also takes a transformers CLIPModel snapshot (hf_clip_to_openai).
     image_size: input resolution of the ViT towers, an int (square) or (H, W) (position embeddings are sized for it;
     the reference's HF ViT is built for its checkpoint's resolution the same way); also accepted as a suffix,
     'breastclip_vit_1024' or 'breastclip_vit_1520x912' (H x W, Mammo-CLIP's own input).  The attention is HIP at
@@ -4130,27 +4407,36 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
         # sized from its shapes and loaded strictly; without ckpt, ViT-B/16's configuration with seeded weights
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(seed)
-            model = OpenAIClip(**VIT_B16) if ckpt is None else OpenAIClip.from_state_dict(openai_clip_state_dict(ckpt))
+            if ckpt is None:
+                model = OpenAIClip(**VIT_B16)
+            else:
+                sd, heads = openai_clip_state_dict(ckpt), {}
+                config = _config_of(ckpt)
+                if HF_CLIP_KEY in sd and HF_CLIP_MODEL_KEY in sd:
+                    # a transformers CLIPModel (the hub's openai/clip-vit-*): OpenAI's names, the head counts of config.json
+                    sd = hf_clip_to_openai(sd, config)
+                    heads = snapshot_kwargs("openai_clip", config, sd)
+                model = OpenAIClip.from_state_dict(sd, **heads)
         return model.to(device).eval(), None
     if target_name in HF_CLIP_TARGETS:
         # transformers' CLIPForImageClassification when a checkpoint of it is at hand: `ckpt` itself when it carries the
         # vision tower's keys, else the one registered for the name (`clip`, or the fine-tunes `clip-cub` /
         # `clip-bloodmnist`, which exist only with such a checkpoint: without one they fall to the ValueError below).  Sized from the shapes (a fine-tuned clip-cub /
         # clip-bloodmnist file is this target with that file) and loaded strictly.  Without either, the stand-in below.
-        sd = None
+        sd = config = None
         if ckpt is not None:
             loaded = _state_dict_of(ckpt)
             if HF_CLIP_KEY in loaded or isinstance(ckpt, RegisteredCheckpoint):
-                sd = loaded
+                sd, config = loaded, _config_of(ckpt)
             else:
                 ckpt = loaded                    # read once: the stand-in below loads from the state dict
         if sd is None and use_registered:
             registered = target_checkpoint(target_name)
-            sd = None if registered is None else _state_dict_of(registered)
+            sd, config = (None, None) if registered is None else (_state_dict_of(registered), _config_of(registered))
         if sd is not None:
             with torch.random.fork_rng(devices=[]):
                 torch.manual_seed(seed)
-                model = HFClip.from_state_dict(sd, n_class=n_class)
+                model = HFClip.from_state_dict(sd, n_class=n_class, **snapshot_kwargs("clip", config, sd))
             _load_local(model, finetuned_ckpt)
             return model.to(device).eval(), None
     if target_name in HF_RESNET_TARGETS:
@@ -4158,18 +4444,18 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
         # it: `ckpt` itself when it carries HF_RESNET_KEY (or is the registered file), else the one registered for the name.
         # Sized from the shapes, the classifier's width included, and loaded strictly.  Without either the name stays
         # unknown (the ValueError below).
-        sd = None
+        sd = config = None
         if ckpt is not None:
             loaded = _state_dict_of(ckpt)
             if isinstance(ckpt, RegisteredCheckpoint) or (isinstance(loaded, dict) and HF_RESNET_KEY in loaded):
-                sd = loaded
+                sd, config = loaded, _config_of(ckpt)
         if sd is None and use_registered:
             registered = target_checkpoint(target_name)
-            sd = None if registered is None else _state_dict_of(registered)
+            sd, config = (None, None) if registered is None else (_state_dict_of(registered), _config_of(registered))
         if sd is not None:
             with torch.random.fork_rng(devices=[]):
                 torch.manual_seed(seed)
-                model = HFResNet.from_state_dict(sd, n_class=n_class)
+                model = HFResNet.from_state_dict(sd, n_class=n_class, **snapshot_kwargs("resnet", config, sd))
             _load_local(model, finetuned_ckpt)
             return model.to(device).eval(), None
     if target_name == "mae":
@@ -4177,18 +4463,31 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
         # the registered file), else the one registered for `mae`.  Sized from the shapes and loaded strictly; n_class is
         # ignored (the model has no classifier).  Without either the name stays unknown (the ValueError below): a seeded
         # stand-in of a pre-training model would dissect nothing anybody trained.
-        sd = None
+        sd = config = None
         if ckpt is not None:
             loaded = _state_dict_of(ckpt)
             if isinstance(ckpt, RegisteredCheckpoint) or (isinstance(loaded, dict) and all(k in loaded for k in MAE_KEYS)):
-                sd = loaded
+                sd, config = loaded, _config_of(ckpt)
         if sd is None and use_registered:
             registered = target_checkpoint("mae")
-            sd = None if registered is None else _state_dict_of(registered)
+            sd, config = (None, None) if registered is None else (_state_dict_of(registered), _config_of(registered))
         if sd is not None:
-            model = HFMae.from_state_dict(sd)
+            model = HFMae.from_state_dict(sd, **snapshot_kwargs("mae", config, sd))
             _load_local(model, finetuned_ckpt)
             return model.to(device).eval(), None
+    hf_kw, hf_sd = {}, None
+    if target_name in HF_TARGETS and ckpt is not None:
+        # a ViTForImageClassification / Dinov2ForImageClassification checkpoint sizes the tower: the widths, the patch, the
+        # position table's resolution and the classifier's width from its shapes (hf_vit_config), the head count, the
+        # LayerNorm eps and DINOv2's LayerScale value from a snapshot's config.json (snapshot_kwargs).  A state dict
+        # without the tower's embedding keys (a partial one) leaves the base configuration, as before.
+        hf_sd, prefix = _state_dict_of(ckpt), HF_TARGETS[target_name][0].prefix
+        config = _config_of(ckpt)
+        if isinstance(hf_sd, dict) and prefix + ".embeddings.cls_token" in hf_sd:
+            hf_kw = hf_vit_config(hf_sd, prefix)
+            hf_kw.update(snapshot_kwargs("vit" if prefix == "vit" else "dino", config, hf_sd))
+        elif config is not None:
+            snapshot_kwargs("vit" if prefix == "vit" else "dino", config)      # a wrong family is an error all the same
     text_kw = {}
     if target_name.startswith("breastclip") and target_name != "breastclip_classifier" and (ckpt is not None or text_tower):
         if ckpt is not None:
@@ -4244,8 +4543,8 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
             model = ClipResNet(layers, embed, image_size=image_size)
         elif target_name in HF_TARGETS:
             cls, width = HF_TARGETS[target_name]
-            model = cls(num_labels=width if width is not None else (2 if n_class is None else n_class),
-                        image_size=image_size)
+            labels = hf_kw.pop("num_labels", width if width is not None else (2 if n_class is None else n_class))
+            model = cls(num_labels=labels, **dict({"image_size": image_size}, **hf_kw))
         else:
             raise ValueError("unknown target model %r (offline build: breastclip, breastclip_vit, breastclip_swin, "
                              "breastclip_classifier, clip, openai_clip, clip_rn50, clip_rn101, resnet18, resnet18_places, resnet34, "
@@ -4257,7 +4556,7 @@ def get_target_model(target_name, device, args=None, ckpt=None, n_class=None, fi
     if target_name == "resnet18_places":
         _load_places(model, ckpt)
     else:
-        _load_local(model, ckpt, text_strict=bool(text_kw))
+        _load_local(model, ckpt, text_strict=bool(text_kw), sd=hf_sd)
     _load_local(model, finetuned_ckpt)
     return model.to(device).eval(), None
 

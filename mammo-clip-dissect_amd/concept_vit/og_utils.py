@@ -33,12 +33,14 @@ CLIP_DISSECTORS = {"RN50": "clip_rn50", "RN101": "clip_rn101"}
 
 def _clip_dissector(device, clip_name="ViT-B/16"):
     """(dissector, tokenize) for --clip_model `clip_name` (reference: clip.load(clip_name), clip.tokenize).
-    With a checkpoint -- `clip_name` an existing local file, the path clip.load takes as well, or a name with a
+    With a checkpoint -- `clip_name` an existing local file, the path clip.load takes as well (or a snapshot directory of
+    transformers' CLIPModel, e.g. the hub's openai/clip-vit-base-patch16), or a name with a
     registered checkpoint (data_utils.register_clip_checkpoint / MCD_CLIP_CKPTS) -- OpenAI CLIP itself: OpenAIClip sized
     from the checkpoint, ViT or ResNet, with the ClipBPETokenizer of the registered merges file at the model's context
     length.  Without one, the shaped stand-ins as before: ClipResNet for RN50 / RN101, ClipViT otherwise, with the
     hashing tokenizer."""
-    ckpt = clip_name if isinstance(clip_name, str) and os.path.isfile(clip_name) else data_utils.clip_checkpoint(clip_name)
+    ckpt = (clip_name if isinstance(clip_name, str) and (os.path.isfile(clip_name) or os.path.isdir(clip_name))
+            else data_utils.clip_checkpoint(clip_name))
     if ckpt is not None:
         model, _ = data_utils.get_target_model("openai_clip", device, ckpt=ckpt)
         return model, model.tokenize
